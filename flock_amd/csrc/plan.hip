@@ -462,6 +462,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
     const Node *L = n->in[0].get(), *R = n->in[1].get();
     const size_t nl = L->schema.size();
     const Field &lk = L->schema[(size_t)n->on_l], &rk = R->schema[(size_t)n->on_r];
+    if (!n->on_lx.empty()) return;   // (more than two key pairs: no fused pipeline reads a third one)
     if (n->on_l2 >= 0) {
         // ---- q9: bid JOIN Q ON auction = id AND price = final (q9.sql, q9_plan.fmt)
         std::vector<int> lmap;
@@ -763,6 +764,7 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     for (int c : n->group) *o += std::to_string(c) + ",";
     for (auto &a : n->aggs) *o += a.fn + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
     *o += "|" + std::to_string(n->on_l) + "," + std::to_string(n->on_r) + "," + std::to_string(n->on_l2) + "," + std::to_string(n->on_r2) + (n->join_partitioned ? "p" : "") + "|";
+    for (size_t k = 0; k < n->on_lx.size(); ++k) *o += std::to_string(n->on_lx[k]) + "=" + std::to_string(n->on_rx[k]) + ",";   // (pairs after the second)
     for (int c : n->hash_cols) *o += std::to_string(c) + ",";
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
     for (auto &k : n->sort_cols) *o += std::to_string(k.col) + (k.descending ? "d" : "a") + (k.nulls_first ? "f" : "l") + ",";
@@ -2092,6 +2094,15 @@ struct Exec {
                 TCol lk, rk;
                 FG_TRY(lazy_key(n, ZL, n->on_l, "lzkl", &lk));
                 FG_TRY(lazy_key(n, ZR, n->on_r, "lzkr", &rk));
+                // key pairs no path below takes -- more than two, or two that are not both Int32 without NULLs -- join on composite-key ids
+                // (two pairs of which one cannot compare -- a Float64 column, Utf8 against an integer, signed against UInt64 -- keep today's path and message)
+                if (n->on_l2 >= 0) {
+                    const TCol &l2 = L.cols[(size_t)n->on_l2], &r2 = R.cols[(size_t)n->on_r2];
+                    const bool i32_pairs = lk.c.type == ColType::I32 && rk.c.type == ColType::I32 && l2.c.type == ColType::I32 && r2.c.type == ColType::I32 &&
+                                           !lk.c.valid && !rk.c.valid && !l2.c.valid && !r2.c.valid;
+                    if (!n->on_lx.empty() || (!i32_pairs && keys_comparable(lk.c.type, rk.c.type) && keys_comparable(l2.c.type, r2.c.type)))
+                        return exec_join_composite(n, ZL, ZR, lk, rk, t);
+                }
                 const bool text_keys = lk.c.type == ColType::UTF8 && rk.c.type == ColType::UTF8 && n->on_l2 < 0;
                 if (!text_keys && ((lk.c.type == ColType::U64) != (rk.c.type == ColType::U64) || lk.c.type == ColType::UTF8 || rk.c.type == ColType::UTF8 ||
                                    lk.c.type == ColType::F64 || rk.c.type == ColType::F64))
@@ -2187,6 +2198,62 @@ struct Exec {
         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: unknown node");
     }
 
+    // A join on several key pairs of any integer / Utf8 types, NULLs allowed (a NULL in any key column matches nothing): the smaller side's
+    // tuples get dense ids (relops.hpp key_codes), the other side looks its tuples up among them, and the dense join pairs the ids -- the way
+    // the one-pair Utf8 join pairs dictionary codes.
+    // a join key pair the composite ids can compare: two Utf8 columns, or two integer columns of one signedness
+    static bool keys_comparable(ColType x, ColType y) {
+        return x != ColType::F64 && y != ColType::F64 && (x == ColType::UTF8) == (y == ColType::UTF8) && (x == ColType::U64) == (y == ColType::U64);
+    }
+    // lk0 / rk0: pair 0's key columns, already taken by the caller
+    int exec_join_composite(const Node *n, const Lazy &ZL, const Lazy &ZR, const TCol &lk0, const TCol &rk0, Table *t) {
+        std::vector<int> on_l{n->on_l, n->on_l2}, on_r{n->on_r, n->on_r2};
+        on_l.insert(on_l.end(), n->on_lx.begin(), n->on_lx.end());
+        on_r.insert(on_r.end(), n->on_rx.begin(), n->on_rx.end());
+        const int np = (int)on_l.size();
+        if (np > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a join on more than %d key pairs", kMaxKeyCols);
+        DevColumn kl[kMaxKeyCols], kr[kMaxKeyCols];
+        int64_t nl = ZL.rows, nr = ZR.rows;
+        for (int p = 0; p < np; ++p) {
+            TCol a = lk0, b = rk0;
+            if (p > 0) {
+                FG_TRY(lazy_key(n, ZL, on_l[(size_t)p], ("ckl" + std::to_string(p)).c_str(), &a));
+                FG_TRY(lazy_key(n, ZR, on_r[(size_t)p], ("ckr" + std::to_string(p)).c_str(), &b));
+            }
+            if (!keys_comparable(a.c.type, b.c.type))
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
+            if (a.c.all_null) nl = 0;   // NULL keys never match
+            if (b.c.all_null) nr = 0;
+            if ((!a.present && !a.c.all_null) || (!b.present && !b.c.all_null)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
+            kl[p] = a.c;
+            kr[p] = b.c;
+        }
+        int32_t *lrows = nullptr, *rrows = nullptr;
+        int64_t pairs = 0;
+        if (nl > 0 && nr > 0) {
+            const bool build_right = nr < nl;   // (the ids go on the smaller side; which side is hashed is unobservable in the pair multiset)
+            const int64_t nb = build_right ? nr : nl, npr = build_right ? nl : nr;
+            int32_t *bg = nullptr, *pg = nullptr, *first = nullptr;
+            int64_t groups = 0;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcb").c_str(), (size_t)nb + 4, &bg));
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcp").c_str(), (size_t)npr + 4, &pg));
+            FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), build_right ? kr : kl, np, nb, bg, &groups, &first, build_right ? kl : kr, npr, pg));
+            DevColumn cb, cp;
+            cb.type = cp.type = ColType::I32;
+            cb.values = bg;
+            cp.values = pg;
+            FG_TRY(join_dense(ctx, node_key(pl, n, "join").c_str(), cb, nb, 0, groups - 1, cp, npr, build_right ? &rrows : &lrows, build_right ? &lrows : &rrows,
+                              &pairs));
+        } else {   // an empty side: no pairs (the one-key join's answer to it)
+            int64_t *none = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kc0").c_str(), 2, &none));
+            FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), none, 0, none, 0, &lrows, &rrows, &pairs));
+        }
+        t->rows = pairs;
+        FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
+        return take_lazy(n, ZR, rrows, pairs, (int)ZL.base.cols.size(), "lzrr", t);
+    }
+
     // SortExec [+ GlobalLimitExec]: the stable order of relops.hpp's sort_rows, then one take of the columns somebody reads
     int exec_sort(const Node *n, int64_t limit, Table *t) {
         Table in;
@@ -2237,6 +2304,55 @@ struct Exec {
         return true;
     }
 
+    // GROUP BY on composite-key ids: gid in [0, G) in order of first appearance, then the dense GROUP BY over the ids (groups come out in id
+    // order) where its accumulators allow, else the hashed one with its groups put back in id order.  g->first_row: the groups' first rows.
+    int group_composite(const Node *n, const Table &in, const AggSpec *specs, int n_specs, GroupResultN *g) {
+        const int nk = (int)n->group.size();
+        DevColumn kc[kMaxKeyCols];
+        for (int c = 0; c < nk; ++c) {
+            const TCol &k = in.cols[(size_t)n->group[(size_t)c]];
+            if (!k.present || k.c.all_null) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a column that was not materialised");
+            kc[c] = k.c;
+        }
+        int32_t *gid = nullptr, *first = nullptr;
+        int64_t groups = 0;
+        FG_TRY(arena_get_t(ctx, node_key(pl, n, "gid").c_str(), (size_t)in.rows + 4, &gid));
+        FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), kc, nk, in.rows, gid, &groups, &first, nullptr, 0, nullptr));
+        *g = GroupResultN{};
+        if (n_specs > 0) {
+            bool dense = groups > 0;
+            for (int a = 0; a < n_specs && dense; ++a)
+                dense = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
+            if (dense) {
+                DevColumn ids;
+                ids.type = ColType::I32;
+                ids.values = gid;
+                FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), ids, in.rows, 0, groups - 1, specs, n_specs, g));
+            } else {
+                int64_t *ids = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "gid64").c_str(), (size_t)in.rows + 2, &ids));
+                DevColumn gc;
+                gc.type = ColType::I32;
+                gc.values = gid;
+                if (in.rows > 0) FG_TRY(widen_to_i64(ctx, gc, in.rows, ids));
+                GroupResultN h;
+                FG_TRY(group_by_key64_n(ctx, node_key(pl, n, "grp").c_str(), ids, in.rows, specs, n_specs, &h, nullptr));
+                // (every id in [0, G) is one group: the accumulators go to position id)
+                for (int a = 0; a < n_specs; ++a) {
+                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "gacc", a).c_str(), (size_t)groups + 2, &g->agg[a]));
+                    FG_TRY(scatter_by_id_u64(ctx, h.keys, h.n_groups, h.agg[a], g->agg[a]));
+                    if (h.agg_valid[a]) {
+                        FG_TRY(arena_get_t(ctx, node_key(pl, n, "gaccv", a).c_str(), (size_t)groups + 16, &g->agg_valid[a]));
+                        FG_TRY(scatter_by_id_u8(ctx, h.keys, h.n_groups, h.agg_valid[a], g->agg_valid[a]));
+                    }
+                }
+            }
+        }
+        g->n_groups = groups;
+        g->first_row = first;
+        return FLOCKGPU_OK;
+    }
+
     int exec_aggregate(const Node *n, Table *t) {
         const Node *partial = nullptr;
         if (final_is_identity(n, &partial)) {
@@ -2275,8 +2391,21 @@ struct Exec {
             t->cols[0].c.all_null = !any;
             return FLOCKGPU_OK;
         }
+        // ---- key shapes the paths below do not take -- three or more columns, two other than (Int32, Int32) / DISTINCT (Int32, Utf8), NULLs in
+        // a two-column key -- group on composite-key ids (relops.hpp key_codes): groups in order of first appearance
+        bool composite = n->group.size() > 2;
+        if (n->group.size() == 2) {
+            const TCol &a = in.cols[(size_t)n->group[0]], &b = in.cols[(size_t)n->group[1]];
+            composite = a.c.type != ColType::I32 || a.c.valid || b.c.valid || b.c.type != (n->aggs.empty() ? ColType::UTF8 : ColType::I32);
+            if (a.c.type == ColType::F64 || b.c.type == ColType::F64) composite = false;   // (refused below with today's message)
+        }
+        if (composite) {
+            if (n->group.size() > (size_t)kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than %d columns", kMaxKeyCols);
+            for (int c : n->group)
+                if (in.cols[(size_t)c].c.type == ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a Float64 column");
+        }
         // ---- DISTINCT (Int32, Utf8)
-        if (n->group.size() == 2 && n->aggs.empty()) {
+        if (n->group.size() == 2 && n->aggs.empty() && !composite) {
             const TCol &k = in.cols[(size_t)n->group[0]], &s = in.cols[(size_t)n->group[1]];
             if (k.c.type != ColType::I32 || s.c.type != ColType::UTF8 || !k.present || !s.present)
                 return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: two-column GROUP BY other than (Int32, Utf8)");
@@ -2293,14 +2422,14 @@ struct Exec {
         }
         // ---- GROUP BY one integer column or two Int32 columns; COUNT / MAX / MIN / SUM / AVG of integer columns.
         // Partial: accumulators over the rows -> state columns (agg_state_cols); Final: the same accumulators over the states.
-        const bool pair = n->group.size() == 2;
-        if (n->group.empty() || n->group.size() > 2) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than two columns");
+        const bool pair = n->group.size() == 2 && !composite;
+        if (n->group.empty() || (n->group.size() > 2 && !composite)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than two columns");
         const TCol &k = in.cols[(size_t)n->group[0]];
         int64_t *keys = nullptr;
         // NULL group keys form ONE group (DataFusion groups NULLs together): an Int32 key column widened to 64 bits has room for a value
         // no Int32 takes, and so have a Utf8 column's dictionary codes (row numbers); other key types with NULLs are handed back
         constexpr int64_t kNullKey = int64_t(1) << 40;
-        const bool null_keys = k.c.valid != nullptr;
+        const bool null_keys = k.c.valid != nullptr && !composite;
         // ... and a 64-bit key (Int64 / UInt64 / Timestamp) hands its validity to the GROUP BY itself, which keeps the NULLs in a slot of their own
         const bool wide_null_keys = null_keys && !pair && k.c.type != ColType::I32 && k.c.type != ColType::UTF8 && k.c.type != ColType::F64;
         if (null_keys && pair) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: NULLs in a two-column GROUP BY key");
@@ -2378,10 +2507,11 @@ struct Exec {
             outs.push_back(o);
         }
         GroupResultN g;
+        if (composite) FG_TRY(group_composite(n, in, specs, n_specs, &g));
         // A dense integer key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer
         // keys") -- slot = key - min over the column's exact range, no hashing, no int64 copy of the key column.  Everything else (Utf8 /
         // two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
-        bool dense = !pair && !null_keys && k.present && in.rows > 0 && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64);
+        bool dense = !composite && !pair && !null_keys && k.present && in.rows > 0 && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64);
         for (int a = 0; a < n_specs && dense; ++a)
             dense = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
         int64_t kmin = 0, kmax = 0;
@@ -2392,7 +2522,7 @@ struct Exec {
         }
         // A Utf8 key's dictionary codes are row numbers of its own relation: dense by construction.  The code of a group IS a row that
         // carries the group's string, so it also stands in for the first row the key column is taken from.
-        bool dense_codes = !pair && !null_keys && k.present && k.c.type == ColType::UTF8 && in.rows > 0 && in.rows < (int64_t(1) << 31);
+        bool dense_codes = !composite && !pair && !null_keys && k.present && k.c.type == ColType::UTF8 && in.rows > 0 && in.rows < (int64_t(1) << 31);
         for (int a = 0; a < n_specs && dense_codes; ++a)
             dense_codes = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
         if (dense_codes) {
@@ -2407,13 +2537,21 @@ struct Exec {
             g.first_row = rep;
         } else if (dense) {
             FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), k.c, in.rows, kmin, kmax, specs, n_specs, &g));
-        } else {
+        } else if (!composite) {
             FG_TRY(prepare_keys());
             FG_TRY(group_by_key64_n(ctx, node_key(pl, n, "grp").c_str(), keys, in.rows, specs, n_specs, &g, wide_null_keys ? k.c.valid : nullptr));
         }
         t->rows = g.n_groups;
         // ---- key columns
-        if (pair) {
+        if (composite) {   // each group's key values are those of its first row (validity taken along)
+            for (size_t c = 0; c < n->group.size(); ++c) {
+                const TCol &src = in.cols[(size_t)n->group[c]];
+                FG_TRY(take_column(ctx, node_key(pl, n, "take", (int)c).c_str(), src.c, g.first_row, g.n_groups, &t->cols[c].c));
+                t->cols[c].present = true;
+                t->cols[c].c.is_ts = n->schema[c].is_ts;
+                t->cols[c].c.nullable = n->schema[c].nullable;
+            }
+        } else if (pair) {
             int32_t *ka = nullptr, *kb = nullptr;
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk").c_str(), (size_t)g.n_groups + 4, &ka));
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk2").c_str(), (size_t)g.n_groups + 4, &kb));

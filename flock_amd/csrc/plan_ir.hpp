@@ -96,6 +96,8 @@ struct Agg {
 // State columns a Partial stage emits per aggregate, as DataFusion ~6 lays them out (Accumulator::state / state_fields,
 // SURVEY.md appendix D): COUNT -> [count UInt64]; MAX / MIN / SUM -> [value]; AVG -> [count UInt64, sum Float64].
 inline int agg_state_cols(const std::string &fn) { return fn == "avg" ? 2 : 1; }
+// key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
+constexpr int kMaxJoinPairs = 8;
 struct Node {
     NKind kind = NKind::Scan;
     int id = 0;
@@ -109,6 +111,7 @@ struct Node {
     std::vector<Agg> aggs;
     int on_l = -1, on_r = -1;       // Join: key columns (left input, right input)
     int on_l2 = -1, on_r2 = -1;     // Join: second key pair (q9: auction = id AND price = final), -1 when there is one
+    std::vector<int> on_lx, on_rx;  // Join: the key pairs after the second (at most kMaxJoinPairs in all)
     bool join_partitioned = false;  // Join: mode=Partitioned (both inputs arrive hash-partitioned on the keys)
     std::vector<int> hash_cols;     // Repartition
     int n_parts = 0;
@@ -534,8 +537,8 @@ struct Builder {
             auto r = node(j->get("right"), depth + 1);
             if (!r) return nullptr;
             const JValue *on = j->get("on");
-            if (!on || on->kind != JValue::Arr || on->arr.empty() || on->arr.size() > 2) {
-                fail("join on other than one or two key pairs");
+            if (!on || on->kind != JValue::Arr || on->arr.empty() || on->arr.size() > (size_t)kMaxJoinPairs) {
+                fail("join on no key pair or on more than 8 key pairs");
                 return nullptr;
             }
             for (auto &pair : on->arr)
@@ -551,10 +554,15 @@ struct Builder {
             n->on_l = keycol(on->arr[0]->arr[0].get(), l->schema);
             n->on_r = keycol(on->arr[0]->arr[1].get(), r->schema);
             if (n->on_l < 0 || n->on_r < 0) { fail("join key not in the input schemas"); return nullptr; }
-            if (on->arr.size() == 2) {
+            if (on->arr.size() >= 2) {
                 n->on_l2 = keycol(on->arr[1]->arr[0].get(), l->schema);
                 n->on_r2 = keycol(on->arr[1]->arr[1].get(), r->schema);
                 if (n->on_l2 < 0 || n->on_r2 < 0) { fail("join key not in the input schemas"); return nullptr; }
+            }
+            for (size_t k = 2; k < on->arr.size(); ++k) {
+                n->on_lx.push_back(keycol(on->arr[k]->arr[0].get(), l->schema));
+                n->on_rx.push_back(keycol(on->arr[k]->arr[1].get(), r->schema));
+                if (n->on_lx.back() < 0 || n->on_rx.back() < 0) { fail("join key not in the input schemas"); return nullptr; }
             }
             n->schema = l->schema;
             n->schema.insert(n->schema.end(), r->schema.begin(), r->schema.end());
@@ -712,6 +720,8 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
             need(r, n->on_r);
             need(l, n->on_l2);
             need(r, n->on_r2);
+            for (int c : n->on_lx) need(l, c);
+            for (int c : n->on_rx) need(r, c);
             mark_required(p, n->in[0].get(), l);
             mark_required(p, n->in[1].get(), r);
             break;
@@ -805,6 +815,8 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
             l[(size_t)n->on_l] = 1;  // NULL keys never match in an inner join
             r[(size_t)n->on_r] = 1;
             if (n->on_l2 >= 0) { l[(size_t)n->on_l2] = 1; r[(size_t)n->on_r2] = 1; }
+            for (int c : n->on_lx) l[(size_t)c] = 1;
+            for (int c : n->on_rx) r[(size_t)c] = 1;
             mark_null_droppable(p, n->in[0].get(), l);
             mark_null_droppable(p, n->in[1].get(), r);
             break;

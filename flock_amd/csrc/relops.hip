@@ -1311,6 +1311,125 @@ __global__ __launch_bounds__(kBlock) void run_rank_kernel(const int32_t *__restr
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) out[i] = (uint64_t)(i - first[run[i] - 1]) + 1;
 }
 
+// ---- composite keys (key_codes): a tuple of key columns -> one dense id
+struct KeyTuple {
+    int32_t n = 0;
+    int32_t type[kMaxKeyCols] = {};
+    const void *values[kMaxKeyCols] = {};
+    const int32_t *offsets[kMaxKeyCols] = {};
+    const uint8_t *valid[kMaxKeyCols] = {};
+};
+constexpr unsigned long long kKeySlotEmpty = ~0ull;   // (no slot holds it: rows stay below 2^31)
+// 64-bit hash of row i's tuple: integers widened to 64 bits first (an Int32 and an Int64 column hash alike), Utf8 over its bytes, a NULL as a
+// marker of its column number.  *any_null: some key column of the row is NULL.
+__device__ __forceinline__ uint64_t key_tuple_hash(const KeyTuple &k, int64_t i, bool *any_null) {
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    for (int c = 0; c < k.n; ++c) {
+        uint64_t v;
+        if (k.valid[c] && !k.valid[c][i]) {
+            v = 0x6A09E667F3BCC909ull * (uint64_t)(c + 1);
+            *any_null = true;
+        } else if (k.type[c] == (int32_t)ColType::UTF8) {
+            const int32_t *off = k.offsets[c];
+            v = hash_bytes(static_cast<const uint8_t *>(k.values[c]) + off[i], off[i + 1] - off[i]);
+        } else {
+            v = (uint64_t)load_as_i64(k.values[c], k.type[c], i);
+        }
+        h = mix64((h * 0x100000001B3ull) ^ v);
+    }
+    return h;
+}
+// row a of tuple ka equals row b of tuple kb: column by column, NULL equal to NULL only
+__device__ __forceinline__ bool key_tuple_equal(const KeyTuple &ka, int64_t a, const KeyTuple &kb, int64_t b) {
+    for (int c = 0; c < ka.n; ++c) {
+        const bool va = !ka.valid[c] || ka.valid[c][a], vb = !kb.valid[c] || kb.valid[c][b];
+        if (va != vb) return false;
+        if (!va) continue;
+        if (ka.type[c] == (int32_t)ColType::UTF8) {
+            const int32_t *oa = ka.offsets[c], *ob = kb.offsets[c];
+            if (!same_bytes(static_cast<const uint8_t *>(ka.values[c]) + oa[a], oa[a + 1] - oa[a], static_cast<const uint8_t *>(kb.values[c]) + ob[b], ob[b + 1] - ob[b]))
+                return false;
+        } else if (load_as_i64(ka.values[c], ka.type[c], a) != load_as_i64(kb.values[c], kb.type[c], b)) {
+            return false;
+        }
+    }
+    return true;
+}
+// Every row finds its tuple's slot (claiming an empty one, or meeting a slot whose tag and tuple agree) and lowers the slot's row to its own
+// where it is smaller: afterwards a slot's row is the first row of its tuple.  The slot's current row is read before any atomic, so once the
+// early rows of a key have claimed it, its later rows only read.  slot_of[i] = the slot of row i.
+__global__ __launch_bounds__(kBlock) void key_codes_insert_kernel(KeyTuple k, int64_t n, unsigned long long *table, uint64_t cap, int32_t *__restrict__ slot_of) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        bool nul = false;
+        const uint64_t h = key_tuple_hash(k, i, &nul);
+        const unsigned long long tag = h >> 32, mine = (tag << 32) | (uint32_t)i;
+        uint64_t s = h & (cap - 1);
+        for (uint64_t probe = 0; probe < cap; ++probe) {
+            unsigned long long cur = __hip_atomic_load(&table[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == kKeySlotEmpty) {
+                unsigned long long expected = kKeySlotEmpty;
+                if (__hip_atomic_compare_exchange_strong(&table[s], &expected, mine, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                cur = expected;
+            }
+            if ((cur >> 32) == tag && key_tuple_equal(k, i, k, (int64_t)(uint32_t)cur)) {
+                // (equal tuples carry equal tags: the minimum of the 64-bit words is the minimum of their rows)
+                if ((uint32_t)cur > (uint32_t)i) __hip_atomic_fetch_min(&table[s], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+            s = (s + 1) & (cap - 1);
+        }
+        slot_of[i] = (int32_t)s;
+    }
+}
+// first[i] = the first row of row i's tuple (in place over slot_of), rep[i] = row i is that row
+__global__ __launch_bounds__(kBlock) void key_codes_first_kernel(const unsigned long long *__restrict__ table, int64_t n, int32_t *__restrict__ slot_first,
+                                                                 uint8_t *__restrict__ rep) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int32_t f = (int32_t)(uint32_t)table[slot_first[i]];
+        slot_first[i] = f;
+        rep[i] = f == (int32_t)i;
+    }
+}
+// gid[first_rows[g]] = g: each representative row holds its own id
+__global__ __launch_bounds__(kBlock) void key_codes_rank_kernel(const int32_t *__restrict__ first_rows, int64_t n_groups, int32_t *__restrict__ gid) {
+    for (int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (int64_t)gridDim.x * kBlock) gid[first_rows[g]] = (int32_t)g;
+}
+// gid[i] = gid[first[i]] for the other rows (a representative's entry is only read, never written here)
+__global__ __launch_bounds__(kBlock) void key_codes_gid_kernel(const int32_t *__restrict__ first, int64_t n, int32_t *gid) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int32_t f = first[i];
+        if (f != (int32_t)i) gid[i] = gid[f];
+    }
+}
+__global__ __launch_bounds__(kBlock) void key_codes_probe_kernel(KeyTuple b, const unsigned long long *__restrict__ table, uint64_t cap, const int32_t *__restrict__ bgid,
+                                                                 KeyTuple p, int64_t n, int32_t *__restrict__ out) {
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (int64_t)gridDim.x * kBlock) {
+        bool nul = false;
+        const uint64_t h = key_tuple_hash(p, j, &nul);
+        int32_t id = -1;
+        if (!nul) {   // (a NULL key column matches nothing)
+            const unsigned long long tag = h >> 32;
+            uint64_t s = h & (cap - 1);
+            for (uint64_t probe = 0; probe < cap; ++probe) {
+                const unsigned long long cur = table[s];
+                if (cur == kKeySlotEmpty) break;
+                if ((cur >> 32) == tag && key_tuple_equal(p, j, b, (int64_t)(uint32_t)cur)) {
+                    id = bgid[(uint32_t)cur];
+                    break;
+                }
+                s = (s + 1) & (cap - 1);
+            }
+        }
+        out[j] = id;
+    }
+}
+__global__ __launch_bounds__(kBlock) void scatter_by_id_u64_kernel(const int64_t *__restrict__ ids, int64_t n, const uint64_t *__restrict__ src, uint64_t *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) dst[ids[i]] = src[i];
+}
+__global__ __launch_bounds__(kBlock) void scatter_by_id_u8_kernel(const int64_t *__restrict__ ids, int64_t n, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) dst[ids[i]] = src[i];
+}
+
 }  // namespace
 
 namespace flockgpu {
@@ -1893,6 +2012,68 @@ int utf8_codes(flockgpu_ctx *ctx, const char *name, const DevColumn &build, int6
     if (probe && probe_codes && n_probe > 0)
         RELOPS_LAUNCH(ctx, "utf8_codes_probe_kernel", utf8_codes_probe_kernel, n_probe, build.offsets, static_cast<const uint8_t *>(build.values), table,
                       cap, probe->offsets, static_cast<const uint8_t *>(probe->values), n_probe, probe_codes);
+    return FLOCKGPU_OK;
+}
+
+int key_codes(flockgpu_ctx *ctx, const char *name, const DevColumn *build_cols, int n_cols, int64_t rows, int32_t *gid, int64_t *n_groups,
+              int32_t **first_rows, const DevColumn *probe_cols, int64_t probe_rows, int32_t *probe_gid) {
+    const std::string base = name;
+    *n_groups = 0;
+    if (n_cols < 1 || n_cols > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: %d key columns (1 to %d are supported)", name, n_cols, kMaxKeyCols);
+    // (the table has pow2_at_least(2 * rows) slots and a row's slot travels as an int32: below 2^30 build rows every slot number is below 2^31,
+    // the limit of every other operator on such a table -- group_by_key64_n, utf8_codes, the join build)
+    if (rows >= (int64_t(1) << 30)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^30 rows in a composite key", name);
+    if (probe_rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 probe rows", name);
+    auto tuple = [&](const DevColumn *cols, KeyTuple *k) -> int {
+        k->n = n_cols;
+        for (int c = 0; c < n_cols; ++c) {
+            const DevColumn &d = cols[c];
+            if (d.type == ColType::F64 || d.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: key column %d is Float64 or has no values", name, c);
+            k->type[c] = (int32_t)d.type;
+            k->values[c] = d.values;
+            k->offsets[c] = d.offsets;
+            k->valid[c] = d.valid;
+        }
+        return FLOCKGPU_OK;
+    };
+    KeyTuple kb, kp;
+    FG_TRY(tuple(build_cols, &kb));
+    if (probe_cols) {
+        FG_TRY(tuple(probe_cols, &kp));
+        for (int c = 0; c < n_cols; ++c)
+            if ((kb.type[c] == (int32_t)ColType::UTF8) != (kp.type[c] == (int32_t)ColType::UTF8) ||
+                (kb.type[c] == (int32_t)ColType::U64) != (kp.type[c] == (int32_t)ColType::U64))
+                return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: key pair %d of incomparable types", name, c);
+    }
+    const uint64_t cap = pow2_at_least((uint64_t)std::max<int64_t>(rows, 1) * 2);
+    unsigned long long *table = nullptr;
+    uint8_t *rep = nullptr;
+    int32_t *first = nullptr;
+    FG_TRY(arena_get_t(ctx, (base + ".table").c_str(), (size_t)cap, &table));
+    FG_TRY(arena_get_t(ctx, (base + ".first").c_str(), (size_t)std::max<int64_t>(rows, 0) + 4, &first));
+    FG_TRY(arena_get_t(ctx, (base + ".rep").c_str(), (size_t)std::max<int64_t>(rows, 0) + 16, &rep));
+    RELOPS_LAUNCH(ctx, "fill_u64_kernel", fill_u64_kernel, (int64_t)cap, reinterpret_cast<uint64_t *>(table), (int64_t)cap, (uint64_t)kKeySlotEmpty);
+    if (rows > 0) {
+        RELOPS_LAUNCH(ctx, "key_codes_insert_kernel", key_codes_insert_kernel, rows, kb, rows, table, cap, first);
+        RELOPS_LAUNCH(ctx, "key_codes_first_kernel", key_codes_first_kernel, rows, table, rows, first, rep);
+    }
+    // the representatives in row order: the groups in order of first appearance (the one wait)
+    FG_TRY(mask_to_rows(ctx, (base + ".reps").c_str(), rep, rows, first_rows, n_groups));
+    if (rows > 0) {
+        RELOPS_LAUNCH(ctx, "key_codes_rank_kernel", key_codes_rank_kernel, *n_groups, *first_rows, *n_groups, gid);
+        RELOPS_LAUNCH(ctx, "key_codes_gid_kernel", key_codes_gid_kernel, rows, first, rows, gid);
+    }
+    if (probe_cols && probe_gid && probe_rows > 0)
+        RELOPS_LAUNCH(ctx, "key_codes_probe_kernel", key_codes_probe_kernel, probe_rows, kb, table, cap, gid, kp, probe_rows, probe_gid);
+    return FLOCKGPU_OK;
+}
+
+int scatter_by_id_u64(flockgpu_ctx *ctx, const int64_t *ids, int64_t n, const uint64_t *src, uint64_t *dst) {
+    if (n > 0) RELOPS_LAUNCH(ctx, "scatter_by_id_u64_kernel", scatter_by_id_u64_kernel, n, ids, n, src, dst);
+    return FLOCKGPU_OK;
+}
+int scatter_by_id_u8(flockgpu_ctx *ctx, const int64_t *ids, int64_t n, const uint8_t *src, uint8_t *dst) {
+    if (n > 0) RELOPS_LAUNCH(ctx, "scatter_by_id_u8_kernel", scatter_by_id_u8_kernel, n, ids, n, src, dst);
     return FLOCKGPU_OK;
 }
 

@@ -109,6 +109,19 @@ int hash_utf8_i64(flockgpu_ctx *ctx, const DevColumn &col, int64_t rows, int64_t
 // `build` does not contain it (negative codes are pairwise different and match nothing).  Either output may be null.
 int utf8_codes(flockgpu_ctx *ctx, const char *name, const DevColumn &build, int64_t n_build, int64_t *build_codes, const DevColumn *probe,
                int64_t n_probe, int64_t *probe_codes);
+// ---- composite keys: a tuple of 1..kMaxKeyCols columns (Int32 / Int64 / Timestamp / UInt64 / Utf8; NULLs allowed) -> one dense id per row.
+// Integers compare by value after widening to 64 bits (an Int32 column meets an Int64 one; UInt64 meets only UInt64 -- the caller's check),
+// Utf8 bytewise, NULL equals NULL within a column.  gid[i] in [0, *n_groups), numbered in order of first appearance; *first_rows (ctx-owned,
+// ascending) = the first row of every group.  A probe side (may be absent): probe_gid[j] = the id of the equal build tuple, or -1 when the
+// build side does not hold it or any of the probe's key columns is NULL there.  Global open-addressing table of 8-byte slots (32-bit hash
+// tag, 32-bit first row: an atomic minimum keeps the first row), full tuple compare only where the tags agree.  One host wait.  Build side below
+// 2^30 rows (the table's slot numbers travel as int32), probe side below 2^31.
+constexpr int kMaxKeyCols = 8;
+int key_codes(flockgpu_ctx *ctx, const char *name, const DevColumn *build_cols, int n_cols, int64_t rows, int32_t *gid, int64_t *n_groups,
+              int32_t **first_rows, const DevColumn *probe_cols, int64_t probe_rows, int32_t *probe_gid);
+// dst[ids[i]] = src[i] for i in [0, n): the groups of a hashed GROUP BY over dense ids put back in id order (8-byte or 1-byte elements)
+int scatter_by_id_u64(flockgpu_ctx *ctx, const int64_t *ids, int64_t n, const uint64_t *src, uint64_t *dst);
+int scatter_by_id_u8(flockgpu_ctx *ctx, const int64_t *ids, int64_t n, const uint8_t *src, uint8_t *dst);
 // (a, b) Int32 pairs <-> one 64-bit key: key = (int64(a) << 32) | uint32(b)
 int pack_i32_pair(flockgpu_ctx *ctx, const int32_t *a, const int32_t *b, int64_t n, int64_t *out);
 int unpack_i32_pair(flockgpu_ctx *ctx, const int64_t *keys, int64_t n, int32_t *a, int32_t *b);
