@@ -698,10 +698,21 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
     if (n->kind == NKind::Window)
-        for (size_t w = 0; w < n->win_part.size(); ++w) {
-            os << (w ? ", " : "(") << "ROW_NUMBER PARTITION BY";
-            for (int c : n->win_part[w]) os << " " << n->in[0]->schema[(size_t)c].name;
-            if (w + 1 == n->win_part.size()) os << ")";
+        for (size_t w = 0; w < n->win.size(); ++w) {
+            const WinExpr &x = n->win[w];
+            const auto &ins = n->in[0]->schema;
+            std::string fn = x.fn;
+            for (auto &ch : fn) ch = (char)std::toupper((unsigned char)ch);
+            os << (w ? ", " : "(");
+            if (x.row_number) os << "ROW_NUMBER";
+            else os << fn << "(" << (x.arg >= 0 ? ins[(size_t)x.arg].name : std::string("*")) << ")";
+            os << " PARTITION BY";
+            for (int c : x.part) os << " " << ins[(size_t)c].name;
+            if (!x.order.empty()) {
+                os << " ORDER BY";
+                for (auto &o : x.order) os << " " << ins[(size_t)o.col].name << (o.descending ? " DESC" : "");
+            }
+            if (w + 1 == n->win.size()) os << ")";
         }
     if (n->kind == NKind::Sort) {
         os << "(";
@@ -769,8 +780,11 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
     for (auto &k : n->sort_cols) *o += std::to_string(k.col) + (k.descending ? "d" : "a") + (k.nulls_first ? "f" : "l") + ",";
     *o += std::to_string(n->limit) + "|";
-    for (auto &part : n->win_part) {   // (Window: the PARTITION BY columns of each ROW_NUMBER())
-        for (int c : part) *o += std::to_string(c) + ",";
+    for (auto &x : n->win) {   // (Window: each column's function, argument, PARTITION BY and ORDER BY)
+        *o += (x.row_number ? std::string("rn") : x.fn + "." + std::to_string(x.arg) + "." + std::to_string((int)x.type)) + ":";
+        for (int c : x.part) *o += std::to_string(c) + ",";
+        *o += "/";
+        for (auto &k : x.order) *o += std::to_string(k.col) + ",";
         *o += ";";
     }
     *o += "|";
@@ -2046,33 +2060,98 @@ struct Exec {
             }
             case NKind::Sort:
                 return exec_sort(n, -1, t);
-            case NKind::Window: {   // ROW_NUMBER() columns first, then the input's (q6_plan.fmt: the WindowAggr schemas)
+            case NKind::Window: {   // the window columns first, then the input's (q6_plan.fmt: the WindowAggr schemas)
                 Table in;
                 FG_TRY(exec(n->in[0].get(), &in));
-                const size_t nw = n->win_part.size();
+                const size_t nw = n->win.size();
                 t->rows = in.rows;
                 t->cols.assign(n->schema.size(), TCol{});
+                auto key_of = [&](int col, DevColumn *out) -> int {
+                    const TCol &k = in.cols[(size_t)col];
+                    if (!k.present && !k.c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window key column was not materialised");
+                    *out = k.c;
+                    if (k.c.all_null) { out->type = ColType::I32; out->values = nullptr; }   // every row NULL: one run as far as this key goes
+                    return FLOCKGPU_OK;
+                };
                 for (size_t w = 0; w < nw; ++w) {
+                    if (!n->win[w].row_number) continue;
                     t->cols[w].c.type = ColType::U64;
                     t->cols[w].c.nullable = true;
                     if (!n->required[w]) continue;
                     DevColumn keys[4];
-                    if (n->win_part[w].size() > 4) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: PARTITION BY more than four columns");
-                    for (size_t c = 0; c < n->win_part[w].size(); ++c) {
-                        const TCol &k = in.cols[(size_t)n->win_part[w][c]];
-                        if (!k.present && !k.c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: PARTITION BY column was not materialised");
-                        keys[c] = k.c;
-                        if (k.c.all_null) { keys[c].type = ColType::I32; keys[c].values = nullptr; }   // every row NULL: one run as far as this key goes
-                    }
+                    if (n->win[w].part.size() > 4) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: PARTITION BY more than four columns");
+                    for (size_t c = 0; c < n->win[w].part.size(); ++c) FG_TRY(key_of(n->win[w].part[c], &keys[c]));
                     int nk = 0;
                     DevColumn live[4];
-                    for (size_t c = 0; c < n->win_part[w].size(); ++c)
+                    for (size_t c = 0; c < n->win[w].part.size(); ++c)
                         if (keys[c].values) live[nk++] = keys[c];
                     uint64_t *rank = nullptr;
                     FG_TRY(arena_get_t(ctx, node_key(pl, n, "rank", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 2, &rank));
                     FG_TRY(row_number_runs(ctx, node_key(pl, n, "rn", (int)w).c_str(), live, nk, in.rows, rank));
                     t->cols[w] = dev_col(ColType::U64, rank);
                     t->cols[w].c.nullable = true;
+                }
+                // aggregate columns: one window_aggregates call per distinct (PARTITION BY, ORDER BY) -- its keys are compared once
+                std::vector<char> done(nw, 0);
+                for (size_t w0 = 0; w0 < nw; ++w0) {
+                    if (n->win[w0].row_number || done[w0]) continue;
+                    const WinExpr &x0 = n->win[w0];
+                    auto same_keys = [&](const WinExpr &y) {
+                        if (y.row_number || y.part != x0.part || y.order.size() != x0.order.size()) return false;
+                        for (size_t k = 0; k < y.order.size(); ++k)
+                            if (y.order[k].col != x0.order[k].col) return false;
+                        return true;
+                    };
+                    DevColumn live[2 * kMaxWindowKeys];   // (an all-NULL key splits nothing: left out)
+                    int np = 0, no = 0;
+                    for (int c : x0.part) {
+                        DevColumn k;
+                        FG_TRY(key_of(c, &k));
+                        if (k.values) live[np++] = k;
+                    }
+                    for (auto &o : x0.order) {
+                        DevColumn k;
+                        FG_TRY(key_of(o.col, &k));
+                        if (k.values) live[np + no++] = k;
+                    }
+                    std::vector<WinAgg> aggs;
+                    for (size_t w = w0; w < nw; ++w) {
+                        const WinExpr &x = n->win[w];
+                        if (!same_keys(x)) continue;
+                        done[w] = 1;
+                        const size_t width = x.type == ColType::I32 ? 4 : 8;
+                        TCol &oc = t->cols[w];
+                        oc.c.type = x.type;
+                        oc.c.is_ts = x.is_ts;
+                        oc.c.nullable = true;
+                        if (!n->required[w]) continue;
+                        WinAgg g;
+                        if (x.arg >= 0) {
+                            const TCol &a = in.cols[(size_t)x.arg];
+                            if (!a.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window argument column was not materialised");
+                            if (x.fn != "count" && (a.c.type == ColType::UTF8 || (a.c.type == ColType::F64 && x.fn != "min" && x.fn != "max")))
+                                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", x.fn.c_str());
+                            g.values = a.c.values;
+                            g.type = a.c.type;
+                            g.valid = a.c.valid;
+                        }
+                        const bool uns = g.type == ColType::U64, f64 = g.type == ColType::F64;
+                        if (x.fn == "count") g.op = AggOp::COUNT;
+                        else if (x.fn == "sum") g.op = AggOp::SUM_INT;
+                        else if (x.fn == "avg") g.avg = true;
+                        else if (x.fn == "max") g.op = f64 ? AggOp::MAX_F64 : uns ? AggOp::MAX_U : AggOp::MAX_S;
+                        else g.op = f64 ? AggOp::MIN_F64 : uns ? AggOp::MIN_U : AggOp::MIN_S;
+                        g.out_type = x.type;
+                        void *out = nullptr;
+                        FG_TRY(arena_get(ctx, node_key(pl, n, "wv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) * width + 64, &out));
+                        g.out = out;
+                        if (x.fn != "count") FG_TRY(arena_get_t(ctx, node_key(pl, n, "wvv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 64, &g.out_valid));
+                        aggs.push_back(g);
+                        oc = dev_col(x.type, out, nullptr, 0, x.is_ts);
+                        oc.c.nullable = true;
+                        oc.c.valid = g.out_valid;
+                    }
+                    FG_TRY(window_aggregates(ctx, node_key(pl, n, "wa", (int)w0).c_str(), live, np, no, in.rows, aggs.data(), (int)aggs.size()));
                 }
                 for (size_t i = 0; i < in.cols.size(); ++i) t->cols[nw + i] = in.cols[i];
                 return FLOCKGPU_OK;

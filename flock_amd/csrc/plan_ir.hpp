@@ -6,8 +6,9 @@
 // repartition_exec with Hash partitioning, sort_exec (ORDER BY over columns: the reference's own boundary goldens end in it,
 // flock/src/runtime/context.rs:471,549; the splitter cuts stages at it, distributed_plan/stage.rs:337) and global_limit_exec /
 // local_limit_exec.  coalesce_batches_exec, repartition_exec RoundRobinBatch, merge_exec / coalesce_partitions_exec change
-// neither the row multiset nor the schema and are dropped.  Anything else (window functions, outer
-// joins, unknown expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
+// neither the row multiset nor the schema and are dropped.  window_agg_exec (Window) takes ROW_NUMBER() and
+// COUNT / SUM / MIN / MAX / AVG over the default frame.  Anything else (other window functions and frames, outer joins, unknown
+// expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -98,6 +99,18 @@ struct Agg {
 inline int agg_state_cols(const std::string &fn) { return fn == "avg" ? 2 : 1; }
 // key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
 constexpr int kMaxJoinPairs = 8;
+// One column of a WindowAggExec: ROW_NUMBER(), or an aggregate over the default frame (RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: the
+// partition's rows up to the last PEER of the current row -- equal ORDER BY values; the whole partition without ORDER BY).
+struct WinExpr {
+    bool row_number = true;
+    std::string fn;                // aggregate: "count" | "sum" | "min" | "max" | "avg"
+    int arg = -1;                  // aggregate: input column of the argument (-1: COUNT(*))
+    ColType type = ColType::U64;   // the window column's type (the aggregate's data_type; COUNT UInt64, AVG Float64)
+    bool is_ts = false;            // MIN / MAX of a Timestamp
+    std::vector<int> part;         // input columns of the PARTITION BY
+    std::vector<SortCol> order;    // aggregate: input columns of the ORDER BY (they delimit the peer groups; the input arrives sorted)
+};
+constexpr int kMaxWindowKeys = 4;   // PARTITION BY / ORDER BY columns of an aggregate window (each)
 struct Node {
     NKind kind = NKind::Scan;
     int id = 0;
@@ -118,7 +131,7 @@ struct Node {
     bool hash_diff = false;         // Repartition: HashDiff -- one partition per DISTINCT key (n_parts = what the host counted)
     std::vector<SortCol> sort_cols; // Sort: ORDER BY keys, most significant first
     int64_t limit = -1;             // Limit: rows kept
-    std::vector<std::vector<int>> win_part;   // Window: per ROW_NUMBER() column (they come FIRST in the schema), the input columns of its PARTITION BY
+    std::vector<WinExpr> win;       // Window: one per window column (they come FIRST in the schema)
     std::vector<char> required;     // per output column: needed by an ancestor (or by the plan output)
 };
 
@@ -609,41 +622,130 @@ struct Builder {
             // WindowAggExec (q6.sql: ROW_NUMBER() OVER (PARTITION BY a_id ORDER BY price DESC), benchmarks/src/nexmark/query/q6_plan.fmt:6,11).
             // The physical planner sorts the input by (PARTITION BY, ORDER BY) underneath (a sort_exec); the operator numbers the rows of every
             // RUN of equal partition keys 1, 2, ... in the order they arrive -- what DataFusion's partition points over a sorted batch give.
-            // Output: the window columns first (UInt64), then the input's (q6_plan.fmt's schemas).  Only ROW_NUMBER is taken.
+            // Output: the window columns first, then the input's (q6_plan.fmt's schemas).  ROW_NUMBER() and the aggregates COUNT / SUM / MIN / MAX /
+            // AVG ("window_expr": "aggregate_window_expr", DataFusion's AggregateWindowExpr) over the default frame are taken.
             n->kind = NKind::Window;
             auto in = node(j->get("input"), depth + 1);
             if (!in) return nullptr;
             const JValue *we = j->get("window_expr");
             if (!we || we->kind != JValue::Arr || we->arr.empty()) { fail("window_agg_exec without window_expr"); return nullptr; }
             std::vector<Field> wf;
+            auto key_col = [&](const JValue *e, const char *what) -> int {
+                if (etag(e) != "column") { fail(std::string(what) + " on something other than a column"); return -1; }
+                const int c = resolve(e, in->schema);
+                if (c < 0) { fail(std::string(what) + " column not in the input schema"); return -1; }
+                return c;
+            };
             for (auto &w : we->arr) {
                 if (w->kind != JValue::Obj) { fail("malformed window_expr"); return nullptr; }
-                std::string fun;
-                for (const char *key : {"fun", "function", "window_function", "built_in", "expr", "name"}) {
-                    const JValue *f = w->get(key);
-                    if (!f) continue;
-                    std::string v = f->kind == JValue::Str ? f->str : (f->kind == JValue::Obj && !f->obj.empty() ? f->obj[0].first : std::string());
-                    for (auto &ch : v) ch = (char)std::tolower((unsigned char)ch);
-                    v.erase(std::remove(v.begin(), v.end(), '_'), v.end());
-                    if (v.find("rownumber") != std::string::npos) { fun = "row_number"; break; }
-                    if (fun.empty() && !v.empty()) fun = v;
+                WinExpr x;
+                Field f;
+                f.nullable = true;
+                const JValue *ag = w->get("aggregate");
+                if (w->s("window_expr") == "aggregate_window_expr" || (ag && ag->kind == JValue::Obj)) {
+                    if (!ag || ag->kind != JValue::Obj) { fail("aggregate_window_expr without its aggregate"); return nullptr; }
+                    x.row_number = false;
+                    x.fn = ag->s("aggregate_expr");
+                    for (auto &ch : x.fn) ch = (char)std::tolower((unsigned char)ch);
+                    if (x.fn != "count" && x.fn != "max" && x.fn != "min" && x.fn != "sum" && x.fn != "avg") {
+                        fail("window function '" + x.fn + "' (supported: ROW_NUMBER, COUNT, SUM, MIN, MAX, AVG)");
+                        return nullptr;
+                    }
+                    f.name = ag->s("name");
+                    if (!parse_type(ag->get("data_type"), &x.type, &x.is_ts)) { fail("window aggregate '" + f.name + "' of an unsupported type"); return nullptr; }
+                    const JValue *arg = ag->get("expr");
+                    if (arg && etag(arg) == "column") {
+                        x.arg = resolve(arg, in->schema);
+                        if (x.arg < 0) { fail("window aggregate argument not in the input schema"); return nullptr; }
+                    } else if (arg && etag(arg) != "literal") {
+                        fail("window aggregate '" + x.fn + "' over a computed expression");
+                        return nullptr;
+                    } else if (x.fn != "count") {
+                        fail("window aggregate '" + x.fn + "' over a literal");
+                        return nullptr;
+                    }
+                    // the argument types of the GROUP BY path (plan.hip exec_aggregate), refused in its words
+                    const ColType at = x.arg >= 0 ? in->schema[(size_t)x.arg].type : ColType::U64;
+                    if (x.fn != "count" && (at == ColType::UTF8 || (at == ColType::F64 && x.fn != "min" && x.fn != "max"))) {
+                        fail(x.fn + " needs an integer column");
+                        return nullptr;
+                    }
+                    if (x.fn == "count") x.type = ColType::U64;
+                    if (x.fn == "avg") x.type = ColType::F64;
+                    x.is_ts = x.is_ts && (x.fn == "min" || x.fn == "max");
+                    if ((x.fn == "min" || x.fn == "max") && (x.type == ColType::F64) != (at == ColType::F64)) {
+                        fail(x.fn + " of a column into a column of another kind");
+                        return nullptr;
+                    }
+                    if (x.type == ColType::UTF8) { fail("window aggregate '" + f.name + "' of an unsupported type"); return nullptr; }
+                    const JValue *ob = w->get("order_by");
+                    if (ob && ob->kind == JValue::Arr)
+                        for (auto &e : ob->arr) {
+                            SortCol sc;
+                            const JValue *ex = e->kind == JValue::Obj && e->get("expr") ? e->get("expr") : e.get();
+                            sc.col = key_col(ex, "ORDER BY");
+                            if (sc.col < 0) return nullptr;
+                            const JValue *op = e->get("options");
+                            if (op && op->get("descending") && op->get("descending")->kind == JValue::Bool) sc.descending = op->get("descending")->b;
+                            if (op && op->get("nulls_first") && op->get("nulls_first")->kind == JValue::Bool) sc.nulls_first = op->get("nulls_first")->b;
+                            x.order.push_back(sc);
+                        }
+                    // the frame: absent, null, or exactly the default (RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW)
+                    const JValue *fr = w->get("window_frame");
+                    if (fr && fr->kind != JValue::Null) {
+                        auto bound = [](const JValue *b) -> std::string {   // "Preceding(None)" | "CurrentRow" | "Following(3)" ...
+                            if (!b) return "?";
+                            if (b->kind == JValue::Str) return b->str;
+                            if (b->kind == JValue::Obj && b->obj.size() == 1) {
+                                const JValue *v = b->obj[0].second.get();
+                                return b->obj[0].first + "(" + (v->kind == JValue::Null ? std::string("None") : v->kind == JValue::Num ? std::to_string(v->inum) : std::string("?")) + ")";
+                            }
+                            return "?";
+                        };
+                        const std::string units = fr->kind == JValue::Obj ? fr->s("units") : std::string("?"),
+                                          lo = fr->kind == JValue::Obj ? bound(fr->get("start_bound")) : "?", hi = fr->kind == JValue::Obj ? bound(fr->get("end_bound")) : "?";
+                        const bool dflt = (units == "Range" || units == "RANGE") && (lo == "Preceding(None)" || lo == "UnboundedPreceding") &&
+                                          (hi == "CurrentRow" || hi == "CurrentRow(None)");
+                        if (!dflt) {
+                            fail("window frame " + units + " BETWEEN " + lo + " AND " + hi + " (supported: the default RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW)");
+                            return nullptr;
+                        }
+                    }
+                    f.type = x.type;
+                    f.is_ts = x.is_ts;
+                    if (f.name.empty()) f.name = w->s("name");
+                } else {
+                    std::string fun;
+                    for (const char *key : {"fun", "function", "window_function", "built_in", "expr", "name"}) {
+                        const JValue *fv = w->get(key);
+                        if (!fv) continue;
+                        std::string v = fv->kind == JValue::Str ? fv->str : (fv->kind == JValue::Obj && !fv->obj.empty() ? fv->obj[0].first : std::string());
+                        for (auto &ch : v) ch = (char)std::tolower((unsigned char)ch);
+                        v.erase(std::remove(v.begin(), v.end(), '_'), v.end());
+                        if (v.find("rownumber") != std::string::npos) { fun = "row_number"; break; }
+                        if (fun.empty() && !v.empty()) fun = v;
+                    }
+                    if (fun != "row_number") { fail("window function '" + fun + "' (supported: ROW_NUMBER, COUNT, SUM, MIN, MAX, AVG)"); return nullptr; }
+                    const JValue *nm = w->get("name");
+                    f.name = nm && nm->kind == JValue::Str ? nm->str : "ROW_NUMBER()";
+                    f.type = ColType::U64;
                 }
-                if (fun != "row_number") { fail("window function '" + fun + "' (supported: ROW_NUMBER)"); return nullptr; }
-                std::vector<int> part;
                 const JValue *pb = w->get("partition_by");
                 if (pb && pb->kind == JValue::Arr)
                     for (auto &e : pb->arr) {
-                        if (etag(e.get()) != "column") { fail("PARTITION BY on something other than a column"); return nullptr; }
-                        const int c = resolve(e.get(), in->schema);
-                        if (c < 0) { fail("PARTITION BY column not in the input schema"); return nullptr; }
-                        part.push_back(c);
+                        const int c = key_col(e.get(), "PARTITION BY");
+                        if (c < 0) return nullptr;
+                        x.part.push_back(c);
                     }
-                n->win_part.push_back(part);
-                Field f;
-                const JValue *nm = w->get("name");
-                f.name = nm && nm->kind == JValue::Str ? nm->str : "ROW_NUMBER()";
-                f.type = ColType::U64;
-                f.nullable = true;
+                if (!x.row_number) {   // (ROW_NUMBER keeps its execute-time checks)
+                    if (x.part.size() > (size_t)kMaxWindowKeys) { fail("PARTITION BY more than four columns"); return nullptr; }
+                    if (x.order.size() > (size_t)kMaxWindowKeys) { fail("window ORDER BY more than four columns"); return nullptr; }
+                    for (int c : x.part)
+                        if (in->schema[(size_t)c].type == ColType::UTF8) { fail("PARTITION BY a Utf8 column"); return nullptr; }
+                    for (auto &o : x.order)
+                        if (in->schema[(size_t)o.col].type == ColType::UTF8) { fail("window ORDER BY a Utf8 column"); return nullptr; }
+                }
+                n->win.push_back(x);
                 wf.push_back(f);
             }
             n->schema = wf;
@@ -742,10 +844,13 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
             mark_required(p, n->in[0].get(), req);
             break;
         case NKind::Window: {
-            const size_t nw = n->win_part.size();
+            const size_t nw = n->win.size();
             std::vector<char> r(req.begin() + (long)nw, req.end());
-            for (auto &part : n->win_part)
-                for (int c : part) need(r, c);
+            for (auto &x : n->win) {
+                for (int c : x.part) need(r, c);
+                for (auto &o : x.order) need(r, o.col);
+                need(r, x.arg);
+            }
             mark_required(p, n->in[0].get(), r);
             break;
         }

@@ -101,6 +101,25 @@ bool dense_range_ok(int64_t kmin, int64_t kmax, int64_t rows, bool uns);
 // are not produced (nothing on this path needs them).  A key outside [kmin, kmax] voids the call (FLOCKGPU_ERR_INVALID).
 int group_by_dense(flockgpu_ctx *ctx, const char *name, const DevColumn &key, int64_t rows, int64_t kmin, int64_t kmax, const AggSpec *specs, int n_specs,
                    GroupResultN *out);
+// ---- aggregate window functions of WindowAggExec (window.hip) over the default frame, RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW, on rows sorted
+// by (PARTITION BY, ORDER BY): row i gets the aggregate of its partition's rows from the first through the last PEER of row i (equal ORDER BY values;
+// without ORDER BY, the whole partition).  Keys compare as in row_number_runs (NULL equals NULL; Utf8 refused): keys[0, n_part) the PARTITION BY,
+// keys[n_part, n_part + n_order) the ORDER BY, at most four each.  Accumulators are 64-bit as GROUP BY's (kMaxGroupAggs per pass of three launches;
+// the keys are compared in the first pass only): COUNT counts valid arguments (`valid` null: every row), SUM_INT wraps, MIN / MAX signed, unsigned or
+// Float64; AVG = double(int64 SUM) / double(COUNT).  NULL arguments are skipped; out_valid[i] = 0 while no valid value is in row i's frame (AVG: no
+// value; COUNT writes none).  `out_type` I32 narrows the result.  Below 2^31 rows; launches only.
+struct WinAgg {
+    AggOp op = AggOp::COUNT;        // COUNT | SUM_INT | MAX_S | MAX_U | MIN_S | MIN_U | MAX_F64 | MIN_F64 (ignored for AVG)
+    bool avg = false;
+    const void *values = nullptr;   // the argument (null: COUNT(*))
+    ColType type = ColType::I64;    // its storage type
+    const uint8_t *valid = nullptr;
+    void *out = nullptr;            // rows values of out_type (Int32: 4 bytes, else 8)
+    ColType out_type = ColType::I64;
+    uint8_t *out_valid = nullptr;   // may be null
+};
+int window_aggregates(flockgpu_ctx *ctx, const char *name, const DevColumn *keys, int n_part, int n_order, int64_t rows, const WinAgg *aggs, int n_aggs);
+
 // ---- Utf8 keys (YSB joins and groups on UUID strings, flock/src/distributed_plan/planner.rs:298-346)
 // out[i] = 64-bit hash of row i's bytes: equal strings -> equal keys (enough for a hash repartition; NOT an equality test)
 int hash_utf8_i64(flockgpu_ctx *ctx, const DevColumn &col, int64_t rows, int64_t *out);
