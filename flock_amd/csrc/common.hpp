@@ -98,9 +98,10 @@ inline int fail(flockgpu_ctx *ctx, int code, const char *fmt, ...) {
         if (rc_ != FLOCKGPU_OK) return rc_; \
     } while (0)
 
-// Experiment knobs (A/B switches the tools/gpu_*.sh scripts flip through the environment) exist only in builds made with
-// -DFLOCKGPU_EXPERIMENTAL (`FLOCKGPU_BUILD_EXPERIMENTAL=1 python -m flock_amd.build`, which writes libflockgpu_experimental.so): the
-// shipped library never reads them, so no untested configuration is reachable from a production host's environment.
+// Diagnostic switches (the guarded arena below, FLOCKGPU_PLAN_TIMES, LaunchScope's reference event placement) are read from the
+// environment only in builds made with -DFLOCKGPU_EXPERIMENTAL (`FLOCKGPU_BUILD_EXPERIMENTAL=1 python -m flock_amd.build`, which writes
+// libflockgpu_experimental.so): the shipped library never reads them, so no untested configuration is reachable from a production host's
+// environment.
 #ifdef FLOCKGPU_EXPERIMENTAL
 inline const char *exp_env(const char *name) { return getenv(name); }
 #else
@@ -138,7 +139,6 @@ inline int arena_get(flockgpu_ctx *ctx, const char *name, size_t bytes, void **o
         }
         size_t want = bytes + bytes / 8;  // slack so that slowly growing windows do not reallocate every call
         want = (want + 255) & ~size_t(255);
-        if (exp_env("FLOCKGPU_ARENA_EXACT")) want = bytes;   // (ordinary memory, no slack: every growth reallocates -- address recycling without the guard)
         if (guard_arena()) {   // exactly what was asked for, its end at the end of the mapping
             // (FLOCKGPU_GUARD_SLACK = a substring: buffers whose name contains it keep the usual slack -- how the buffer behind a failing
             // guarded run is found; FLOCKGPU_GUARD_TRACE: every (re)allocation on stderr)
@@ -214,7 +214,7 @@ struct LaunchScope {
         if (ctx->profiling && !on && ctx->profile_only.find('|') != std::string::npos)   // "a|b": the kernels a call may choose between for one step
             on = ("|" + ctx->profile_only + "|").find("|" + std::string(n) + "|") != std::string::npos;
         outer = g_launch_scope;
-        recorded = exp_env("FLOCKGPU_AB_RECORDED_EVENTS") != nullptr;   // (A/B builds only: the events recorded either side of the launch, as in rounds 1-5)
+        recorded = exp_env("FLOCKGPU_RECORDED_EVENTS") != nullptr;   // (the reference path for a test of the bound events: one event recorded either side of the scope)
         g_launch_scope = on && !recorded ? this : nullptr;   // (an inner scope that is not sampled must not lend its launches to an outer one)
         if (!on) return;
         auto take = [&]() {
@@ -301,15 +301,12 @@ inline void pinned_pending(uint64_t *words, int n) {
 }
 template <typename W>
 inline int wait_pinned_words(flockgpu_ctx *ctx, const W *words, int n, W pending) {
-    static const bool no_poll = exp_env("FLOCKGPU_NO_POLL") != nullptr;   // (A/B knob of the experimental build)
-    if (!no_poll) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 0;; ++spins) {
-            int i = 0;
-            while (i < n && __atomic_load_n(&words[i], __ATOMIC_ACQUIRE) != pending) ++i;
-            if (i == n) return FLOCKGPU_OK;
-            if ((spins & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-        }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 0;; ++spins) {
+        int i = 0;
+        while (i < n && __atomic_load_n(&words[i], __ATOMIC_ACQUIRE) != pending) ++i;
+        if (i == n) return FLOCKGPU_OK;
+        if ((spins & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
     FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FLOCKGPU_OK;
@@ -355,27 +352,15 @@ typedef int flockgpu_v4i __attribute__((ext_vector_type(4)));
 // write-back does not land on whatever kernel runs next (the q5 counters' clear cost the count pass 0.04-0.15 ms that way).
 typedef unsigned int flockgpu_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void stream_store4(void *p, uint4 v) {
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_PLAIN_STORES)   // (A/B builds only)
-    *reinterpret_cast<uint4 *>(p) = v;
-#else
     flockgpu_v4u t;
     t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
     __builtin_nontemporal_store(t, reinterpret_cast<flockgpu_v4u *>(p));
-#endif
 }
 __device__ __forceinline__ void stream_store(int32_t *p, int32_t v) {
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_PLAIN_STORES)
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 __device__ __forceinline__ void stream_store(int64_t *p, int64_t v) {
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_PLAIN_STORES)
-    *p = v;
-#else
     __builtin_nontemporal_store(v, p);
-#endif
 }
 __device__ __forceinline__ uint4 stream_load4u(const uint32_t *p) {
     const flockgpu_v4u v = __builtin_nontemporal_load(reinterpret_cast<const flockgpu_v4u *>(p));

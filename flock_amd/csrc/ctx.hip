@@ -210,7 +210,6 @@ int flockgpu_malloc_guarded(flockgpu_ctx *ctx, size_t bytes, void **out_device_p
     FG_HIP(ctx, hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityMinimum));
     if (gran == 0) return fail(ctx, FLOCKGPU_ERR_HIP, "flockgpu_malloc_guarded: zero allocation granularity");
     size_t want = ((bytes ? bytes : 16) + 15) & ~size_t(15);
-    if (const char *a = flockgpu::exp_env("FLOCKGPU_GUARD_ALIGN")) want = (want + (size_t)atoll(a) - 1) / (size_t)atoll(a) * (size_t)atoll(a);   // (experiment: coarser start alignment)
     flockgpu::GuardedAlloc g;
     g.mapped = (want + gran - 1) / gran * gran;
     g.reserved = g.mapped + gran;

@@ -75,7 +75,8 @@ __global__ __launch_bounds__(kBlock) void q11_gather_kernel(const int64_t *__res
 // time in the middle of the representable span; all arithmetic modulo 2^64, so a value that fits is restored exactly).  A row that does
 // not fit raises `unfit` and the host falls back to the gather.  Rows arrive in epoch order, so a thread finds its first row's epoch by
 // bisection and walks on from there.  The pass reads the bidder column as well and leaves its minimum / maximum (the sort's digit range):
-// one launch instead of key_min_max's.
+// one launch instead of key_min_max's.  `mode` is 0 in every call (its bits cut phases out: 1 no slot atomics, 2 no bisection, 4 no stores); it
+// stays a runtime argument because the kernel compiled without it holds 37 VGPRs instead of 33.
 constexpr int kPackItems = 8;
 constexpr int kPackTile = kBlock * kPackItems;   // 2048 rows per workgroup
 constexpr int kPackSlots = 64, kPackSlotStride = 32, kPackSlot0 = 32;   // bidder minimum / maximum: slot s at minmax[kPackSlot0 + s * kPackSlotStride]
@@ -467,7 +468,7 @@ int flockgpu_q11_user_sessions(flockgpu_ctx *ctx, const flockgpu_bid_cols *bid, 
     int e_bits = 1;
     while (e_bits < 31 && ((uint32_t)(n_epochs - 1) >> e_bits)) ++e_bits;
     int t_bits = 32 - e_bits;
-    if (t_bits < 12 || exp_env("FLOCKGPU_Q11_GATHER") != nullptr) t_bits = 0;   // (A/B knob of the experimental build)
+    if (t_bits < 12) t_bits = 0;
     uint32_t *pay = nullptr;
     uint32_t *d_unfit = reinterpret_cast<uint32_t *>(d_mm + 2);
     uint64_t *d_tref = reinterpret_cast<uint64_t *>(d_mm + 4);
@@ -478,7 +479,7 @@ int flockgpu_q11_user_sessions(flockgpu_ctx *ctx, const flockgpu_bid_cols *bid, 
         {
             LaunchScope ls(ctx, "q11_pack_kernel");
             hipLaunchKernelGGL(q11_pack_kernel, dim3((unsigned)div_up(n, (int64_t)kPackTile)), dim3(kBlock), 0, ctx->stream, keys, dt, n,
-                               d_eoff, n_epochs, t_bits, pay, d_mm, d_tref, d_unfit, exp_env("FLOCKGPU_Q11_PACK_MODE") ? atoi(exp_env("FLOCKGPU_Q11_PACK_MODE")) : 0);
+                               d_eoff, n_epochs, t_bits, pay, d_mm, d_tref, d_unfit, 0);
         }
         FG_TRY(check_launch(ctx, "q11_pack_kernel"));
     } else {

@@ -652,10 +652,9 @@ __global__ __launch_bounds__(kLdsBuildThreads) void q3_window_join_lds_kernel(co
                                                                               const int64_t *__restrict__ kept_off, uint32_t cap, int32_t *__restrict__ next,
                                                                               uint32_t *err, const int32_t *__restrict__ seller, const int32_t *__restrict__ category,
                                                                               int64_t n_rows, int64_t category_lit, SegTiles st, uint32_t *__restrict__ counts,
-                                                                              uint32_t *__restrict__ heads, int32_t ab_mode) {
+                                                                              uint32_t *__restrict__ heads) {
     __shared__ uint64_t s_tab[kLdsBuildCap];
     const int32_t w = (int32_t)blockIdx.x;
-    // (ab_mode: phase cut-outs of experimental builds -- 1: no probe phase, 2: no inserts, 3: probe without table lookups; 0 in the shipped library)
     // the window's persons that passed the state filter: a compact row list a streaming pass wrote (q3_state_flag_kernel -> scan -> emit;
     // with the filter inside this kernel its dependent loads -- offsets, then the state's bytes -- were the workgroup's whole build phase:
     // one workgroup per CU hides no latency)
@@ -675,13 +674,12 @@ __global__ __launch_bounds__(kLdsBuildThreads) void q3_window_join_lds_kernel(co
         for (int k = 0; k < kPer; ++k) key[k] = p_id[row[k] < 0 ? 0 : row[k]];
 #pragma unroll
         for (int k = 0; k < kPer; ++k)
-            if (row[k] >= 0 && ab_mode != 2 && !multimap_insert_marked(s_tab, cap, next, key[k], row[k])) full = true;
+            if (row[k] >= 0 && !multimap_insert_marked(s_tab, cap, next, key[k], row[k])) full = true;
     }
     if (__syncthreads_or(full)) {   // the window's persons do not fit the LDS table: the host repeats the call on the global tables
         if (threadIdx.x == 0) atomicOr(err, 1u);
         return;
     }
-    if (ab_mode == 1) return;
     // ---- probe: quarter q of the workgroup takes tile first + 4 g + q of the window
     const int32_t t_first = st.tile_first[w], t_end = st.tile_first[w + 1];
     const int quarter = threadIdx.x >> 8, lt = threadIdx.x & 255, lwave = lt >> 6, lane = lane_id();
@@ -711,7 +709,7 @@ __global__ __launch_bounds__(kLdsBuildThreads) void q3_window_join_lds_kernel(co
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int64_t r = r0 + j;
-                    need[j] = r >= tr.lo && r < tr.hi && (int64_t)cv[i][j] == category_lit && ab_mode != 3;
+                    need[j] = r >= tr.lo && r < tr.hi && (int64_t)cv[i][j] == category_lit;
                     slot[j] = slot_of((uint32_t)sv[i][j], cap);
                     first[j] = s_tab[need[j] ? slot[j] : 0u];
                 }
@@ -956,8 +954,7 @@ int flockgpu_q3_join(flockgpu_ctx *ctx, const flockgpu_auction_cols *auction, co
     // totals in ONE synchronisation (three before: statistics, pair counts, byte totals; ~60 us each at 1e8 events where
     // the kernels take 90 us).  After a call that did not qualify the statistics are read first, as before.
     // iterations of a person tile per build workgroup: all eight when the tiles alone fill the chip, else two
-    int build_y_shift = st_p.n_tiles >= (int64_t)ctx->num_cus * 4 ? 3 : 1;
-    if (const char *e = exp_env("FLOCKGPU_Q3_YSHIFT")) build_y_shift = atoi(e);   // (experiment knob: iterations of a tile per workgroup = 1 << shift)
+    const int build_y_shift = st_p.n_tiles >= (int64_t)ctx->num_cus * 4 ? 3 : 1;
     std::vector<int64_t> &regime = ctx->host_i64["q3.dense_regime"];
     // 2: dense, every window gapless last time (bit blocks, no row table) -- also where a ctx starts; 1: dense with the row table;
     // 0: the last call took the general path
@@ -992,11 +989,10 @@ int flockgpu_q3_join(flockgpu_ctx *ctx, const flockgpu_auction_cols *auction, co
     std::vector<int64_t> &fast = ctx->host_i64["q3.fast_hint"];   // {rows the take is laid out for, byte capacity x 3, valid}
     if (fast.size() != 5) fast.assign(5, 0);
     bool fast_done = false;
-    static const bool no_fast = exp_env("FLOCKGPU_Q3_NO_FAST") != nullptr;   // (A/B knob)
     // (beyond a few thousand tiles the self-scans cost more than the scan launches they replace: 1e9 events, 7324 + 3 x 5860 tiles, ran
     // 0.571 vs 0.530 ms -- and there the launches and waits are a small part of the call anyway)
-    static const int64_t fast_max_tiles = exp_env("FLOCKGPU_Q3_FAST_MAX_TILES") ? atoll(exp_env("FLOCKGPU_Q3_FAST_MAX_TILES")) : 2048;
-    bool fast_ok = try_dense && bits_mode && fast[4] && !no_fast && st_a.n_tiles > 0 && st_a.n_tiles <= fast_max_tiles && st_p.n_tiles > 0;
+    constexpr int64_t fast_max_tiles = 2048;
+    bool fast_ok = try_dense && bits_mode && fast[4] && st_a.n_tiles > 0 && st_a.n_tiles <= fast_max_tiles && st_p.n_tiles > 0;
     for (int w = 0; w < n_win && fast_ok; ++w)
         if (pe[w] == pb[w] && ae[w] > ab[w]) fast_ok = false;   // (a window without persons leaves its table entry unwritten)
     if (fast_ok) {
@@ -1278,8 +1274,7 @@ int flockgpu_q3_join(flockgpu_ctx *ctx, const flockgpu_auction_cols *auction, co
         // dropped its share; a ctx whose last such bet was lost builds in global memory until its windows shrink
         std::vector<int64_t> &lds_state = ctx->host_i64["q3.lds_build"];   // {rows of the largest window when a bet was lost}
         if (lds_state.empty()) lds_state.push_back(0);
-        static const bool no_lds_build = exp_env("FLOCKGPU_Q3_NO_LDS_BUILD") != nullptr;   // (A/B knob)
-        bool lds_build = !no_lds_build && n_win > 0 && st_p.n_tiles > 0 && max_person_rows <= 2 * (int64_t)kLdsBuildCap &&
+        bool lds_build = n_win > 0 && st_p.n_tiles > 0 && max_person_rows <= 2 * (int64_t)kLdsBuildCap &&
                          (cap64 <= kLdsBuildCap || lds_state[0] == 0 || max_person_rows < lds_state[0]);
         uint32_t cap = 0;
         uint64_t *tables = nullptr;
@@ -1313,8 +1308,7 @@ int flockgpu_q3_join(flockgpu_ctx *ctx, const flockgpu_auction_cols *auction, co
                 FG_TRY(emit_flagged_rows(ctx, st_p, p_flags, p_counts, p_base, p_rows));
                 LaunchScope ls(ctx, "q3_window_join_lds_kernel");
                 hipLaunchKernelGGL(q3_window_join_lds_kernel, dim3((unsigned)n_win), dim3(kLdsBuildThreads), 0, ctx->stream, person->p_id, p_rows, p_off, cap, next,
-                                   d_err, auction->seller, auction->category, auction->rows, category_lit, st_a, counts, heads,
-                                   exp_env("FLOCKGPU_Q3W_MODE") ? atoi(exp_env("FLOCKGPU_Q3W_MODE")) : 0);
+                                   d_err, auction->seller, auction->category, auction->rows, category_lit, st_a, counts, heads);
                 FG_TRY(check_launch(ctx, "q3_window_join_lds_kernel"));
             } else {
                 FG_TRY(arena_get_t(ctx, "q3.tables", (size_t)cap * std::max(n_win, 1), &tables));

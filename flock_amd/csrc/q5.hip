@@ -30,36 +30,20 @@ namespace {
 constexpr int kQ5Iters = 8;
 constexpr int kQ5Tile = kBlock * 4 * kQ5Iters;  // 8192 rows
 constexpr int kHist = 4096;                     // direct-mapped LDS histogram bins (u32)
-constexpr int kHistPad = 64;                    // one scratch bin per lane for "not mine" adds
+constexpr int kHistPad = 64;                    // 64 words past the bins (zeroed with them, not counted into)
 constexpr int kSlots = kHist / 2;               // the same LDS viewed as packed {key:32,count:32} hash slots
 constexpr int kSlotBits = 11;
 static_assert(kSlots == (1 << kSlotBits), "slot bits");
 constexpr int kLdsMaxProbe = 24;
 constexpr uint32_t kFib = 0x9E3779B1u;
-// The count kernel's LDS phase: 1 (shipped) = lanes holding the wave's hot key issue no LDS atomic at all (exec-masked); 0 = they add to
-// a private scratch bin instead (branch-free, rounds 1-3); 2 = 1 + four lane-indexed replicas of every bin while the tile's span leaves
-// room.  A/B on one box, alternating (tools/gpu_ab_libs.sh, round 4): 0.741 / 0.728 / 0.730 and 0.753 / 0.732 / 0.728 ms per 1e9 bids --
-// the scratch-bin adds cost 2 %, and replicas buy nothing on top: with half the lanes masked off, the ~32 that remain spread over the
-// ~110 auctions in flight collide rarely enough (the counters' "two thirds of the LDS cycles are bank conflicts" was mostly the hot
-// lanes' 64 scratch adds folding twice over the 32 banks).  Round 6, after tools/micro/stream_read.hip showed the phase costing 0.08 ms on top
-// of the stream: 3 = variant 1 with a row's instructions written out in assembly (2 VALU + 4 SALU + 1 DS per row instead of the compiler's
-// 5 + 4 + 1): 0.694 against 0.693 ms, nothing; 5 = the same without the exec mask, the hot lanes adding to scratch bins (3 + 2 + 1): 0.711
-// against 0.688; hot rows counted per lane (3 + 2 + 1, no ballot): 1.30 ms, the wave-wide sum at every change of candidate costs more than
-// the ballots.  The phase is bound by the LDS adds that are executed, lane by lane -- not by the instructions around them.  Variants other than 1
-// exist in experimental builds only.
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_Q5_VARIANT)
-constexpr int kQ5Variant = FLOCKGPU_AB_Q5_VARIANT;
-#else
-constexpr int kQ5Variant = 1;
-#endif
-constexpr int kQ5WaveForm = 0;                  // count kernel form of the shipped build: 0 = one workgroup per tile, 1 / 2 / 4 = one WAVE per tile, that many waves per workgroup
-constexpr int kQ5WavesPerCu = 20;               // persistent wave form: waves per CU in the grid (8 KB of LDS each)
+// The count kernel's LDS phase: lanes holding the wave's hot key issue no LDS atomic at all (exec-masked); the phase is bound by the LDS adds
+// that are executed, lane by lane -- not by the instructions around them.  (Other forms of the phase and of the count pass lost: DESIGN.md
+// section 10, profiles/r06/q5_variants_ab.md.)
 // 16-bit counters (round 6): two keys share a 32-bit word of the counter arena (key - base even: low half).  What bounds the q5 step is the
 // bytes it moves, reads and writes together (profiles/r06/q5_variants_ab.md): half-width counters halve the zeroes stored per call, the max /
 // select sweeps and the lines the flush atomics touch.  A (pane, key) count above 65535 carries into its neighbour or out of the word --
 // either way the pane's counter SUM comes out below its row count, which the max pass adds up anyway: q5_finish_kernel compares, and a
 // mismatch makes the host repeat the call with 32-bit counters and keep them for this ctx (NEXMark's hottest auction draws ~770 bids).
-constexpr bool kQ5Counters16 = true;
 constexpr int kHotMin = 16;                     // a candidate seen in fewer lanes than this is not "hot"
 constexpr int kMaxWinPanes = 8;                 // windows of more panes use the hash tables only
 constexpr uint32_t kWideTile = 0x40000000u;     // slow-list tag: declined for its key spread (not for being ragged)
@@ -328,7 +312,7 @@ __device__ __forceinline__ void q5_layout_block(const int32_t *__restrict__ rng,
 __global__ __launch_bounds__(kBlock) void q5_clear_kernel(uint32_t *__restrict__ counters, uint64_t cnt_host,
                                                           uint64_t cnt_from, uint64_t *__restrict__ tables, uint64_t table_words,
                                                           uint64_t *__restrict__ meta, uint64_t meta_words, int32_t *__restrict__ slow_list,
-                                                          uint32_t *__restrict__ block_max, uint64_t block_max_words, int plain_stores, int c16, LayoutArgs lay) {
+                                                          uint32_t *__restrict__ block_max, uint64_t block_max_words, int c16, LayoutArgs lay) {
     if (lay.rng && blockIdx.x == 0) q5_layout_block(lay.rng, lay.pane_win_ptr, lay.seg_off, lay.n_panes, lay.n_win, lay.capacity, lay.budget_bytes, lay.panes, lay.wins, lay.info);
     uint64_t cnt = cnt_host;                // counters to zero (a speculating call: all the arena holds -- the layout is being made next door) ...
     if (c16) cnt = (cnt + 1) / 2;           // ... and the 32-bit words that hold them (cnt_from is in words, too)
@@ -336,9 +320,7 @@ __global__ __launch_bounds__(kBlock) void q5_clear_kernel(uint32_t *__restrict__
     const uint4 z = make_uint4(0, 0, 0, 0);
     // (non-temporal: the zeroes go to HBM as they are written instead of lingering as dirty lines whose write-back lands on the kernel that
     // runs next -- measured: +0.04 ms on whichever kernel followed the clear)
-    if (plain_stores) {   // (FLOCKGPU_Q5_PLAIN_CLEAR: the round-1 behaviour, kept for the counter-level A/B in profiles/r02/q5_clear_policy.txt)
-        for (uint64_t i = i0 + cnt_from / 4; i * 4 < cnt + 3; i += stride) reinterpret_cast<uint4 *>(counters)[i] = z;
-    } else
+    // (cached stores measured against these: profiles/r02/q5_clear_policy.txt)
     for (uint64_t i = i0 + cnt_from / 4; i * 4 < cnt + 3; i += stride) {
         uint32_t *p = counters + i * 4;
         __builtin_nontemporal_store(0u, p);
@@ -469,83 +451,13 @@ __device__ __forceinline__ void q5_count_tile(const int32_t *__restrict__ auctio
     // hot key of this wave, kept in scalar registers across iterations
     int32_t hot = __builtin_amdgcn_readfirstlane(k[0][0]);
     uint32_t hot_cnt = 0;
-    const bool rep = kQ5Variant == 2 && span * 4 + 3 < (uint32_t)kHist;   // (block-uniform) room for four replicas of every bin
-    const uint32_t rmul = rep ? 4u : 1u, radd = rep ? (uint32_t)(lane & 3) : 0u;
-    if (kQ5Variant == 3 || kQ5Variant == 5) {
-        // Variant 1 with the row's instructions written out: the hot key's rows are counted as the complement of the rows that go to the
-        // histogram (one population count of the SAME mask that becomes the exec mask), a row's bin is one shift-add from its key, and the
-        // constant 1 stays in a register: 2 VALU + 4 SALU + 1 DS instruction per row where the compiler's form of variant 1 issues 5 + 4 + 1.
-        // (A wave64 instruction holds its SIMD16 for four cycles and the CU's scalar unit serves a SIMD every fourth cycle: at eight waves per
-        // SIMD this phase is bound by its instruction count, and while a workgroup is in it, it has no loads in flight -- tools/micro/stream_read.hip.
-        // Counting the cold rows per LANE instead -- 3 VALU + 2 SALU -- was run, too: the wave-wide sum it needs whenever the candidate changes
-        // costs more than it saves, the candidate changes in most iterations of NEXMark's bids: 1.30 ms against 0.71.)
-        uint32_t cold = 0;                         // (wave-uniform) rows since the last switch of candidates that were NOT the candidate's
-        uint32_t since = 0;                        // (wave-uniform) rows since that switch
-        uint32_t one = 1;
-        asm volatile("" : "+v"(one));              // (kept in a register: the compiler re-made the constant in front of every LDS add)
-        // the LDS byte address of bin 0 minus four times the tile's minimum: a key's bin is at (key << 2) + this
-        const uint32_t hist_at_mn = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)hist - ((uint32_t)mn << 2));
-#pragma unroll
-        for (int it = 0; it < kQ5Iters; ++it) {
-            const uint64_t b0 = __ballot(k[it][0] == hot);
-            if ((int)__builtin_popcountll(b0) < kHotMin) {
-                // the candidate went cold: park its count, then try this iteration's first two distinct keys
-                if (since != cold) {
-                    if (lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], since - cold);
-                }
-                cold = 0;
-                since = 0;
-                const int32_t c1 = __builtin_amdgcn_readfirstlane(k[it][0]);
-                const uint64_t m1 = __ballot(k[it][0] == c1);
-                hot = c1;
-                if ((int)__builtin_popcountll(m1) < kHotMin && ~m1) {
-                    const int l2 = __ffsll((unsigned long long)~m1) - 1;
-                    const int32_t c2 = __builtin_amdgcn_readlane(k[it][0], l2);
-                    const uint64_t m2 = __ballot(k[it][0] == c2);
-                    if (__builtin_popcountll(m2) > __builtin_popcountll(m1)) hot = c2;
-                }
-            }
-            since += 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                // if (k != hot) hist[k - mn] += 1, and cold += the number of such lanes
-                uint32_t bin, n_cold;
-                unsigned long long saved;
-                if (kQ5Variant == 5) {   // (A/B builds: no exec mask -- the hot key's lanes add to a scratch bin of their own)
-                    const uint32_t scratch = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)hist + (uint32_t)(kHist + lane) * 4u;
-                    asm volatile("v_cmp_ne_u32 vcc, %[hot], %[key]\n\t"
-                                 "s_bcnt1_i32_b64 %[n_cold], vcc\n\t"
-                                 "v_lshl_add_u32 %[bin], %[key], 2, %[base]\n\t"
-                                 "v_cndmask_b32 %[bin], %[scratch], %[bin], vcc\n\t"
-                                 "ds_add_u32 %[bin], %[one]"
-                                 : [bin] "=&v"(bin), [n_cold] "=&s"(n_cold)
-                                 : [hot] "s"(hot), [key] "v"(k[it][j]), [base] "s"(hist_at_mn), [one] "v"(one), [scratch] "v"(scratch)
-                                 : "vcc", "scc", "memory");
-                    cold += n_cold;
-                    continue;
-                }
-                asm volatile("v_cmp_ne_u32 vcc, %[hot], %[key]\n\t"
-                             "s_bcnt1_i32_b64 %[n_cold], vcc\n\t"
-                             "s_and_saveexec_b64 %[saved], vcc\n\t"
-                             "v_lshl_add_u32 %[bin], %[key], 2, %[base]\n\t"
-                             "ds_add_u32 %[bin], %[one]\n\t"
-                             "s_mov_b64 exec, %[saved]"
-                             : [bin] "=&v"(bin), [saved] "=&s"(saved), [n_cold] "=&s"(n_cold)
-                             : [hot] "s"(hot), [key] "v"(k[it][j]), [base] "s"(hist_at_mn), [one] "v"(one)
-                             : "vcc", "scc", "memory");
-                cold += n_cold;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the LDS adds above are not the compiler's to count)
-        if (since != cold && lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], since - cold);
-    } else {
 #pragma unroll
     for (int it = 0; it < kQ5Iters; ++it) {
         uint64_t b0 = __ballot(k[it][0] == hot);
         if (__popcll((unsigned long long)b0) < kHotMin) {
             // the candidate went cold: park its count, then try this iteration's first two distinct keys
             if (hot_cnt) {
-                if (lane == 0) atomicAdd(&hist[((uint32_t)hot - (uint32_t)mn) * rmul], hot_cnt);
+                if (lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], hot_cnt);
                 hot_cnt = 0;
             }
             const int32_t c1 = __builtin_amdgcn_readfirstlane(k[it][0]);
@@ -567,26 +479,16 @@ __device__ __forceinline__ void q5_count_tile(const int32_t *__restrict__ auctio
             const bool is_hot = k[it][j] == hot;
             const uint64_t b = (j == 0) ? b0 : __ballot(is_hot);
             hot_cnt += (uint32_t)__popcll((unsigned long long)b);
-            if (kQ5Variant == 0) {
-                // branch-free: lanes holding the hot key hit their private scratch bin instead
-                const uint32_t bin = is_hot ? (uint32_t)(kHist + lane) : (uint32_t)k[it][j] - (uint32_t)mn;
-                atomicAdd(&hist[bin], 1u);
-            } else if (!is_hot) {
-                atomicAdd(&hist[((uint32_t)k[it][j] - (uint32_t)mn) * rmul + radd], 1u);
-            }
+            if (!is_hot) atomicAdd(&hist[(uint32_t)k[it][j] - (uint32_t)mn], 1u);   // (lanes holding the hot key issue no LDS atomic)
         }
     }
-    if (hot_cnt && lane == 0) atomicAdd(&hist[((uint32_t)hot - (uint32_t)mn) * rmul], hot_cnt);
-    }
+    if (hot_cnt && lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], hot_cnt);
     __syncthreads();
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_Q5_ABLATE)   // (ablation builds, WRONG results by design: what the flush costs)
-    if (hist[threadIdx.x] != 0x7fffffffu) return;
-#endif
-    if (!full_tile) {   // hand the copies of key0 back (block-uniform branch; with replicas the SUM over a bin's four comes out right)
-        if (threadIdx.x == 0) hist[((uint32_t)key0 - (uint32_t)mn) * rmul] -= (uint32_t)(kQ5Tile - (tr.hi - tr.lo));
+    if (!full_tile) {   // hand the copies of key0 back (block-uniform branch)
+        if (threadIdx.x == 0) hist[(uint32_t)key0 - (uint32_t)mn] -= (uint32_t)(kQ5Tile - (tr.hi - tr.lo));
         __syncthreads();
     }
-    if (c16 && kQ5Variant != 2) {   // (block-uniform) an even key and its successor: one atomic on the word they share
+    if (c16) {   // (block-uniform) an even key and its successor: one atomic on the word they share
         const uint32_t d = (uint32_t)mn & 1u;   // bins are indexed from mn, pairs from the even key at or below it (offsets, so that a range across 0 needs no care)
         for (uint32_t s = threadIdx.x * 2; s <= span + d; s += kBlock * 2) {
             const uint32_t c0 = s >= d ? hist[s - d] : 0u, c1 = s + 1 - d <= span ? hist[s + 1 - d] : 0u;
@@ -595,13 +497,7 @@ __device__ __forceinline__ void q5_count_tile(const int32_t *__restrict__ auctio
         return;
     }
     for (uint32_t s = threadIdx.x; s <= span; s += kBlock) {
-        uint32_t c;
-        if (rep) {
-            const uint4 r4 = *reinterpret_cast<const uint4 *>(&hist[s * 4]);
-            c = r4.x + r4.y + r4.z + r4.w;
-        } else {
-            c = hist[s];
-        }
+        const uint32_t c = hist[s];
         if (c) emit_pair((int32_t)((uint32_t)mn + s), c, f);
     }
 }
@@ -618,432 +514,9 @@ __global__ __launch_bounds__(kBlock) void q5_count_kernel(const int32_t *__restr
     __shared__ int32_t s_red[8];
     __shared__ unsigned long long s_w[kWavesPerBlock];
     if (spec_info && !spec_info[2]) return;  // the device layout declined this call
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_Q5_PERSIST)   // (A/B builds only: num_cus x 8 workgroups walk the tiles)
-    for (int32_t tile = (int32_t)blockIdx.x; tile < st.n_tiles; tile += (int32_t)gridDim.x) {
-        q5_count_tile<kWeighted>(auction, weight, st, panes, pane_win_ptr, pane_win_idx, counters, tables, cap, tab_used, err, slow_list, pane_wsum, tile, hist, s_red, s_w, c16 != 0, tab_rows);
-        __syncthreads();   // the next tile zeroes the histogram and rewrites the reduction slots
-    }
-#else
     q5_count_tile<kWeighted>(auction, weight, st, panes, pane_win_ptr, pane_win_idx, counters, tables, cap, tab_used, err, slow_list, pane_wsum, (int32_t)blockIdx.x, hist, s_red, s_w, c16 != 0, tab_rows);
-#endif
 }
 
-#ifdef FLOCKGPU_EXPERIMENTAL   // (the count pass's other forms: measured in round 6, profiles/r06/q5_variants_ab.md; none beat the workgroup form)
-// ---- count, wave-private form (round 6) ------------------------------------------------------------------------------------------
-// The workgroup form above is co-bound by its LDS atomics (~53 % of the kernel's cycles) BECAUSE its phases are serial per workgroup: eight
-// 16-byte loads per lane, a barrier (a workgroup-scope fence: `s_waitcnt vmcnt(0)` on gfx9), the 32 LDS adds per lane, a barrier, the
-// flush -- while a workgroup counts it has nothing in flight, and the eight workgroups of a CU cover for each other only on average.
-// Here a tile belongs to ONE wave with a private 2048-bin histogram (8 KB of LDS): no barrier anywhere (a wave's DS operations complete in
-// order), so the wave streams its 8192 rows as four chunks of eight loads, the next chunk's loads in flight under the current chunk's
-// LDS adds (`vmcnt(8)`, never 0), and nothing but the wave itself waits for its flush.  Bins are indexed by the key's low 11 bits, so no
-// minimum has to be known before the first add; the tile's span (max - min, reduced over the wave at the end) says afterwards whether two
-// keys shared a bin -- such a tile adds nothing and goes to the slow list, as the tiles wider than the workgroup form's histogram do.
-constexpr int kWaveHist = 2048;
-constexpr int kWaveChunks = 4, kWaveChunkIters = kQ5Iters * (kBlock / 64) / kWaveChunks;   // 4 chunks x 8 loads x 64 lanes x 4 keys = 8192 rows
-static_assert(kWaveChunks * kWaveChunkIters * 64 * 4 == kQ5Tile, "a wave tile is a q5 tile");
-
-__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-struct WaveCountState {
-    int32_t hot;
-    uint32_t hot_cnt;
-    int32_t mn, mx;
-};
-
-// one chunk: eight iterations of the hot-key ballot + LDS adds of q5_count_tile, bins by the key's low bits
-__device__ __forceinline__ void q5_wave_chunk(const int32_t (&k)[kWaveChunkIters][4], uint32_t *hist, WaveCountState &s, const int lane) {
-#pragma unroll
-    for (int it = 0; it < kWaveChunkIters; ++it) {
-        s.mn = min(s.mn, min(min(k[it][0], k[it][1]), min(k[it][2], k[it][3])));
-        s.mx = max(s.mx, max(max(k[it][0], k[it][1]), max(k[it][2], k[it][3])));
-        uint64_t b0 = __ballot(k[it][0] == s.hot);
-        if (__popcll((unsigned long long)b0) < kHotMin) {
-            if (s.hot_cnt) {   // the candidate went cold: park its count
-                if (lane == 0) atomicAdd(&hist[(uint32_t)s.hot & (kWaveHist - 1)], s.hot_cnt);
-                s.hot_cnt = 0;
-            }
-            const int32_t c1 = __builtin_amdgcn_readfirstlane(k[it][0]);
-            const uint64_t m1 = __ballot(k[it][0] == c1);
-            s.hot = c1;
-            b0 = m1;
-            if (__popcll((unsigned long long)m1) < kHotMin && ~m1) {
-                const int l2 = __ffsll((unsigned long long)~m1) - 1;
-                const int32_t c2 = __builtin_amdgcn_readlane(k[it][0], l2);
-                const uint64_t m2 = __ballot(k[it][0] == c2);
-                if (__popcll((unsigned long long)m2) > __popcll((unsigned long long)m1)) {
-                    s.hot = c2;
-                    b0 = m2;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool is_hot = k[it][j] == s.hot;
-            const uint64_t b = (j == 0) ? b0 : __ballot(is_hot);
-            s.hot_cnt += (uint32_t)__popcll((unsigned long long)b);
-            if (!is_hot) atomicAdd(&hist[(uint32_t)k[it][j] & (kWaveHist - 1)], 1u);
-        }
-    }
-}
-
-template <int kWaves>
-__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(4, 5))) void q5_count_wave_kernel(
-    const int32_t *__restrict__ auction, SegTiles st, const PaneDesc *__restrict__ panes, const int32_t *__restrict__ pane_win_ptr,
-    const int32_t *__restrict__ pane_win_idx, uint32_t *counters, uint64_t *tables, uint32_t cap, uint32_t *tab_used, uint32_t *err,
-    int32_t *slow_list, const uint64_t *__restrict__ spec_info) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[kWaves][kWaveHist];
-    if (spec_info && !spec_info[2]) return;  // the device layout declined this call
-    const int lane = lane_id();
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int32_t tile = (int32_t)blockIdx.x * kWaves + wave;
-    if (tile >= st.n_tiles) return;
-    uint32_t *hist = s_hist[wave];
-    const TileRange tr = locate_tile(st, tile, kQ5Tile);
-    const bool full_tile = tr.lo == tr.tile_begin && tr.hi == tr.tile_begin + kQ5Tile;
-    // a uniform base (SGPRs) + one loop-invariant 32-bit lane offset: the loads then need no address VGPRs of their own
-    const char *base = reinterpret_cast<const char *>(auction + tr.tile_begin);
-    const uint32_t lane_off = (uint32_t)lane * 16u;
-    int32_t ka[kWaveChunkIters][4], kb[kWaveChunkIters][4];
-    if (!full_tile) {   // the first / last tile of a pane (~430 of 122 K at 1e9 bids): the general path
-        if (lane == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = tile;
-        return;
-    }
-    // two loop-carried 32-bit lane offsets (the 13-bit immediate reaches 4 KB), advanced once per chunk, on ONE scalar base: no address
-    // temporaries that the register allocator could place in a key register whose load the waitcnt pass still tracks
-    uint32_t o0 = lane_off, o1 = lane_off + 4096u;
-    auto load_chunk = [&](int32_t (&k)[kWaveChunkIters][4], int) {
-        asm volatile("" : "+v"(o0), "+v"(o1));
-#pragma unroll
-        for (int it = 0; it < kWaveChunkIters; ++it) {
-            const int4 t = stream_load4(reinterpret_cast<const int32_t *>(base + (it < 4 ? o0 : o1) + (it & 3) * 1024));
-            k[it][0] = t.x; k[it][1] = t.y; k[it][2] = t.z; k[it][3] = t.w;
-        }
-        o0 += kWaveChunkIters * 1024;
-        o1 += kWaveChunkIters * 1024;
-    };
-    load_chunk(ka, 0);
-    {   // the histogram is zeroed under the first chunk's loads
-        uint4 *z = reinterpret_cast<uint4 *>(hist);
-#pragma unroll
-        for (int i = 0; i < kWaveHist / 4 / 64; ++i) z[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-    }
-    FlushArgs f;
-    f.wp0 = pane_win_ptr[tr.seg];
-    f.wp1 = pane_win_ptr[tr.seg + 1];
-    if (f.wp0 == f.wp1) return;  // pane belongs to no (full) window
-    f.pane = panes[tr.seg];
-    f.pane_win_idx = pane_win_idx;
-    f.counters = counters;
-    f.tables = tables;
-    f.cap = cap;
-    f.tab_used = tab_used;
-    f.err = err;
-    WaveCountState s;
-    s.hot_cnt = 0;
-    s.mn = 0x7fffffff;
-    s.mx = (int32_t)0x80000000;
-    s.hot = 0;
-    // a rolled loop over chunk pairs: ka / kb are loop-carried, so the register allocator keeps TWO chunks of keys (64 VGPRs), not four
-#pragma unroll 1
-    for (int c = 0;; c += 2) {
-        load_chunk(kb, c + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        q5_wave_chunk(ka, hist, s, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        if (c + 2 >= kWaveChunks) break;
-        load_chunk(ka, c + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        q5_wave_chunk(kb, hist, s, lane);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    q5_wave_chunk(kb, hist, s, lane);
-    if (s.hot_cnt && lane == 0) atomicAdd(&hist[(uint32_t)s.hot & (kWaveHist - 1)], s.hot_cnt);
-    const int32_t mn = wave_min_i32(s.mn), mx = wave_max_i32(s.mx);
-    const uint32_t span = (uint32_t)mx - (uint32_t)mn;
-    if (span >= (uint32_t)kWaveHist) {  // two keys may have shared a bin: nothing is flushed, the general path counts the tile
-        if (lane == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = (int32_t)((uint32_t)tile | kWideTile);
-        return;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the lanes' adds before the lanes' reads: one wave, DS operations in order)
-    for (uint32_t o = lane; o <= span; o += 64) {
-        const uint32_t key = (uint32_t)mn + o, c = hist[key & (kWaveHist - 1)];
-        if (c) emit_pair((int32_t)key, c, f);
-    }
-}
-
-// The same, PERSISTENT: wave g of G walks tiles g, g + G, ... and its loads never stop -- chunk 0 of the NEXT tile is requested before the
-// last chunk of the current one is counted, so the flush (LDS reads, ~10 global atomics per lane) and the next tile's descriptor run under
-// eight loads in flight.  The flush zeroes the bins it reads (only [min, max] can be non-zero), so the histogram is cleared once per wave.
-// ONE rolled loop over chunk PAIRS across tiles (two copies of the chunk body, two key buffers = 64 VGPRs), the flush under a uniform branch.
-template <int kWaves>
-__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(4, 5))) void q5_count_wavep_kernel(
-    const int32_t *__restrict__ auction, const TileRange *__restrict__ tiles, int32_t n_tiles, const PaneDesc *__restrict__ panes,
-    const int32_t *__restrict__ pane_win_ptr, const int32_t *__restrict__ pane_win_idx, uint32_t *counters, uint64_t *tables, uint32_t cap,
-    uint32_t *tab_used, uint32_t *err, int32_t *slow_list, const uint64_t *__restrict__ spec_info) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[kWaves][kWaveHist];
-    if (spec_info && !spec_info[2]) return;  // the device layout declined this call
-    const int lane = lane_id();
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int32_t stride = (int32_t)gridDim.x * kWaves;
-    uint32_t *hist = s_hist[wave];
-    {
-        uint4 *z = reinterpret_cast<uint4 *>(hist);
-#pragma unroll
-        for (int i = 0; i < kWaveHist / 4 / 64; ++i) z[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-    }
-    // two loop-invariant 32-bit lane offsets (the 13-bit immediate reaches 4 KB) on a scalar base per chunk, opaque to the compiler so that no
-    // address arithmetic is re-materialised into a key register whose load the waitcnt pass still tracks
-    uint32_t o0 = (uint32_t)lane * 16u, o1 = o0 + 4096u;
-    asm volatile("" : "+v"(o0), "+v"(o1));
-    // BUFFER loads: the tile's rows as a buffer resource in SGPRs, the chunk as the scalar offset, the lane as a 32-bit VGPR offset, the load
-    // within the chunk as the immediate -- no address arithmetic in VGPRs at all
-    auto load_chunk = [&](int32_t (&k)[kWaveChunkIters][4], __amdgpu_buffer_rsrc_t rs, int chunk) {
-#pragma unroll
-        for (int it = 0; it < kWaveChunkIters; ++it) {
-            const flockgpu_v4u t = __builtin_amdgcn_raw_buffer_load_b128(rs, (it < 4 ? o0 : o1) + (uint32_t)((it & 3) * 1024), chunk * (kWaveChunkIters * 1024), 2 /* nt */);
-            k[it][0] = (int32_t)t.x; k[it][1] = (int32_t)t.y; k[it][2] = (int32_t)t.z; k[it][3] = (int32_t)t.w;
-        }
-    };
-    FlushArgs f;
-    f.pane_win_idx = pane_win_idx;
-    f.counters = counters;
-    f.tables = tables;
-    f.cap = cap;
-    f.tab_used = tab_used;
-    f.err = err;
-    WaveCountState s;
-    s.hot = 0;
-    s.hot_cnt = 0;
-    s.mn = 0x7fffffff;
-    s.mx = (int32_t)0x80000000;
-    int32_t ka[kWaveChunkIters][4], kb[kWaveChunkIters][4];
-    // the tiles this wave streams: full tiles of panes that belong to a window; the others (a pane's first / last tile: the general path; panes
-    // of no window: nothing) are settled on the way, without loads.  t: the candidate; result: tile (-1: none), its rows' address, its pane.
-    // (`tiles` is a __restrict__ parameter of its own, not SegTiles' member: the descriptors then come through the scalar cache although
-    // the loop stores in between)
-    int32_t tile = -1, seg = 0;
-    __amdgpu_buffer_rsrc_t tbase = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(auction), 0, 0, 0x00020000);   // the tile's rows as a buffer resource
-    auto advance = [&](int32_t t) {
-        tile = -1;
-        for (;;) {
-            t = __builtin_amdgcn_readfirstlane(t);   // (wave-uniform by construction)
-            if (t >= n_tiles) return;
-            const TileRange tr = tiles[t];
-            if (pane_win_ptr[tr.seg] != pane_win_ptr[tr.seg + 1]) {
-                if (tr.lo == tr.tile_begin && tr.hi == tr.tile_begin + kQ5Tile) {
-                    tile = t;
-                    seg = tr.seg;
-                    tbase = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(auction + tr.tile_begin), 0, kQ5Tile * 4, 0x00020000);
-                    return;
-                }
-                if (lane == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = t;
-            }
-            t += stride;
-        }
-    };
-    auto flush = [&](int32_t this_tile, int32_t this_seg) {
-        if (s.hot_cnt) {   // the tile's counts are flushed: the hot key's share goes with them (the candidate itself stays)
-            if (lane == 0) atomicAdd(&hist[(uint32_t)s.hot & (kWaveHist - 1)], s.hot_cnt);
-            s.hot_cnt = 0;
-        }
-        const int32_t mn = wave_min_i32(s.mn), mx = wave_max_i32(s.mx);
-        s.mn = 0x7fffffff;
-        s.mx = (int32_t)0x80000000;
-        const uint32_t span = (uint32_t)mx - (uint32_t)mn;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the lanes' adds before the lanes' reads: one wave, DS operations in order)
-        if (span >= (uint32_t)kWaveHist) {  // two keys may have shared a bin: nothing is flushed, the general path counts the tile
-            if (lane == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = (int32_t)((uint32_t)this_tile | kWideTile);
-            uint4 *z = reinterpret_cast<uint4 *>(hist);
-#pragma unroll
-            for (int i = 0; i < kWaveHist / 4 / 64; ++i) z[i * 64 + lane] = make_uint4(0, 0, 0, 0);
-        } else {
-            f.wp0 = pane_win_ptr[this_seg];
-            f.wp1 = pane_win_ptr[this_seg + 1];
-            f.pane = panes[this_seg];
-#pragma unroll 1
-            for (uint32_t i = lane; i <= span; i += 64) {
-                const uint32_t key = (uint32_t)mn + i, cnt = hist[key & (kWaveHist - 1)];
-                if (cnt) {
-                    hist[key & (kWaveHist - 1)] = 0;
-                    emit_pair((int32_t)key, cnt, f);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    };
-    advance((int32_t)blockIdx.x * kWaves + wave);
-    if (tile < 0) return;
-    load_chunk(ka, tbase, 0);
-    int c = 0;   // the chunk pair of the current tile: chunks (c, c + 1), c = 0 or 2
-    // every trip issues exactly eight loads before each chunk body (so the waits stay `vmcnt(8 + n)`): the trip that finds no further tile
-    // leaves the loop before its second half, and the tail below counts the last chunk
-#pragma unroll 1
-    for (;;) {
-        load_chunk(kb, tbase, c + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        q5_wave_chunk(ka, hist, s, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        const int32_t this_tile = tile, this_seg = seg;
-        const bool last_pair = c != 0;
-        if (last_pair) {
-            advance(tile + stride);
-            if (tile < 0) {
-                tile = this_tile;
-                seg = this_seg;
-                break;
-            }
-        }
-        c ^= 2;
-        load_chunk(ka, tbase, c);
-        __builtin_amdgcn_sched_barrier(0);
-        q5_wave_chunk(kb, hist, s, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        if (last_pair) flush(this_tile, this_seg);
-    }
-    q5_wave_chunk(kb, hist, s, lane);
-    flush(tile, seg);
-}
-
-// The workgroup form made PERSISTENT with the next tile's loads in flight under the LDS phase and the flush (the round-2 attempts at this died
-// on `__syncthreads()`: a workgroup-scope fence, i.e. `s_waitcnt vmcnt(0)` -- the prefetch was waited for at the first barrier).  Here the
-// barriers are raw: `s_waitcnt lgkmcnt(0); s_barrier` (the LDS traffic of a wave is what the other waves must see; nothing in flight from
-// memory is anybody else's business).  Workgroup b walks tiles b, b + G, ...
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 6))) void q5_count_wgp_kernel(
-    const int32_t *__restrict__ auction, const TileRange *__restrict__ tiles, int32_t n_tiles, const PaneDesc *__restrict__ panes,
-    const int32_t *__restrict__ pane_win_ptr, const int32_t *__restrict__ pane_win_idx, uint32_t *counters, uint64_t *tables, uint32_t cap,
-    uint32_t *tab_used, uint32_t *err, int32_t *slow_list, const uint64_t *__restrict__ spec_info) {
-    __shared__ __attribute__((aligned(16))) uint32_t hist[kHist + kHistPad];
-    __shared__ int32_t s_red[2][8];
-    if (spec_info && !spec_info[2]) return;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    FlushArgs f;
-    f.pane_win_idx = pane_win_idx;
-    f.counters = counters;
-    f.tables = tables;
-    f.cap = cap;
-    f.tab_used = tab_used;
-    f.err = err;
-    // full tiles of counted panes are streamed; ragged ones go to the general path (as the wave forms do)
-    auto next_streamed = [&](int32_t t, TileRange *tr) -> int32_t {
-        for (; t < n_tiles; t += (int32_t)gridDim.x) {
-            *tr = tiles[t];
-            if (pane_win_ptr[tr->seg] == pane_win_ptr[tr->seg + 1]) continue;
-            if (tr->lo == tr->tile_begin && tr->hi == tr->tile_begin + kQ5Tile) return t;
-            if (threadIdx.x == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = t;
-        }
-        return -1;
-    };
-    auto load_tile = [&](int32_t (&k)[kQ5Iters][4], const TileRange &tr) {
-#pragma unroll
-        for (int it = 0; it < kQ5Iters; ++it) {
-            const int4 t = stream_load4(auction + tr.tile_begin + it * (kBlock * 4) + threadIdx.x * 4);
-            k[it][0] = t.x; k[it][1] = t.y; k[it][2] = t.z; k[it][3] = t.w;
-        }
-    };
-    TileRange tr;
-    int32_t tile = next_streamed((int32_t)blockIdx.x, &tr);
-    if (tile < 0) return;
-    int32_t k[kQ5Iters][4], kn[kQ5Iters][4];
-    load_tile(k, tr);
-    int par = 0;
-#pragma unroll 1
-    for (;;) {
-        {
-            uint4 *z = reinterpret_cast<uint4 *>(hist);
-            for (int s2 = threadIdx.x; s2 < (kHist + kHistPad) / 4; s2 += kBlock) z[s2] = make_uint4(0, 0, 0, 0);
-        }
-        int32_t mn = 0x7fffffff, mx = (int32_t)0x80000000;
-#pragma unroll
-        for (int it = 0; it < kQ5Iters; ++it) {
-            mn = min(mn, min(min(k[it][0], k[it][1]), min(k[it][2], k[it][3])));
-            mx = max(mx, max(max(k[it][0], k[it][1]), max(k[it][2], k[it][3])));
-        }
-        // the next tile: its descriptor, then its rows -- in flight from here to the top of the next trip
-        TileRange trn;
-        const int32_t next = next_streamed(tile + (int32_t)gridDim.x, &trn);
-        if (next >= 0) {
-            load_tile(kn, trn);
-            __builtin_amdgcn_sched_barrier(0);   // (the requests stay HERE: the scheduler would sink them below the LDS phase to save registers)
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        mn = wave_min_i32(mn);
-        mx = wave_max_i32(mx);
-        if (lane == 0) {
-            s_red[par][wave] = mn;
-            s_red[par][4 + wave] = mx;
-        }
-        lds_barrier();   // (histogram zeroed, extrema posted)
-        mn = min(min(s_red[par][0], s_red[par][1]), min(s_red[par][2], s_red[par][3]));
-        mx = max(max(s_red[par][4], s_red[par][5]), max(s_red[par][6], s_red[par][7]));
-        par ^= 1;
-        const uint32_t span = (uint32_t)mx - (uint32_t)mn;
-        if (span >= (uint32_t)kHist) {   // (block-uniform)
-            if (threadIdx.x == 0) slow_list[1 + atomicAdd(&slow_list[0], 1)] = (int32_t)((uint32_t)tile | kWideTile);
-        } else {
-            int32_t hot = __builtin_amdgcn_readfirstlane(k[0][0]);
-            uint32_t hot_cnt = 0;
-#pragma unroll
-            for (int it = 0; it < kQ5Iters; ++it) {
-                uint64_t b0 = __ballot(k[it][0] == hot);
-                if (__popcll((unsigned long long)b0) < kHotMin) {
-                    if (hot_cnt) {
-                        if (lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], hot_cnt);
-                        hot_cnt = 0;
-                    }
-                    const int32_t c1 = __builtin_amdgcn_readfirstlane(k[it][0]);
-                    const uint64_t m1 = __ballot(k[it][0] == c1);
-                    hot = c1;
-                    b0 = m1;
-                    if (__popcll((unsigned long long)m1) < kHotMin && ~m1) {
-                        const int l2 = __ffsll((unsigned long long)~m1) - 1;
-                        const int32_t c2 = __builtin_amdgcn_readlane(k[it][0], l2);
-                        const uint64_t m2 = __ballot(k[it][0] == c2);
-                        if (__popcll((unsigned long long)m2) > __popcll((unsigned long long)m1)) {
-                            hot = c2;
-                            b0 = m2;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool is_hot = k[it][j] == hot;
-                    const uint64_t b = (j == 0) ? b0 : __ballot(is_hot);
-                    hot_cnt += (uint32_t)__popcll((unsigned long long)b);
-                    if (!is_hot) atomicAdd(&hist[(uint32_t)k[it][j] - (uint32_t)mn], 1u);
-                }
-            }
-            if (hot_cnt && lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], hot_cnt);
-            lds_barrier();   // (every wave's adds are in)
-            f.wp0 = pane_win_ptr[tr.seg];
-            f.wp1 = pane_win_ptr[tr.seg + 1];
-            f.pane = panes[tr.seg];
-            for (uint32_t s2 = threadIdx.x; s2 <= span; s2 += kBlock) {
-                const uint32_t c = hist[s2];
-                if (c) emit_pair((int32_t)((uint32_t)mn + s2), c, f);
-            }
-        }
-        if (next < 0) break;
-        lds_barrier();   // (the bins are read: the next trip may zero them)
-        tile = next;
-        tr = trn;
-#pragma unroll
-        for (int it = 0; it < kQ5Iters; ++it)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) k[it][j] = kn[it][j];
-    }
-}
-
-#endif
 
 // ---- Partial COUNT per tile (the exchange's stage 0): the histogram phase of q5_count_kernel, then the tile's bins are written as
 // (key, count) pairs at a position claimed with ONE atomic per tile on the pane's cursor.  Ragged tiles and tiles whose keys spread wider than the histogram hand their rows out as
@@ -1146,7 +619,7 @@ __global__ __launch_bounds__(kBlock) void q5_partial_tile_kernel(const int32_t *
             const bool is_hot = k[it][j] == hot;
             const uint64_t b = (j == 0) ? b0 : __ballot(is_hot);
             hot_cnt += (uint32_t)__popcll((unsigned long long)b);
-            if (!is_hot) atomicAdd(&hist[(uint32_t)k[it][j] - (uint32_t)mn], 1u);   // (hot lanes masked, not sent to a scratch bin: the count pass's variant 1)
+            if (!is_hot) atomicAdd(&hist[(uint32_t)k[it][j] - (uint32_t)mn], 1u);   // (hot lanes masked, as in the count pass)
         }
     }
     if (hot_cnt && lane == 0) atomicAdd(&hist[(uint32_t)hot - (uint32_t)mn], hot_cnt);
@@ -1418,7 +891,7 @@ __global__ __launch_bounds__(kBlock) void q5_scan_kernel(const WinDesc *__restri
 //   as the SECOND pane of window wa = (p - 1, p): only the keys pane p - 1 does NOT cover (the others were accounted by its sweep).
 // A generic version of this (any number of panes per window and windows per pane, descriptors in LDS) measured 0.134 + 0.048 ms
 // against 0.105 + 0.015 ms of the window walk: instruction overhead ate the saved traffic.  This one is specialised to the two roles.
-// k16: 16-bit counters, two per word (see kQ5Counters16) -- a lane's 16-byte group holds EIGHT keys; the max pass then also adds up
+// k16: 16-bit counters, two per word (see the head of this file) -- a lane's 16-byte group holds EIGHT keys; the max pass then also adds up
 // every counter of the pane it reads (pane_sum: the overflow check of q5_finish_kernel).
 template <bool SELECT, bool k16>
 __global__ __launch_bounds__(kBlock) void q5_hop2_scan_kernel(const PaneDesc *__restrict__ panes, const int32_t *__restrict__ pane_wa,
@@ -1598,7 +1071,7 @@ __global__ __launch_bounds__(kFinishThreads) void q5_finish_kernel(const uint64_
     const uint32_t *tail = reinterpret_cast<const uint32_t *>(meta + 2 * (size_t)n_win);
     const uint32_t n_sel = tail[0], err = tail[1];
     // 16-bit counters: every counted pane's counters (added up by the max pass) + the rows it sent to the straggler tables = its rows, unless a
-    // count outgrew its 16 bits (kQ5Counters16).  (A call the device layout declined counted nothing: the host repeats it anyway.)
+    // count outgrew its 16 bits.  (A call the device layout declined counted nothing: the host repeats it anyway.)
     if (threadIdx.x == 0) s_bad = 0;
     __syncthreads();
     if (pane_sum && (!info || info[2]))
@@ -1957,7 +1430,6 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "q5: auction / count columns must be 16-byte aligned");
     FG_HIP(ctx, hipSetDevice(ctx->device));
     const int n_win = win->n_windows, n_panes = win->n_panes;
-    static const bool plain_clear = exp_env("FLOCKGPU_Q5_PLAIN_CLEAR") != nullptr;   // (experiment knob: cached stores in the clear, as in round 1)
 
     // pane -> windows CSR, window row counts
     std::vector<int32_t> ptr(n_panes + 1, 0), idx;
@@ -2057,8 +1529,7 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
     // found most tiles wider than the fast kernel's histogram, left when a sample of the partition's tiles is narrow again
     std::vector<int64_t> &wide_hint = ctx->host_i64["q5.wide_hint"];
     if (wide_hint.size() != 1) wide_hint.assign(1, 0);
-    static const bool no_wide = exp_env("FLOCKGPU_Q5_NO_WIDE") != nullptr;   // (A/B knob)
-    bool wide_mode = wide_hint[0] != 0 && !weight && !part && !no_wide && dense;
+    bool wide_mode = wide_hint[0] != 0 && !weight && !part && dense;
     bool wide_ran = false;   // wide mode was asked for AND feasible for this input (digit count within limits)
     bool speculate = dense && !part && hint[2] && hint[0] > 0 && !wide_mode;   // (wide mode sizes its digit count from the host-side layout)
     auto host_layout = [&]() -> int {   // the same rules on the host: first call of a ctx, the Partial stage, a declined speculation
@@ -2128,11 +1599,8 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
     if (preclean.size() != 2) preclean.assign(2, 0);
     LayoutArgs lay{};
     uint64_t clean_upto = 0;   // (in 32-bit WORDS of the arena, as preclean[1]: whatever the counters' width was when they were zeroed)
-    // 16-bit counters (kQ5Counters16): the bid path over windows of one or two panes, until a call's sum check fails on this ctx
-    static const bool no_hop2 = exp_env("FLOCKGPU_Q5_WINDOW_SCAN") != nullptr;   // (A/B knob: the window-walking passes)
-    static const bool no_c16 = exp_env("FLOCKGPU_Q5_NO_C16") != nullptr;         // (A/B knob: 32-bit counters, as in rounds 1-5)
-    const bool c16 = kQ5Counters16 && kQ5Variant != 2 && !no_c16 && !weight && !part && !wide_mode && hop2 && !no_hop2 && ctx->host_i64["q5.no_c16"].empty() &&
-                     !exp_env("FLOCKGPU_Q5_COUNT");   // (the experimental count forms keep 32-bit counters)
+    // 16-bit counters (see the head of this file): the bid path over windows of one or two panes, until a call's sum check fails on this ctx
+    const bool c16 = !weight && !part && !wide_mode && hop2 && ctx->host_i64["q5.no_c16"].empty();
     auto words_of = [&](uint64_t n_counters) -> uint64_t { return c16 ? (n_counters + 1) / 2 : n_counters; };
     if (speculate) {
         // window pane ranges for the device pass (bases / ranges are filled in there); counters for the previous call's size + 1/8
@@ -2203,11 +1671,10 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
         // 64 workgroups per window: max + select measured 0.158 / 0.122 / 0.119 / 0.145 ms with 8 / 32 / 64 / 128
         // (fewer: select cannot skip finely; more: per-workgroup prologue and the per-window atomics)
         const uint64_t per_win = n_win > 0 ? std::max<uint64_t>(cap, scan_total / n_win / 4) : cap;
-        const bool pane_walk = hop2 && !no_hop2;
+        const bool pane_walk = hop2;
         const uint64_t per_pane = n_panes > 0 ? std::max<uint64_t>(cap, cnt_total / (uint64_t)n_panes / 4) : cap;
         // (32-bit counters: max pass 0.062 / 0.073 / 0.108 ms with 32 / 64 / 128 workgroups per pane; 16-bit: max + select 0.052 / 0.050 / 0.051 / 0.056 / 0.066 ms with 8 / 16 / 24 / 32 / 48)
-        static const int hop2_blocks_env = exp_env("FLOCKGPU_Q5_HOP2_BLOCKS") ? atoi(exp_env("FLOCKGPU_Q5_HOP2_BLOCKS")) : 0;
-        const int hop2_blocks = hop2_blocks_env ? hop2_blocks_env : c16 ? 16 : 32;
+        const int hop2_blocks = c16 ? 16 : 32;
         const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>(div_up((int64_t)(pane_walk ? per_pane : per_win), kBlock * 2), 1), pane_walk ? hop2_blocks : 64);
         uint32_t *block_max = nullptr;
         const uint64_t n_block_max = (uint64_t)gx * std::max(n_win, 1) * (pane_walk ? 2 : 1);
@@ -2219,7 +1686,7 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
                 LaunchScope ls(ctx, "q5_clear_kernel");
                 hipLaunchKernelGGL(q5_clear_kernel, dim3(cg), dim3(kBlock), 0, ctx->stream, counters, speculate ? capacity : cnt_total,
                                    (attempt == 0 && speculate) ? (clean_upto & ~uint64_t(3)) : uint64_t(0), tables, (uint64_t)cap * n_win, d_meta, (uint64_t)n_meta_all,
-                                   slow_list, block_max, n_block_max, plain_clear ? 1 : 0, c16 ? 1 : 0, speculate ? lay : LayoutArgs{});
+                                   slow_list, block_max, n_block_max, c16 ? 1 : 0, speculate ? lay : LayoutArgs{});
                 if (speculate) clean_upto = std::max(clean_upto, words_of(capacity));   // (the arena is zero up to there now; only [0, counters in use) gets dirty)
             }
             FG_TRY(check_launch(ctx, "q5_clear_kernel"));
@@ -2262,44 +1729,9 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
             FG_TRY(check_launch(ctx, "q5_bucket_count_kernel"));
             FG_HIP(ctx, hipMemcpyAsync(h_sample, d_sample, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         } else if (st.n_tiles > 0 && n_win > 0) {
-#ifdef FLOCKGPU_EXPERIMENTAL
-            // (A/B knob, experimental builds: FLOCKGPU_Q5_COUNT = wg | wave1 | wave2 | wave4 | wavep1 | wavep4 | wgp, FLOCKGPU_Q5_WAVES_PER_CU)
-            static const char *count_form_env = exp_env("FLOCKGPU_Q5_COUNT");
-            const int wave_form = weight ? 0 : count_form_env ? (!strcmp(count_form_env, "wave1") ? 1 : !strcmp(count_form_env, "wave2") ? 2 : !strcmp(count_form_env, "wave4") ? 4 :
-                                                                   !strcmp(count_form_env, "wavep1") ? 101 : !strcmp(count_form_env, "wavep4") ? 104 : !strcmp(count_form_env, "wgp") ? 200 : 0) : kQ5WaveForm;
-            if (wave_form == 200) {
-                LaunchScope ls(ctx, "q5_count_kernel");
-                static const int per_cu = exp_env("FLOCKGPU_Q5_WAVES_PER_CU") ? atoi(exp_env("FLOCKGPU_Q5_WAVES_PER_CU")) : 5;   // (workgroups per CU here)
-                const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(st.n_tiles, (int64_t)ctx->num_cus * per_cu));
-                hipLaunchKernelGGL(q5_count_wgp_kernel, dim3(g), dim3(kBlock), 0, ctx->stream, auction, st.tiles, st.n_tiles, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-            } else if (wave_form > 100) {
-                LaunchScope ls(ctx, "q5_count_kernel");
-                const int kw = wave_form - 100;
-                static const int per_cu = exp_env("FLOCKGPU_Q5_WAVES_PER_CU") ? atoi(exp_env("FLOCKGPU_Q5_WAVES_PER_CU")) : kQ5WavesPerCu;
-                const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(div_up((int64_t)st.n_tiles, kw), (int64_t)ctx->num_cus * per_cu / kw));
-                if (kw == 1)
-                    hipLaunchKernelGGL(q5_count_wavep_kernel<1>, dim3(g), dim3(64), 0, ctx->stream, auction, st.tiles, st.n_tiles, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-                else
-                    hipLaunchKernelGGL(q5_count_wavep_kernel<4>, dim3(g), dim3(256), 0, ctx->stream, auction, st.tiles, st.n_tiles, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-            } else if (wave_form) {
-                LaunchScope ls(ctx, "q5_count_kernel");
-                const unsigned g = (unsigned)div_up((int64_t)st.n_tiles, wave_form);
-                if (wave_form == 1)
-                    hipLaunchKernelGGL(q5_count_wave_kernel<1>, dim3(g), dim3(64), 0, ctx->stream, auction, st, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-                else if (wave_form == 2)
-                    hipLaunchKernelGGL(q5_count_wave_kernel<2>, dim3(g), dim3(128), 0, ctx->stream, auction, st, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-                else
-                    hipLaunchKernelGGL(q5_count_wave_kernel<4>, dim3(g), dim3(256), 0, ctx->stream, auction, st, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err, slow_list, spec_info);
-            } else
-#endif
             {
                 LaunchScope ls(ctx, "q5_count_kernel");
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_Q5_PERSIST)
-                const unsigned count_grid = (unsigned)std::min<int64_t>(st.n_tiles, (int64_t)ctx->num_cus * (exp_env("FLOCKGPU_Q5_PERSIST_PER_CU") ? atoi(exp_env("FLOCKGPU_Q5_PERSIST_PER_CU")) : 8));
-#else
-                const unsigned count_grid = (unsigned)st.n_tiles;
-#endif
-                hipLaunchKernelGGL(weight ? q5_count_kernel<true> : q5_count_kernel<false>, dim3(count_grid), dim3(kBlock), 0,
+                hipLaunchKernelGGL(weight ? q5_count_kernel<true> : q5_count_kernel<false>, dim3((unsigned)st.n_tiles), dim3(kBlock), 0,
                                    ctx->stream, auction, weight, st, d_panes, d_ptr, d_idx, counters, tables, cap, d_used, d_err,
                                    slow_list, spec_info, d_wsum, c16 ? 1 : 0, c16 ? d_tab_rows : (unsigned long long *)nullptr);
             }
@@ -2579,15 +2011,14 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
     out->win_groups = wgrp.data();
     out->rows = n_sel;
     }
-    static const bool no_preclean = exp_env("FLOCKGPU_Q5_NO_PRECLEAN") != nullptr || exp_env("FLOCKGPU_Q5_PLAIN_CLEAR") != nullptr;   // (A/B knobs)
-    if (speculate && dense && cnt_total > 0 && !no_preclean) {   // clean up after use (see `preclean` above); the results above are already on their way
+    if (speculate && dense && cnt_total > 0) {   // clean up after use (see `preclean` above); the results above are already on their way
         int32_t *slow_list = nullptr;
         FG_TRY(arena_get_t(ctx, "q5.slow_list", (size_t)st.n_tiles + 2, &slow_list));
         {
             LaunchScope ls(ctx, "q5_clear_kernel");
             const unsigned cg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(div_up((int64_t)words_of(cnt_total) / 4 + 1, kBlock), (int64_t)ctx->num_cus * 16));
             hipLaunchKernelGGL(q5_clear_kernel, dim3(cg), dim3(kBlock), 0, ctx->stream, counters, cnt_total, uint64_t(0), (uint64_t *)nullptr,
-                               uint64_t(0), (uint64_t *)nullptr, uint64_t(0), slow_list, (uint32_t *)nullptr, uint64_t(0), plain_clear ? 1 : 0, c16 ? 1 : 0, LayoutArgs{});
+                               uint64_t(0), (uint64_t *)nullptr, uint64_t(0), slow_list, (uint32_t *)nullptr, uint64_t(0), c16 ? 1 : 0, LayoutArgs{});
         }
         FG_TRY(check_launch(ctx, "q5_clear_kernel"));
         preclean[0] = (int64_t)reinterpret_cast<uintptr_t>(counters);

@@ -837,9 +837,6 @@ __global__ __launch_bounds__(kJoinBlock) void q8_bucket_join_kernel(const int32_
             for (int j = 0; j < kJoinPre; ++j) {
                 const uint32_t k = sk[j];
                 if (k == kEmpty32) continue;
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(Q8_JSTOP)
-                if (Q8_JSTOP == 1) { if (k == 0x1234567u) s_m1 = 2; continue; }
-#endif
                 uint32_t sl = part_slot(k, log2nb, log2sell);
                 bool placed = false;
                 for (int probe = 0; probe < kJoinProbes; ++probe) {
@@ -895,9 +892,6 @@ __global__ __launch_bounds__(kJoinBlock) void q8_bucket_join_kernel(const int32_
             }
             if (!done) bad |= kPartErrPersons;
         }
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(Q8_JSTOP)
-        if (Q8_JSTOP == 3) { if (unique && rel == 0xFFFFFu) atomicOr(err, 4u); return; }
-#endif
         if (unique) flag_bytes[(size_t)tile * kFlagTile + rel] = 1;
     };
     {   // the requested entries: every stage for all of them together (LDS round trips in flight side by side)
@@ -911,14 +905,6 @@ __global__ __launch_bounds__(kJoinBlock) void q8_bucket_join_kernel(const int32_
 #pragma unroll
         for (int j = 0; j < kJoinPre; ++j)
             if (slot[j] == 0) slot[j] = seller_slot(pk[j], first[j]);
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(Q8_JSTOP)
-        if (Q8_JSTOP == 2) {
-            uint32_t c_ = 0;
-            for (int j = 0; j < kJoinPre; ++j) c_ += slot[j] >= 0;
-            if (c_ == 77u) atomicOr(err, 4u);
-            return;
-        }
-#endif
 #pragma unroll
         for (int j = 0; j < kJoinPre; ++j) owner[j] = slot[j] >= 0 ? atomicCAS(&s_own[slot[j]], kEmpty32, sp_tbeg[pt[j]] + pr[j]) : 0u;
 #pragma unroll

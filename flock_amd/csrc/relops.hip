@@ -74,15 +74,6 @@ __global__ __launch_bounds__(kBlock) void mask_flag_kernel(const uint8_t *__rest
 }
 
 // ---- group by
-__global__ __launch_bounds__(kBlock) void group_init_kernel(int64_t *__restrict__ tk, uint64_t *__restrict__ ta, int32_t *__restrict__ tf,
-                                                            int64_t slots, uint32_t *__restrict__ err) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *err = 0u;   // (instead of a hipMemsetAsync of its own: ~10 us of host time each)
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < slots; i += (int64_t)gridDim.x * kBlock) {
-        tk[i] = kEmptyKey;
-        ta[i] = 0;
-        tf[i] = 0x7fffffff;
-    }
-}
 // slot of `key` in an open-addressing table of `cap` (power of two) slots, claiming an empty one; -1: table full
 // (probing is cut off after kClaimProbes slots: in a table at most half full a longer run does not happen, and in one sized from a hint
 // that turned out too small -- group_by_key64_n -- it must end in "full", not in a walk over the whole table per row)
@@ -103,34 +94,6 @@ __device__ __forceinline__ int64_t claim_slot(int64_t *tk, uint64_t cap, int64_t
         s = (s + 1) & (cap - 1);
     }
     return -1;
-}
-__device__ __forceinline__ int64_t find_slot(const int64_t *tk, uint64_t cap, int64_t key) {
-    if (key == kEmptyKey) return (int64_t)cap;
-    uint64_t s = mix64((uint64_t)key) & (cap - 1);
-    for (uint64_t probe = 0; probe < cap; ++probe) {
-        const int64_t cur = tk[s];
-        if (cur == kEmptyKey) return -1;
-        if (cur == key) return (int64_t)s;
-        s = (s + 1) & (cap - 1);
-    }
-    return -1;
-}
-__global__ __launch_bounds__(kBlock) void group_insert_kernel(const int64_t *__restrict__ keys, const uint64_t *__restrict__ values,
-                                                              int32_t kind, int64_t n, int64_t *tk, uint64_t *ta, int32_t *tf, uint64_t cap,
-                                                              uint32_t *err) {
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const int64_t key = keys[i];
-        const int64_t s = claim_slot(tk, cap, key);
-        if (s < 0) {
-            atomicOr(err, 1u);
-            continue;
-        }
-        if (s == (int64_t)cap) tk[s] = key;  // the dedicated slot of the sentinel key
-        atomicMin(&tf[s], (int32_t)i);
-        const uint64_t v = values ? values[i] : 1ull;
-        if (kind == (int32_t)AggKind::SUM) atomicAdd(reinterpret_cast<unsigned long long *>(&ta[s]), (unsigned long long)v);
-        else if (kind == (int32_t)AggKind::MAX) atomicMax(reinterpret_cast<unsigned long long *>(&ta[s]), (unsigned long long)v);
-    }
 }
 // (the pass that runs behind the inserts also hands their error word to the host: `h_err` is pinned memory, read after the next wait)
 __global__ __launch_bounds__(kBlock) void live_slot_mask_kernel(const int32_t *__restrict__ tf, int64_t slots, uint8_t *__restrict__ mask,
@@ -1596,7 +1559,9 @@ int add_i32(flockgpu_ctx *ctx, int32_t *data, int64_t n, int32_t delta) {
     return FLOCKGPU_OK;
 }
 
-int mask_to_rows(flockgpu_ctx *ctx, const char *name, const uint8_t *mask, int64_t rows, int32_t **out_rows, int64_t *n_out) {
+// A byte mask (1 = keep) -> its rows, for the operators' own bookkeeping: rows with mask != 0, in order.  *out_rows: ctx-owned (arena key
+// `name`), n_out through ONE synchronisation.
+static int mask_to_rows(flockgpu_ctx *ctx, const char *name, const uint8_t *mask, int64_t rows, int32_t **out_rows, int64_t *n_out) {
     const std::string base = name;
     int32_t *o_rows = nullptr;
     FG_TRY(arena_get_t(ctx, (base + ".rows").c_str(), (size_t)std::max<int64_t>(rows, 0) + 4, &o_rows));
@@ -1673,48 +1638,6 @@ int take_column(flockgpu_ctx *ctx, const char *name, const DevColumn &src, const
     out->values = p;
     if (src.type == ColType::I32) return gather_i32(ctx, static_cast<const int32_t *>(src.values), rows, n, static_cast<int32_t *>(p));
     return gather_i64(ctx, static_cast<const int64_t *>(src.values), rows, n, static_cast<int64_t *>(p));
-}
-
-int group_by_key64(flockgpu_ctx *ctx, const char *name, const int64_t *keys, const uint64_t *values, AggKind kind, int64_t rows,
-                   GroupResult *out) {
-    *out = GroupResult{};
-    const std::string base = name;
-    if (rows >= (int64_t(1) << 30)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^30 rows in a generic GROUP BY", name);
-    const uint64_t cap = pow2_at_least((uint64_t)std::max<int64_t>(rows, 1) * 2);
-    const int64_t slots = (int64_t)cap + 1;
-    int64_t *tk = nullptr;
-    uint64_t *ta = nullptr;
-    int32_t *tf = nullptr;
-    uint8_t *live = nullptr;
-    uint32_t *d_err = nullptr, *h_err = nullptr;
-    FG_TRY(arena_get_t(ctx, (base + ".tk").c_str(), (size_t)slots, &tk));
-    FG_TRY(arena_get_t(ctx, (base + ".ta").c_str(), (size_t)slots, &ta));
-    FG_TRY(arena_get_t(ctx, (base + ".tf").c_str(), (size_t)slots, &tf));
-    FG_TRY(arena_get_t(ctx, (base + ".live").c_str(), (size_t)slots + 16, &live));
-    FG_TRY(arena_get_t(ctx, (base + ".err").c_str(), 4, &d_err));
-    FG_TRY(pinned_get_t(ctx, (base + ".err").c_str(), 4, &h_err));
-    RELOPS_LAUNCH(ctx, "group_init_kernel", group_init_kernel, slots, tk, ta, tf, slots, d_err);
-    if (rows > 0)
-        RELOPS_LAUNCH(ctx, "group_insert_kernel", group_insert_kernel, rows, keys, values, (int32_t)kind, rows, tk, ta, tf, cap, d_err);
-    RELOPS_LAUNCH(ctx, "live_slot_mask_kernel", live_slot_mask_kernel, slots, tf, slots, live, d_err, h_err);
-    int32_t *slot_rows = nullptr;
-    int64_t n_groups = 0;
-    FG_TRY(mask_to_rows(ctx, (base + ".sel").c_str(), live, slots, &slot_rows, &n_groups));  // synchronises
-    if (*h_err) return fail(ctx, FLOCKGPU_ERR_CAPACITY, "%s: group table overflow", name);
-    int64_t *ok = nullptr;
-    uint64_t *oa = nullptr;
-    int32_t *of = nullptr;
-    FG_TRY(arena_get_t(ctx, (base + ".ok").c_str(), (size_t)n_groups + 2, &ok));
-    FG_TRY(arena_get_t(ctx, (base + ".oa").c_str(), (size_t)n_groups + 2, &oa));
-    FG_TRY(arena_get_t(ctx, (base + ".of").c_str(), (size_t)n_groups + 4, &of));
-    FG_TRY(gather_i64(ctx, tk, slot_rows, n_groups, ok));
-    FG_TRY(gather_i64(ctx, reinterpret_cast<const int64_t *>(ta), slot_rows, n_groups, reinterpret_cast<int64_t *>(oa)));
-    FG_TRY(gather_i32(ctx, tf, slot_rows, n_groups, of));
-    out->n_groups = n_groups;
-    out->keys = ok;
-    out->agg = oa;
-    out->first_row = of;
-    return FLOCKGPU_OK;
 }
 
 int group_by_key64_n(flockgpu_ctx *ctx, const char *name, const int64_t *keys, int64_t rows, const AggSpec *specs, int n_specs,

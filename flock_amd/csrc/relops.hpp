@@ -33,7 +33,6 @@ struct DevColumn {
 };
 
 enum class CmpOp : int32_t { EQ = 0, NE = 1, LT = 2, LE = 3, GT = 4, GE = 5 };
-enum class AggKind : int32_t { NONE = 0, SUM = 1, MAX = 2 };
 
 // ROW_NUMBER() of WindowAggExec over an input that arrives sorted by (PARTITION BY, ORDER BY): out[i] = 1 + i - (first row of the RUN of equal
 // partition keys row i lies in); a run ends where any of the up to four key columns changes (NULL equals NULL; Float64 by its bits; Utf8 keys are
@@ -43,10 +42,6 @@ int row_number_runs(flockgpu_ctx *ctx, const char *name, const DevColumn *cols, 
 // keys of an integer column as int64 (I32 sign-extended; I64 / U64 bit pattern): out[rows]
 int widen_to_i64(flockgpu_ctx *ctx, const DevColumn &col, int64_t rows, int64_t *out);
 
-// ---- predicates: pred.hpp (one pass per FilterExec).  A byte mask (1 = keep) -> its rows, for the operators' own bookkeeping:
-// rows with mask != 0, in order.  *out_rows: ctx-owned (arena key `name`), n_out through ONE synchronisation.
-int mask_to_rows(flockgpu_ctx *ctx, const char *name, const uint8_t *mask, int64_t rows, int32_t **out_rows, int64_t *n_out);
-
 // ---- take (a column's validity bytes are taken along)
 int take_column(flockgpu_ctx *ctx, const char *name, const DevColumn &src, const int32_t *rows, int64_t n, DevColumn *out);
 int gather_u8(flockgpu_ctx *ctx, const uint8_t *src, const int32_t *rows, int64_t n, uint8_t *out);
@@ -55,17 +50,8 @@ int replace_invalid_i64(flockgpu_ctx *ctx, int64_t *keys, const uint8_t *valid, 
 // out[i] = keys[i] != sentinel (the validity of a group-key column that went through replace_invalid_i64); out[i] = count[i] != 0 (AVG over no valid value)
 int valid_from_i64(flockgpu_ctx *ctx, const int64_t *keys, int64_t n, int64_t sentinel, uint8_t *out);
 
-// ---- GROUP BY one integer key (as int64): distinct keys + SUM / MAX of `values` (null: SUM counts rows) per key.
-// Outputs are ctx-owned: keys[n_groups], agg[n_groups], first_row[n_groups] (smallest input row of the group).
-struct GroupResult {
-    int64_t n_groups = 0;
-    int64_t *keys = nullptr;
-    uint64_t *agg = nullptr;
-    int32_t *first_row = nullptr;
-};
-int group_by_key64(flockgpu_ctx *ctx, const char *name, const int64_t *keys, const uint64_t *values, AggKind kind, int64_t rows,
-                   GroupResult *out);
-// The same GROUP BY with up to kMaxGroupAggs accumulators per group, all in one table (one pass over the rows).
+// ---- GROUP BY one integer key (as int64) with up to kMaxGroupAggs accumulators per group, all in one table (one pass over the rows).
+// Outputs are ctx-owned, one entry per group (first_row: the smallest input row of the group).
 // MAX_F64 / MIN_F64 order doubles through their order-preserving bit pattern (no NaN among the inputs: Arrow's min / max kernels
 // skip NaN only against non-NaN values, a case the engine does not claim).
 // Accumulators are 64-bit: COUNT (rows), SUM_INT (two's complement add of an integer column: Int32 sign-extended), MAX / MIN

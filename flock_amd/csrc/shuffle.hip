@@ -29,11 +29,7 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {  // murmur3 finaliser
 }
 
 __device__ __forceinline__ uint32_t part_of(int32_t key, uint32_t n_parts) {
-#if defined(FLOCKGPU_EXPERIMENTAL) && defined(FLOCKGPU_AB_PART_NOHASH)   // (A/B builds only: what the three integer multiplies of the hash cost the count pass)
-    return (uint32_t)key & (n_parts - 1);
-#else
     return (uint32_t)(((uint64_t)mix32((uint32_t)key) * n_parts) >> 32);
-#endif
 }
 
 // Destination of each of the lane's 32 rows, one byte each (0xFF = row outside the window), four per word.
@@ -515,21 +511,7 @@ int flockgpu_partition_by_key(flockgpu_ctx *ctx, const int32_t *keys, int64_t ro
     const int32_t *d_rows = nullptr;
     const int64_t *d_off = nullptr, *h_off = nullptr;
     int64_t n_out = 0;
-    const PartPayload *pay_p = nullptr;
-#if defined(FLOCKGPU_EXPERIMENTAL)   // (A/B builds only, tools/gpu_partition_ab.py --payload k: k payload columns ride in the emit pass as in comm.hip's exchange -- the key column k times)
-    PartPayload pay;
-    if (const char *e = exp_env("FLOCKGPU_AB_PART_PAYLOAD")) {
-        for (int c = 0; c < atoi(e) && c < 4; ++c) {
-            void *p = nullptr;
-            FG_TRY(arena_get(ctx, ("partition.ab_payload" + std::to_string(c)).c_str(), (size_t)rows * 4 + 16, &p));
-            pay.src[pay.n] = keys;
-            pay.dst[pay.n++] = static_cast<int32_t *>(p);
-        }
-        pay.skip_rows = true;
-        pay_p = &pay;
-    }
-#endif
-    FG_TRY(partition_by_key_async(ctx, keys, rows, win, n_parts, &d_rows, &d_off, &h_off, &n_out, pay_p));
+    FG_TRY(partition_by_key_async(ctx, keys, rows, win, n_parts, &d_rows, &d_off, &h_off, &n_out, nullptr));
     FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const size_t n_groups = (size_t)n_parts * win->n_windows;
     std::vector<int64_t> &offs = ctx->host_i64["partition.group_offsets"];

@@ -554,9 +554,7 @@ __global__ __launch_bounds__(kBlock) void valprog_kernel(ValProgram p, int64_t n
 size_t stack_bytes(const ValProgram &prog);
 // groups per pass: four (two) while the operand stack below the top fits half the 64 KB a launch gets without asking
 int groups_of(const ValProgram &prog) {
-    static const int forced = exp_env("FLOCKGPU_VALPROG_GROUPS") ? atoi(exp_env("FLOCKGPU_VALPROG_GROUPS")) : 0;   // (A/B knob)
-    const int g = forced ? forced : kValGroups;
-    return prog.max_stack <= 2 ? g : prog.max_stack <= 3 && g > 2 ? 2 : 1;
+    return prog.max_stack <= 2 ? kValGroups : prog.max_stack <= 3 && kValGroups > 2 ? 2 : 1;
 }
 template <bool kMask>
 void launch(flockgpu_ctx *ctx, const ValProgram &prog, unsigned grid, int64_t rows, int32_t n_tiles, void *out_values, uint8_t *out_valid, int32_t out_type, uint32_t *flags,

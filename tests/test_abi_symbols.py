@@ -71,6 +71,26 @@ def test_shipped_library_reads_no_environment():
         assert not re.search(r"\bgetenv\b", dyn), "libflockgpu.so imports getenv"
 
 
+def test_only_diagnostics_are_left_behind_exp_env():
+    """The A/B variants of the kernel rounds are decided and gone (results: profiles/r02 .. r06): no source or tool names a
+    define of the A/B family, and what exp_env() still reads in an experimental build are diagnostics, not selections between kernels."""
+    kept = {"FLOCKGPU_GUARD_ARENA", "FLOCKGPU_GUARD_SLACK", "FLOCKGPU_GUARD_TRACE", "FLOCKGPU_PLAN_TIMES", "FLOCKGPU_RECORDED_EVENTS"}
+    ab_family = "FLOCKGPU_" + "AB_"   # (spelled in two halves: a search of the tree for the prefix finds nothing, this file included)
+    read = set()
+    for top in (os.path.join(ROOT, "flock_amd", "csrc"), os.path.join(ROOT, "tools")):
+        for dirpath, _, files in os.walk(top):
+            for f in files:
+                path = os.path.join(dirpath, f)
+                src = open(path, errors="ignore").read()
+                assert ab_family not in src, os.path.relpath(path, ROOT)
+                if top.endswith("csrc"):
+                    calls = re.findall(r"exp_env\(\s*([^)]*)\)", src)
+                    names = [re.fullmatch(r'"(\w+)"', c.strip()) for c in calls if c.strip() not in ("const char *name", "const char *")]
+                    assert all(names), (f, calls)   # every read names its variable literally
+                    read |= {m.group(1) for m in names}
+    assert read == kept, sorted(read ^ kept)
+
+
 def test_counts_closed_form_matches_oracle():
     # host-only entry point (no GPU needed): event-kind counts of a stream slice
     import oracle

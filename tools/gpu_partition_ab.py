@@ -1,6 +1,6 @@
 """gpurun helper: `flockgpu_partition_by_key` (RepartitionExec Hash([key], n), shuffle.hip) at 1 .. 64 destinations on ONE GPU -- the stage-0 side of the
 exchange as 2 / 4 / 8 ranks would run it.  NEXMark-shaped input: 8e7 (auction, count) pairs of 216 hopping windows' Partial groups stand in as
-8e7 keys over 216 windows; with --payload the two 4-byte columns of q5's exchange ride in the emit pass (what comm.hip asks for).
+8e7 keys over 216 windows.
 Prints per destination count: ms per call (host clock around 10 calls) and the LaunchScope averages of the count / emit kernels.
 
     python tools/gpu_partition_ab.py [--rows 80000000] [--windows 216] [--parts 1,2,4,8,16,64]
