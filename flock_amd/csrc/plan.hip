@@ -21,6 +21,7 @@
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
 #include "pred.hpp"
+#include "strmatch.hpp"
 #include "valprog.hpp"
 
 using namespace flockgpu;
@@ -690,6 +691,56 @@ const char *fused_name(Fused f) {
         default: return "generic (relops.hip)";
     }
 }
+// A filter's predicate as text -- printed for the predicates that hold a LIKE (the others' lines are what they were)
+bool holds_like(const Expr *e) {
+    if (!e) return false;
+    if (e->kind == EKind::Bin && (e->s == "Like" || e->s == "NotLike")) return true;
+    if (holds_like(e->l.get()) || holds_like(e->r.get())) return true;
+    for (auto &x : e->list)
+        if (holds_like(x.get())) return true;
+    return false;
+}
+void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstream &os) {
+    if (!e) { os << "?"; return; }
+    static const std::pair<const char *, const char *> ops[] = {{"Eq", "="}, {"NotEq", "<>"}, {"Lt", "<"}, {"LtEq", "<="}, {"Gt", ">"}, {"GtEq", ">="}, {"And", "AND"}, {"Or", "OR"},
+                                                                {"Like", "LIKE"}, {"NotLike", "NOT LIKE"}, {"Modulo", "%"}, {"Plus", "+"}, {"Minus", "-"}, {"Multiply", "*"}, {"Divide", "/"}};
+    switch (e->kind) {
+        case EKind::Col: os << schema[(size_t)e->col].name; return;
+        case EKind::LitI: if (e->big_unsigned) os << (uint64_t)e->i; else os << e->i; return;
+        case EKind::LitF: os << e->f; return;
+        case EKind::LitS: os << "'" << e->s << "'"; return;
+        case EKind::LitB: os << (e->i ? "TRUE" : "FALSE"); return;
+        case EKind::LitNull: os << "NULL"; return;
+        case EKind::Cast: pred_text(e->l.get(), schema, os); return;   // (the value, not its conversion)
+        case EKind::Neg: os << "-"; pred_text(e->l.get(), schema, os); return;
+        case EKind::Not: os << "NOT ("; pred_text(e->l.get(), schema, os); os << ")"; return;
+        case EKind::IsNull: pred_text(e->l.get(), schema, os); os << " IS NULL"; return;
+        case EKind::IsNotNull: pred_text(e->l.get(), schema, os); os << " IS NOT NULL"; return;
+        case EKind::InList:
+            pred_text(e->l.get(), schema, os);
+            os << (e->negated ? " NOT IN (" : " IN (");
+            for (size_t i = 0; i < e->list.size(); ++i) { os << (i ? ", " : ""); pred_text(e->list[i].get(), schema, os); }
+            os << ")";
+            return;
+        case EKind::Case: os << "CASE ..."; return;
+        case EKind::Bin: {
+            const char *sym = e->s.c_str();
+            for (auto &o : ops)
+                if (e->s == o.first) sym = o.second;
+            const bool junction = e->s == "And" || e->s == "Or";
+            auto side = [&](const Expr *x) {
+                const bool paren = junction && x && x->kind == EKind::Bin && (x->s == "And" || x->s == "Or") && x->s != e->s;
+                if (paren) os << "(";
+                pred_text(x, schema, os);
+                if (paren) os << ")";
+            };
+            side(e->l.get());
+            os << " " << sym << " ";
+            side(e->r.get());
+            return;
+        }
+    }
+}
 void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstream &os) {
     static const char *kinds[] = {"Scan", "Filter", "Project", "Aggregate", "Join", "Repartition", "Sort", "Limit", "Window"};
     os << std::string((size_t)depth * 2, ' ') << kinds[(int)n->kind];
@@ -697,6 +748,11 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
+    if (n->kind == NKind::Filter && holds_like(n->pred.get())) {
+        os << "(";
+        pred_text(n->pred.get(), n->schema, os);
+        os << ")";
+    }
     if (n->kind == NKind::Window)
         for (size_t w = 0; w < n->win.size(); ++w) {
             const WinExpr &x = n->win[w];
@@ -1312,7 +1368,8 @@ struct Exec {
         return false;
     }
     // FilterExec's predicate -> the postfix program of pred.hpp (ONE kernel evaluates it per flag tile).  Leaves: a column against a
-    // literal or another column (integers, Float64, Utf8 `=` / `<>`), `column % literal` against a literal, IS [NOT] NULL, a boolean
+    // literal or another column (integers, Float64, Utf8 `=` / `<>`), `column % literal` against a literal, IS [NOT] NULL;
+    // Utf8 LIKE / NOT LIKE / `<` `<=` `>` `>=` against a literal (a kernel of its own per leaf, strmatch.hpp: the program reads its words); a boolean
     // literal; IN lists become OR chains of `=` leaves; NOT / AND / OR combine in three-valued logic on the device.  AND / OR push
     // their deeper operand first (they commute), so the operand stack stays at log2(leaves) + 1.
     struct Operand {
@@ -1421,8 +1478,14 @@ struct Exec {
             return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a column (or its remainder) against a non-literal has no one-pass leaf");
         const ColType ct = l.col->c.type;
         if (r.k == Operand::STR) {
-            if (ct != ColType::UTF8 || l.k == Operand::MOD || (op != CmpOp::EQ && op != CmpOp::NE))
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a Utf8 literal compares with a Utf8 column by = or <>");
+            if (ct != ColType::UTF8 || l.k == Operand::MOD)
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a Utf8 literal compares with a Utf8 column only");
+            if (op != CmpOp::EQ && op != CmpOp::NE) {   // <, <=, >, >=: bytewise order, a kernel of its own (strmatch.hpp)
+                StrPattern sp;
+                std::string why;
+                if (!strmatch_compile_cmp(r.s, (int)op, &sp, &why)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: Utf8 comparison with %s", why.c_str());
+                return pred_words(l.col, sp, b);
+            }
             d.kind = (uint8_t)PredLeafKind::Utf8Eq;
             d.negate = op == CmpOp::NE;
             d.lit_len = (int32_t)r.s.size();
@@ -1498,6 +1561,36 @@ struct Exec {
         FG_TRY(pred_const(b, 2));
         return b.push(v ? PredOpKind::Or : PredOpKind::And) ? FLOCKGPU_OK : pred_full();
     }
+    // A leaf whose TRUE bits a kernel of its own writes (strmatch.hip): launched here, read by the program's Words leaf
+    const Node *words_node = nullptr;   // the filter being compiled (filter_rows)
+    int words_used = 0;
+    int pred_words(const TCol *col, const StrPattern &sp, PredBuilder &b) {
+        if (!words_node) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a string-match leaf outside a filter");
+        uint32_t *words = nullptr;
+        FG_TRY(strmatch_words(ctx, node_key(pl, words_node, "like", words_used++).c_str(), col->c, col_rows, sp, &words));
+        PredLeafDesc d{};
+        d.kind = (uint8_t)PredLeafKind::Words;
+        d.lit = (int64_t)reinterpret_cast<uintptr_t>(words);
+        const int ia = b.add_col(col->c);
+        if (ia < 0) return pred_full();
+        d.a = (uint8_t)ia;
+        return b.add_leaf(d) ? FLOCKGPU_OK : pred_full();
+    }
+    int64_t col_rows = 0;   // rows of the filter's input
+    int pred_like(const Expr *e, const Table &in, PredBuilder &b) {
+        const Expr *c = uncast_exact(e->l.get(), in), *p = uncast_exact(e->r.get(), in);
+        if (c->kind != EKind::Col || in.cols[(size_t)c->col].c.type != ColType::UTF8 || p->kind != EKind::LitS)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: LIKE takes a Utf8 column and a literal pattern");
+        const TCol &col = in.cols[(size_t)c->col];
+        if (col.c.all_null) return pred_const(b, 2);
+        if (!col.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: predicate column was not materialised");
+        StrPattern sp;
+        std::string why;
+        if (!strmatch_compile_like(p->s, &sp, &why)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: LIKE with %s", why.c_str());
+        FG_TRY(pred_words(&col, sp, b));
+        if (e->s == "NotLike" && !b.push(PredOpKind::Not)) return pred_full();
+        return FLOCKGPU_OK;
+    }
     int compile_pred(const Expr *e, const Table &in, PredBuilder &b) {
         switch (e->kind) {
             case EKind::LitB: return pred_const(b, e->i ? 1 : 0);
@@ -1537,6 +1630,7 @@ struct Exec {
                     FG_TRY(compile_pred(second, in, b));
                     return b.push(e->s == "And" ? PredOpKind::And : PredOpKind::Or) ? FLOCKGPU_OK : pred_full();
                 }
+                if (e->s == "Like" || e->s == "NotLike") return pred_like(e, in, b);
                 return pred_compare(e->s, e->l.get(), e->r.get(), in, b);
             }
             default:
@@ -1862,7 +1956,11 @@ struct Exec {
     int filter_rows(const Node *n, Table *in, int32_t **rows, int64_t *n_out) {
         FG_TRY(exec(n->in[0].get(), in));
         PredBuilder b;
+        words_node = n;
+        words_used = 0;
+        col_rows = in->rows;
         const int rc = compile_pred(n->pred.get(), *in, b);
+        words_node = nullptr;
         if (rc == FLOCKGPU_OK) return pred_to_rows(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, rows, n_out);
         if (rc != FLOCKGPU_ERR_UNSUPPORTED) return rc;
         // a predicate the one-pass program has no leaf for (arithmetic inside a comparison, CASE, casts of computed values): the general

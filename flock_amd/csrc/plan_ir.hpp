@@ -17,6 +17,7 @@
 
 #include "plan_json.hpp"
 #include "relops.hpp"
+#include "strmatch.hpp"
 
 namespace flockgpu {
 namespace ir {
@@ -36,7 +37,7 @@ struct Expr {
     int col = -1;  // Col: index into the input schema
     int64_t i = 0;   // LitI value / LitB 0 | 1
     double f = 0;
-    std::string s;   // LitS value / Bin operator (Rust enum ident: Eq, NotEq, Lt, LtEq, Gt, GtEq, And, Or, Modulo, Multiply)
+    std::string s;   // LitS value / Bin operator (Rust enum ident: Eq, NotEq, Lt, LtEq, Gt, GtEq, And, Or, Modulo, Multiply, Like, NotLike)
     ColType cast_to = ColType::I64;
     std::unique_ptr<Expr> l, r;  // Bin operands; the operand of Cast / Not / IsNull / IsNotNull / Neg / InList in l
     std::vector<std::unique_ptr<Expr>> list;   // InList: the literals; Case: WHEN, THEN, WHEN, THEN, ... (base expression in l, ELSE in r; either may be null)
@@ -323,6 +324,33 @@ struct Builder {
         return nullptr;
     }
 
+    // LIKE / NOT LIKE (strmatch.hpp): a Utf8 column (a cast to Utf8 may sit in front of it) against a literal pattern without a backslash, within the
+    // limits of the compiled pattern; `skeleton`: `e` is reached from a filter's predicate through AND / OR / NOT only -- where a leaf of the one-pass
+    // predicate program can stand.  Anywhere else (CASE, an operand of a comparison, a projected value) LIKE is refused.
+    bool check_like(const Expr *e, const std::vector<Field> &schema, bool skeleton) {
+        if (!e) return true;
+        const bool like = e->kind == EKind::Bin && (e->s == "Like" || e->s == "NotLike");
+        if (like) {
+            if (!skeleton) return fail("LIKE inside a computed expression (CASE, an operand, a projected value): it is taken as a filter predicate under AND / OR / NOT only");
+            const Expr *c = e->l.get(), *p = e->r.get();
+            while (c->kind == EKind::Cast && c->cast_to == ColType::UTF8) c = c->l.get();
+            while (p->kind == EKind::Cast && p->cast_to == ColType::UTF8) p = p->l.get();
+            if (c->kind != EKind::Col || schema[(size_t)c->col].type != ColType::UTF8) return fail("LIKE on something that is not a Utf8 column");
+            if (p->kind != EKind::LitS) return fail("LIKE with a pattern that is not a Utf8 literal");
+            if (p->s.find('\\') != std::string::npos) return fail("LIKE pattern with a backslash: there is no escape character");
+            int pct = 0;
+            for (char ch : p->s) pct += ch == '%';
+            if (p->s.size() - (size_t)pct > (size_t)kStrMaxPattern || pct > kStrMaxPieces - 1)
+                return fail("LIKE pattern beyond " + std::to_string(kStrMaxPattern) + " bytes / " + std::to_string(kStrMaxPieces - 1) + " '%'");
+            return true;
+        }
+        const bool through = skeleton && (e->kind == EKind::Not || (e->kind == EKind::Bin && (e->s == "And" || e->s == "Or")));
+        if (!check_like(e->l.get(), schema, through) || !check_like(e->r.get(), schema, through)) return false;
+        for (auto &x : e->list)
+            if (!check_like(x.get(), schema, false)) return false;
+        return true;
+    }
+
     // An EXPRESSION where an operator reads a column (GROUP BY a % 10, SUM(price * 2), ORDER BY a + b): `in` gets a projection on top (once:
     // `wrapped`) that carries every column through and the expression's value beside them (the general evaluator, valprog.hpp); returns the
     // new column's index in the wrapped schema, -1 when refused (`err` says why).
@@ -428,7 +456,7 @@ struct Builder {
             if (!in) return nullptr;
             n->schema = in->schema;
             n->pred = expr(j->get("predicate"), n->schema);
-            if (!n->pred) return nullptr;
+            if (!n->pred || !check_like(n->pred.get(), n->schema, true)) return nullptr;
             n->in.push_back(std::move(in));
         } else if (t == "projection_exec") {
             n->kind = NKind::Project;
@@ -448,6 +476,7 @@ struct Builder {
                 } else {   // computed: q1's `literal * column` kernel, or the general evaluator (valprog.hpp) -- a numeric result either way
                     const int ty = expr_static_type(e.get(), in->schema);
                     if (ty < 0 || ty > 3) { fail(ty == 5 ? "projection of a Boolean expression (no Boolean columns at this boundary)" : "projection expression without a numeric type"); return nullptr; }
+                    if (!check_like(e.get(), in->schema, false)) return nullptr;
                     f.type = (ColType)ty;
                     f.nullable = true;
                     f.is_ts = e->kind == EKind::Cast && e->cast_ts;   // CAST(x AS Timestamp(Millisecond))

@@ -269,8 +269,8 @@ __device__ __forceinline__ TN leaf_utf8_eq(const PredProgram &P, const PredLeafD
 // kWide: the program holds a leaf over 64-bit values (Int64 / UInt64 / Timestamp / Float64 columns, column-to-column comparisons, `%` by
 // more than 2^31).  Programs without one -- Int32 and Utf8 columns against literals, what NEXMark's filters are -- run the instance
 // that does not carry those paths' registers (78 against 190 VGPRs: occupancy is what a streaming pass lives on).
-template <bool kWide>
-__device__ __forceinline__ TN eval_leaf(const PredProgram &P, int which, int64_t wbase, int64_t n_rows, bool full, int sub) {
+template <bool kWide, bool kWords>
+__device__ __forceinline__ TN eval_leaf(const PredProgram &P, int which, int64_t wbase, int64_t n_rows, bool full, int sub, int32_t tile) {
     const PredLeafDesc &L = P.leaves[which];
     switch (L.kind) {   // (uniform)
         case (uint8_t)PredLeafKind::CmpIntLit: return leaf_cmp_int_lit<kWide>(P, L, wbase, n_rows, full, sub);
@@ -282,6 +282,13 @@ __device__ __forceinline__ TN eval_leaf(const PredProgram &P, int which, int64_t
             const uint32_t valid = valid_bits(P.cols[L.a].valid, wbase, n_rows, full, sub);
             return TN{L.negate ? valid : ~valid, 0u};
         }
+        case (uint8_t)PredLeafKind::Words:
+            if (kWords) {   // which rows are TRUE was written by the leaf's own kernel (strmatch.hip); NULL where the column is
+                const uint32_t valid = valid_bits(P.cols[L.a].valid, wbase, n_rows, full, sub);
+                const uint32_t w = reinterpret_cast<const uint32_t *>(L.lit)[(size_t)tile * kBlock + threadIdx.x];
+                return TN{w & valid, ~valid};
+            }
+            return TN{0u, 0u};
         default: return TN{L.lit == 1 ? ~0u : 0u, L.lit == 2 ? ~0u : 0u};
     }
 }
@@ -292,7 +299,8 @@ __device__ __forceinline__ TN eval_leaf(const PredProgram &P, int which, int64_t
 // lane -- and ORs / adds its share into the tile's flag words / wave counts (cleared by the host).  A leaf's eight iterations are eight
 // DEPENDENT rounds of loads (offsets, then bytes; a 64-bit software division at a time), which a streaming pass hides behind its other
 // workgroups and a relation of a few tiles does not: q3's two filters over 6e4 auctions and 2e4 persons took 21 us per launch.
-template <bool kFull, bool kWide, bool kSplit = false>
+// kWords: the program holds a Words leaf (pred.hpp) -- instances of their own, so that the others keep their registers.
+template <bool kFull, bool kWide, bool kSplit = false, bool kWords = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kFull ? (kWide ? 3 : 4) : 1))) void pred_flag_kernel(const PredProgram P, int64_t n_rows, SegTiles st, int32_t first_tile,
                                                            uint32_t *__restrict__ flag_words, uint32_t *__restrict__ counts) {
     const int sub = kSplit ? (int)blockIdx.y : -1;
@@ -311,7 +319,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kFull ? 
                 s_t[sp - 1][threadIdx.x] = top.t;
                 s_n[sp - 1][threadIdx.x] = top.n;
             }
-            top = eval_leaf<kWide>(P, P.arg[i], wbase, n_rows, full, sub);
+            top = eval_leaf<kWide, kWords>(P, P.arg[i], wbase, n_rows, full, sub, tile);
             ++sp;
         } else if (op == (uint8_t)PredOpKind::Not) {
             top.t = ~top.t & ~top.n;
@@ -376,30 +384,39 @@ int pred_to_rows(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, i
     FG_TRY(arena_get_t(ctx, (base + ".base").c_str(), (size_t)st.n_tiles + 1, &tile_base));
     FG_TRY(pinned_get_t(ctx, (base + ".off").c_str(), 2, &h_off));
     pinned_pending(reinterpret_cast<uint64_t *>(h_off), 2);   // (wait_pinned below)
-    bool wide = false;
+    bool wide = false, words = false;
     for (int i = 0; i < prog.n_leaves; ++i) {
         const PredLeafDesc &l = prog.leaves[i];
         const PredLeafKind k = (PredLeafKind)l.kind;
+        words = words || k == PredLeafKind::Words;
         wide = wide || k == PredLeafKind::CmpF64Lit || k == PredLeafKind::CmpIntCol || k == PredLeafKind::CmpF64Col ||
                (k == PredLeafKind::CmpIntLit && (l.mod_kind == 2 || prog.cols[l.a].type != (int32_t)ColType::I32));
     }
     // the tiles that lie inside the relation, then -- a launch of its own -- the ragged last one (one segment: there is at most one)
     const int32_t n_full = (int32_t)(rows / kFlagTile);
+    // (full, wide, split, words) -> the instance
+    auto launch = [&](bool full, bool split, dim3 grid, int32_t first) {
+#define FG_PRED_LAUNCH(F, W, S, X) hipLaunchKernelGGL((pred_flag_kernel<F, W, S, X>), grid, dim3(kBlock), 0, ctx->stream, prog, rows, st, first, flags, counts)
+        if (split) {
+            if (words) { if (wide) FG_PRED_LAUNCH(false, true, true, true); else FG_PRED_LAUNCH(false, false, true, true); }
+            else { if (wide) FG_PRED_LAUNCH(false, true, true, false); else FG_PRED_LAUNCH(false, false, true, false); }
+        } else if (full) {
+            if (words) { if (wide) FG_PRED_LAUNCH(true, true, false, true); else FG_PRED_LAUNCH(true, false, false, true); }
+            else { if (wide) FG_PRED_LAUNCH(true, true, false, false); else FG_PRED_LAUNCH(true, false, false, false); }
+        } else {
+            if (words) { if (wide) FG_PRED_LAUNCH(false, true, false, true); else FG_PRED_LAUNCH(false, false, false, true); }
+            else { if (wide) FG_PRED_LAUNCH(false, true, false, false); else FG_PRED_LAUNCH(false, false, false, false); }
+        }
+#undef FG_PRED_LAUNCH
+    };
     if (st.n_tiles < 4 * ctx->num_cus) {   // a few tiles only: every tile's eight iterations on workgroups of their own (kSplit)
         FG_TRY(fill_words(ctx, FillList().add(flags, 0u, (uint64_t)st.n_tiles * kBlock).add(counts, 0u, (uint64_t)st.n_tiles * kWavesPerBlock)));
         LaunchScope ls(ctx, "pred_flag_kernel");
-        if (wide) hipLaunchKernelGGL((pred_flag_kernel<false, true, true>), dim3((unsigned)st.n_tiles, kFlagIters), dim3(kBlock), 0, ctx->stream, prog, rows, st, 0, flags, counts);
-        else hipLaunchKernelGGL((pred_flag_kernel<false, false, true>), dim3((unsigned)st.n_tiles, kFlagIters), dim3(kBlock), 0, ctx->stream, prog, rows, st, 0, flags, counts);
+        launch(false, true, dim3((unsigned)st.n_tiles, kFlagIters), 0);
     } else {
         LaunchScope ls(ctx, "pred_flag_kernel");
-        if (n_full > 0) {
-            if (wide) hipLaunchKernelGGL((pred_flag_kernel<true, true>), dim3((unsigned)n_full), dim3(kBlock), 0, ctx->stream, prog, rows, st, 0, flags, counts);
-            else hipLaunchKernelGGL((pred_flag_kernel<true, false>), dim3((unsigned)n_full), dim3(kBlock), 0, ctx->stream, prog, rows, st, 0, flags, counts);
-        }
-        if (st.n_tiles > n_full) {
-            if (wide) hipLaunchKernelGGL((pred_flag_kernel<false, true>), dim3((unsigned)(st.n_tiles - n_full)), dim3(kBlock), 0, ctx->stream, prog, rows, st, n_full, flags, counts);
-            else hipLaunchKernelGGL((pred_flag_kernel<false, false>), dim3((unsigned)(st.n_tiles - n_full)), dim3(kBlock), 0, ctx->stream, prog, rows, st, n_full, flags, counts);
-        }
+        if (n_full > 0) launch(true, false, dim3((unsigned)n_full), 0);
+        if (st.n_tiles > n_full) launch(false, false, dim3((unsigned)(st.n_tiles - n_full)), n_full);
     }
     FG_TRY(check_launch(ctx, "pred_flag_kernel"));
     if (st.n_tiles <= 2048) {   // a relation of up to 1.7e7 rows: the emit sums the lower tiles' counts itself (one launch less; 16 B per lower tile from L2)

@@ -1,5 +1,5 @@
 // FilterExec predicates as ONE pass (pred.hip): the expression tree of a `filter_exec` node -- comparisons of columns with
-// literals or columns, `%`, Utf8 `=` / `<>` / IN, IS [NOT] NULL, NOT, AND / OR -- is flattened at execute into a small postfix
+// literals or columns, `%`, Utf8 `=` / `<>` / IN, LIKE and ordered Utf8 comparisons (through Words leaves), IS [NOT] NULL, NOT, AND / OR -- is flattened at execute into a small postfix
 // program whose leaves each read their column(s) once, in the flag-tile geometry of scan.hpp, and whose result is the tile's
 // flag words + wave counts directly: no byte mask per expression node, no int64 copy of a column, no mask -> flag pass
 // (round 4 ran one kernel per node, each writing a byte per row to HBM; VERDICT r4 "generic operators").
@@ -21,7 +21,7 @@ constexpr int kPredMaxCols = 8;
 constexpr int kPredLitPool = 256;
 constexpr int kPredMaxStack = 8;
 
-enum class PredLeafKind : uint8_t { CmpIntLit = 0, CmpF64Lit = 1, CmpIntCol = 2, CmpF64Col = 3, Utf8Eq = 4, IsNull = 5, Const = 6 };
+enum class PredLeafKind : uint8_t { CmpIntLit = 0, CmpF64Lit = 1, CmpIntCol = 2, CmpF64Col = 3, Utf8Eq = 4, IsNull = 5, Const = 6, Words = 7 };
 enum class PredOpKind : uint8_t { Leaf = 0, And = 1, Or = 2, Not = 3 };
 
 struct PredCol {
@@ -39,7 +39,7 @@ struct PredLeafDesc {
     uint8_t uns;               // compare as unsigned 64-bit (UInt64 columns)
     uint8_t pad;
     int32_t lit_off, lit_len;  // Utf8Eq: the literal's bytes in the pool
-    int64_t lit;               // CmpIntLit: the literal; CmpF64Lit: its bits; Const: 0 FALSE, 1 TRUE, 2 NULL
+    int64_t lit;               // CmpIntLit: the literal; CmpF64Lit: its bits; Const: 0 FALSE, 1 TRUE, 2 NULL; Words: the device address of the leaf's flag-tile words
     int64_t modulus;           // |m|
     UMod32 mod;
 };
@@ -53,6 +53,10 @@ struct PredProgram {
     int32_t pool_used = 0, pad = 0;
 };
 
+// A Words leaf (LIKE, ordered Utf8 comparisons: strmatch.hpp) evaluates nothing: a kernel of its own wrote which rows are TRUE, one 32-bit word per lane and
+// tile in the flag-tile layout; the leaf loads that word and takes the NULL bits from column `a`'s validity bytes.  Programs that hold one run instances of
+// their own (pred.hip kWords), so the others' registers are what they were.
+//
 // Host-side assembly (plan.hip walks the expression tree).  Every add_* returns false when the program is full.
 struct PredBuilder {
     PredProgram p{};
