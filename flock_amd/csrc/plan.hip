@@ -324,7 +324,7 @@ bool match_winning_bids(const Node *agg, bool with_category, WinningBids *w) {
     Peeled pf = peel(la.below);
     if (pf.n->kind != NKind::Filter) return false;
     Peeled pj = peel(pf.n->in[0].get());
-    if (pj.n->kind != NKind::Join || pj.n->on_l2 >= 0) return false;
+    if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on_l2 >= 0) return false;
     const Node *J = pj.n;
     const int nl = (int)J->in[0]->schema.size();
     auto to_join = [&](int below_col) {  // column of la.below -> column of the join's output
@@ -433,7 +433,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         // (ysb.sql; planner.rs:298-346)
         if (top.fns[0] == "count" && top.below->schema[(size_t)top.group[0]].type == ColType::UTF8) {
             Peeled pj = peel(top.below);
-            if (pj.n->kind != NKind::Join || pj.n->on_l2 >= 0) return;
+            if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on_l2 >= 0) return;
             const Node *J = pj.n;
             const int nl = (int)J->in[0]->schema.size();
             Peeled pl_ = peel(J->in[0].get());
@@ -459,7 +459,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         }
         return;
     }
-    if (n->kind != NKind::Join) return;
+    if (n->kind != NKind::Join || n->join_type != JoinType::Inner) return;   // (a Semi / Anti look-alike of q3 / q8 / q9 runs on the generic operators)
     const Node *L = n->in[0].get(), *R = n->in[1].get();
     const size_t nl = L->schema.size();
     const Field &lk = L->schema[(size_t)n->on_l], &rk = R->schema[(size_t)n->on_r];
@@ -741,9 +741,14 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
         }
     }
 }
-void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstream &os) {
+// keys_only: `n` lies under the right input of a Semi / Anti join, which reads that side for its key columns alone -- a scan there says which of its
+// columns the plan uploads
+void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstream &os, bool keys_only = false) {
     static const char *kinds[] = {"Scan", "Filter", "Project", "Aggregate", "Join", "Repartition", "Sort", "Limit", "Window"};
-    os << std::string((size_t)depth * 2, ' ') << kinds[(int)n->kind];
+    const char *kind = kinds[(int)n->kind];
+    if (n->kind == NKind::Join && n->join_type == JoinType::Semi) kind = "SemiJoin";
+    if (n->kind == NKind::Join && n->join_type == JoinType::Anti) kind = "AntiJoin";
+    os << std::string((size_t)depth * 2, ' ') << kind;
     if (n->kind == NKind::Aggregate) os << "(" << n->mode << ")";
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
@@ -779,11 +784,20 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     os << " [";
     for (size_t i = 0; i < n->schema.size(); ++i) os << (i ? ", " : "") << n->schema[i].name << ":" << type_name(n->schema[i]);
     os << "]";
+    if (keys_only && n->kind == NKind::Scan) {
+        const Leaf &lf = pl->ir.leaves[(size_t)n->leaf];
+        os << "  reads [";
+        bool first = true;
+        for (size_t i = 0; i < lf.needed.size(); ++i)
+            if (lf.needed[i]) { os << (first ? "" : ", ") << lf.schema[i].name; first = false; }
+        os << "]";
+    }
     const Fused f = pl->fused[(size_t)n->id].kind;
     if (n->kind != NKind::Scan && n->kind != NKind::Project && n->kind != NKind::Repartition) os << "  <- " << fused_name(f);
     os << "\n";
     if (f != kNone) return;  // the fused pipeline swallows the sub-tree
-    for (auto &c : n->in) describe(pl, c.get(), depth + 1, os);
+    for (size_t i = 0; i < n->in.size(); ++i)
+        describe(pl, n->in[i].get(), depth + 1, os, keys_only || (i == 1 && n->kind == NKind::Join && n->join_type != JoinType::Inner));
 }
 
 // The whole plan is one NEXMark pipeline when, below pure projections, its root is a fused node (or q1's projection).
@@ -830,7 +844,8 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     *o += "|" + n->mode + "|";
     for (int c : n->group) *o += std::to_string(c) + ",";
     for (auto &a : n->aggs) *o += a.fn + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
-    *o += "|" + std::to_string(n->on_l) + "," + std::to_string(n->on_r) + "," + std::to_string(n->on_l2) + "," + std::to_string(n->on_r2) + (n->join_partitioned ? "p" : "") + "|";
+    *o += "|" + std::to_string(n->on_l) + "," + std::to_string(n->on_r) + "," + std::to_string(n->on_l2) + "," + std::to_string(n->on_r2) + (n->join_partitioned ? "p" : "") +
+          (n->join_type == JoinType::Semi ? "s" : n->join_type == JoinType::Anti ? "a" : "") + "|";
     for (size_t k = 0; k < n->on_lx.size(); ++k) *o += std::to_string(n->on_lx[k]) + "=" + std::to_string(n->on_rx[k]) + ",";   // (pairs after the second)
     for (int c : n->hash_cols) *o += std::to_string(c) + ",";
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
@@ -1985,6 +2000,8 @@ struct Exec {
     int exec_lazy(const Node *n, Lazy *z) {
         if (pl->fused[(size_t)n->id].kind == kNone) {
             if (n->kind == NKind::Repartition) return exec_lazy(n->in[0].get(), z);
+            // a Semi / Anti join is a choice of rows of its left input, like a filter: nothing is taken until the consumer's output
+            if (n->kind == NKind::Join && n->join_type != JoinType::Inner) return exec_semi_lazy(n, z);
             if (n->kind == NKind::Filter) {
                 int32_t *rows = nullptr;
                 int64_t n_out = 0;
@@ -2263,6 +2280,17 @@ struct Exec {
                 return FLOCKGPU_OK;
             }
             case NKind::Join: {
+                if (n->join_type != JoinType::Inner) {   // Semi / Anti: the kept left rows, then ONE take of the left columns somebody reads
+                    Lazy z;
+                    FG_TRY(exec_semi_lazy(n, &z));
+                    t->rows = z.rows;
+                    t->cols.assign(n->schema.size(), TCol{});
+                    if (!z.via) {   // (every row kept and no row list below: the left table itself)
+                        for (size_t i = 0; i < t->cols.size() && i < z.base.cols.size(); ++i) t->cols[i] = z.base.cols[i];
+                        return FLOCKGPU_OK;
+                    }
+                    return take_table(n, z.base, n->required, z.via, z.rows, 0, t);
+                }
                 Lazy ZL, ZR;
                 FG_TRY(exec_lazy(n->in[0].get(), &ZL));
                 FG_TRY(exec_lazy(n->in[1].get(), &ZR));
@@ -2375,13 +2403,106 @@ struct Exec {
         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: unknown node");
     }
 
+    // HashJoinExec join_type Semi / Anti (relops.hpp A-S1..6) as a LAZY table: the left input's base table and the list of its rows that have
+    // (Semi) / lack (Anti) a partner on the right.  The left side arrives lazily itself, its key columns are read through lazy_key, and the
+    // kept rows compose with its row list -- no right-side take, no pair rows, no `.dups` bookkeeping.  Key shapes: one integer pair goes to
+    // semi_rows (a bitmap when the right keys are dense, a hashed key set otherwise), two Int32 pairs as one packed 64-bit key to the same, one
+    // Utf8 pair through utf8_codes, anything else -- more pairs, mixed types, NULLs in a multi-column key or on a computed right side -- through
+    // key_codes; both already say "absent" per left row.  Empty and all-NULL sides are answered without a probe.
+    int exec_semi_lazy(const Node *n, Lazy *z) {
+        const bool anti = n->join_type == JoinType::Anti;
+        Lazy ZL, ZR;
+        FG_TRY(exec_lazy(n->in[0].get(), &ZL));
+        FG_TRY(exec_lazy(n->in[1].get(), &ZR));
+        std::vector<int> on_l{n->on_l}, on_r{n->on_r};
+        if (n->on_l2 >= 0) { on_l.push_back(n->on_l2); on_r.push_back(n->on_r2); }
+        on_l.insert(on_l.end(), n->on_lx.begin(), n->on_lx.end());
+        on_r.insert(on_r.end(), n->on_rx.begin(), n->on_rx.end());
+        const int np = (int)on_l.size();
+        if (np > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a join on more than %d key pairs", kMaxKeyCols);
+        const int64_t nl = ZL.rows, nr = ZR.rows;
+        TCol lk[kMaxKeyCols], rk[kMaxKeyCols];
+        bool l_null = false, r_null = false, l_valid = false, r_valid = false, all_i32 = true, any_text = false;
+        for (int p = 0; p < np; ++p) {
+            FG_TRY(lazy_key(n, ZL, on_l[(size_t)p], ("skl" + std::to_string(p)).c_str(), &lk[p]));
+            FG_TRY(lazy_key(n, ZR, on_r[(size_t)p], ("skr" + std::to_string(p)).c_str(), &rk[p]));
+            if (!keys_comparable(lk[p].c.type, rk[p].c.type))
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
+            if ((!lk[p].present && !lk[p].c.all_null) || (!rk[p].present && !rk[p].c.all_null)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
+            l_null = l_null || lk[p].c.all_null;
+            r_null = r_null || rk[p].c.all_null;
+            l_valid = l_valid || lk[p].c.valid;
+            r_valid = r_valid || rk[p].c.valid;
+            all_i32 = all_i32 && lk[p].c.type == ColType::I32 && rk[p].c.type == ColType::I32;
+            any_text = any_text || lk[p].c.type == ColType::UTF8;
+        }
+        z->base = ZL.base;
+        // (A-S4) nothing on the left, nothing that could match on the right, or nothing but NULL keys on the left: no probe
+        if (nl <= 0 || nr <= 0 || r_null || l_null) {
+            const bool keep_all = anti && nl > 0;
+            z->rows = keep_all ? nl : 0;
+            z->via = ZL.via;
+            if (!keep_all) {   // (a row list of its own, so that "no rows" is not read as "the table itself")
+                int32_t *none = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "semi0").c_str(), 4, &none));
+                z->via = none;
+            }
+            return FLOCKGPU_OK;
+        }
+        int32_t *rows = nullptr;
+        int64_t n_out = 0;
+        const std::string nm = node_key(pl, n, "semi");
+        if (np == 1 && !any_text && !r_valid) {
+            int64_t kmin = 0, kmax = 0;
+            bool dense = false;
+            // (a pair of sizes the one-workgroup kernel takes is ONE launch and one wait, whatever the statistics say; a leaf's statistics are cached)
+            if (!semi_is_tiny(nl, nr)) {
+                FG_TRY(int_col_stats(rk[0], nr, &kmin, &kmax));
+                dense = dense_range_ok(kmin, kmax, nr, rk[0].c.type == ColType::U64);
+            }
+            FG_TRY(semi_rows(ctx, nm.c_str(), lk[0].c, nl, rk[0].c, nr, dense, kmin, kmax, anti, &rows, &n_out));
+        } else if (np == 2 && all_i32 && !l_valid && !r_valid) {   // two Int32 pairs compare as one 64-bit key
+            int64_t *kl = nullptr, *kr = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &kl));
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kr").c_str(), (size_t)nr + 2, &kr));
+            FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(lk[0].c.values), static_cast<const int32_t *>(lk[1].c.values), nl, kl));
+            FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(rk[0].c.values), static_cast<const int32_t *>(rk[1].c.values), nr, kr));
+            DevColumn cl, cr;
+            cl.type = cr.type = ColType::I64;
+            cl.values = kl;
+            cr.values = kr;
+            FG_TRY(semi_rows(ctx, nm.c_str(), cl, nl, cr, nr, false, 0, 0, anti, &rows, &n_out));
+        } else if (np == 1 && any_text && !l_valid && !r_valid) {   // equal strings <-> a dictionary code of the right side (exact: full byte compare inside utf8_codes)
+            int64_t *codes = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &codes));
+            FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), rk[0].c, nr, nullptr, &lk[0].c, nl, codes));
+            FG_TRY(semi_rows_from_ids(ctx, nm.c_str(), codes, true, nl, anti, &rows, &n_out));
+        } else {
+            DevColumn kl[kMaxKeyCols], kr[kMaxKeyCols];
+            for (int p = 0; p < np; ++p) { kl[p] = lk[p].c; kr[p] = rk[p].c; }
+            int32_t *bg = nullptr, *pg = nullptr, *first = nullptr;
+            int64_t groups = 0;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcb").c_str(), (size_t)nr + 4, &bg));
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcp").c_str(), (size_t)nl + 4, &pg));
+            FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), kr, np, nr, bg, &groups, &first, kl, nl, pg));
+            FG_TRY(semi_rows_from_ids(ctx, nm.c_str(), pg, false, nl, anti, &rows, &n_out));
+        }
+        z->rows = n_out;
+        z->via = rows;
+        if (ZL.via && n_out > 0) {   // rows of the left input's own row list -> rows of its base table
+            int32_t *composed = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "semiv").c_str(), (size_t)n_out + 4, &composed));
+            FG_TRY(gather_i32(ctx, ZL.via, rows, n_out, composed));
+            z->via = composed;
+        }
+        return FLOCKGPU_OK;
+    }
+
     // A join on several key pairs of any integer / Utf8 types, NULLs allowed (a NULL in any key column matches nothing): the smaller side's
     // tuples get dense ids (relops.hpp key_codes), the other side looks its tuples up among them, and the dense join pairs the ids -- the way
     // the one-pair Utf8 join pairs dictionary codes.
     // a join key pair the composite ids can compare: two Utf8 columns, or two integer columns of one signedness
-    static bool keys_comparable(ColType x, ColType y) {
-        return x != ColType::F64 && y != ColType::F64 && (x == ColType::UTF8) == (y == ColType::UTF8) && (x == ColType::U64) == (y == ColType::U64);
-    }
+    static bool keys_comparable(ColType x, ColType y) { return join_keys_comparable(x, y); }   // (plan_ir.hpp: the rule Semi / Anti are refused by at create)
     // lk0 / rk0: pair 0's key columns, already taken by the caller
     int exec_join_composite(const Node *n, const Lazy &ZL, const Lazy &ZR, const TCol &lk0, const TCol &rk0, Table *t) {
         std::vector<int> on_l{n->on_l, n->on_l2}, on_r{n->on_r, n->on_r2};

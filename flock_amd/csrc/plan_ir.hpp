@@ -7,8 +7,9 @@
 // flock/src/runtime/context.rs:471,549; the splitter cuts stages at it, distributed_plan/stage.rs:337) and global_limit_exec /
 // local_limit_exec.  coalesce_batches_exec, repartition_exec RoundRobinBatch, merge_exec / coalesce_partitions_exec change
 // neither the row multiset nor the schema and are dropped.  window_agg_exec (Window) takes ROW_NUMBER() and
-// COUNT / SUM / MIN / MAX / AVG over the default frame.  Anything else (other window functions and frames, outer joins, unknown
-// expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
+// COUNT / SUM / MIN / MAX / AVG over the default frame.  hash_join_exec takes join_type Inner, Semi and Anti (Semi / Anti: the left input's rows
+// that have / lack a partner on the right, the left input's schema -- relops.hpp A-S1..6).  Anything else (other window functions and frames,
+// Left / Right / Full joins, unknown expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -112,6 +113,11 @@ struct WinExpr {
     std::vector<SortCol> order;    // aggregate: input columns of the ORDER BY (they delimit the peer groups; the input arrives sorted)
 };
 constexpr int kMaxWindowKeys = 4;   // PARTITION BY / ORDER BY columns of an aggregate window (each)
+enum class JoinType { Inner, Semi, Anti };
+// a join key pair that can compare: two Utf8 columns, or two integer columns of one signedness (Float64 keys are refused)
+inline bool join_keys_comparable(ColType x, ColType y) {
+    return x != ColType::F64 && y != ColType::F64 && (x == ColType::UTF8) == (y == ColType::UTF8) && (x == ColType::U64) == (y == ColType::U64);
+}
 struct Node {
     NKind kind = NKind::Scan;
     int id = 0;
@@ -127,6 +133,7 @@ struct Node {
     int on_l2 = -1, on_r2 = -1;     // Join: second key pair (q9: auction = id AND price = final), -1 when there is one
     std::vector<int> on_lx, on_rx;  // Join: the key pairs after the second (at most kMaxJoinPairs in all)
     bool join_partitioned = false;  // Join: mode=Partitioned (both inputs arrive hash-partitioned on the keys)
+    JoinType join_type = JoinType::Inner;   // Join: Semi / Anti return rows of the LEFT input only (schema = the left input's)
     std::vector<int> hash_cols;     // Repartition
     int n_parts = 0;
     bool hash_diff = false;         // Repartition: HashDiff -- one partition per DISTINCT key (n_parts = what the host counted)
@@ -572,7 +579,11 @@ struct Builder {
             n->in.push_back(std::move(in));
         } else if (t == "hash_join_exec") {
             n->kind = NKind::Join;
-            if (j->s("join_type") != "Inner") { fail("only Inner joins"); return nullptr; }
+            const std::string jt = j->s("join_type");
+            if (jt == "Semi") n->join_type = JoinType::Semi;
+            else if (jt == "Anti") n->join_type = JoinType::Anti;
+            else if (jt != "Inner") { fail("join_type '" + jt + "': only Inner, Semi and Anti joins"); return nullptr; }
+            const bool semi = n->join_type != JoinType::Inner;
             n->join_partitioned = j->s("mode") == "Partitioned";
             auto l = node(j->get("left"), depth + 1);
             if (!l) return nullptr;
@@ -607,7 +618,29 @@ struct Builder {
                 if (n->on_lx.back() < 0 || n->on_rx.back() < 0) { fail("join key not in the input schemas"); return nullptr; }
             }
             n->schema = l->schema;
-            n->schema.insert(n->schema.end(), r->schema.begin(), r->schema.end());
+            if (!semi) n->schema.insert(n->schema.end(), r->schema.begin(), r->schema.end());
+            if (semi) {
+                // Semi / Anti (relops.hpp A-S2): the left input's schema.  A serialised schema that says otherwise -- right columns carried along, other
+                // types -- is another operator's; key pairs that cannot compare are refused here, in the words the inner join's execute uses
+                const char *kind = n->join_type == JoinType::Semi ? "Semi" : "Anti";
+                const JValue *sc = j->get("schema");
+                const JValue *sf = sc ? sc->get("fields") : nullptr;
+                if (sf && sf->kind == JValue::Arr) {
+                    std::vector<Field> given;
+                    if (!fields_of(sc, &given)) return nullptr;
+                    bool same = given.size() == l->schema.size();
+                    for (size_t i = 0; same && i < given.size(); ++i) same = given[i].type == l->schema[i].type && given[i].is_ts == l->schema[i].is_ts;
+                    if (!same) {
+                        fail(std::string(kind) + " join: the node's schema (" + std::to_string(given.size()) + " columns) is not the left input's (" +
+                             std::to_string(l->schema.size()) + " columns): a " + kind + " join returns left columns only");
+                        return nullptr;
+                    }
+                }
+                bool ok = join_keys_comparable(l->schema[(size_t)n->on_l].type, r->schema[(size_t)n->on_r].type);
+                if (n->on_l2 >= 0) ok = ok && join_keys_comparable(l->schema[(size_t)n->on_l2].type, r->schema[(size_t)n->on_r2].type);
+                for (size_t k = 0; k < n->on_lx.size(); ++k) ok = ok && join_keys_comparable(l->schema[(size_t)n->on_lx[k]].type, r->schema[(size_t)n->on_rx[k]].type);
+                if (!ok) { fail(std::string(kind) + " join: join keys must be integer columns of one signedness, or two Utf8 columns"); return nullptr; }
+            }
             n->in.push_back(std::move(l));
             n->in.push_back(std::move(r));
         } else if (t == "sort_exec") {
@@ -846,7 +879,11 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
         }
         case NKind::Join: {
             const size_t nl = n->in[0]->schema.size();
-            std::vector<char> l(req.begin(), req.begin() + nl), r(req.begin() + nl, req.end());
+            // (Semi / Anti: the output IS the left side; the right child is read for its key columns alone -- a leaf under it uploads nothing else)
+            const bool semi = n->join_type != JoinType::Inner;
+            std::vector<char> l(req.begin(), req.begin() + nl), r;
+            if (semi) r.assign(n->in[1]->schema.size(), 0);
+            else r.assign(req.begin() + nl, req.end());
             need(l, n->on_l);
             need(r, n->on_r);
             need(l, n->on_l2);
@@ -945,6 +982,21 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
         }
         case NKind::Join: {
             const size_t nl = n->in[0]->schema.size();
+            if (n->join_type != JoinType::Inner) {
+                // Semi / Anti: `droppable` speaks of the left columns alone.  A NULL key never matches: the right rows it sits in can go, and so can
+                // Semi's left rows -- but an ANTI join KEEPS its NULL-keyed left rows (relops.hpp A-S4): their key columns arrive with validity bytes
+                // and the probe reads them
+                std::vector<char> l = droppable, r(n->in[1]->schema.size(), 0);
+                const bool semi = n->join_type == JoinType::Semi;
+                if (semi) l[(size_t)n->on_l] = 1;
+                r[(size_t)n->on_r] = 1;
+                if (n->on_l2 >= 0) { if (semi) l[(size_t)n->on_l2] = 1; r[(size_t)n->on_r2] = 1; }
+                for (int c : n->on_lx) if (semi) l[(size_t)c] = 1;
+                for (int c : n->on_rx) r[(size_t)c] = 1;
+                mark_null_droppable(p, n->in[0].get(), l);
+                mark_null_droppable(p, n->in[1].get(), r);
+                break;
+            }
             std::vector<char> l(droppable.begin(), droppable.begin() + nl), r(droppable.begin() + nl, droppable.end());
             l[(size_t)n->on_l] = 1;  // NULL keys never match in an inner join
             r[(size_t)n->on_r] = 1;

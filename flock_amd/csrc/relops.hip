@@ -1025,6 +1025,154 @@ __global__ __launch_bounds__(kBlock) void join_probe_dense_kernel(const void *__
         if (lane_id() == 0 && mine) atomicAdd(total64 + (blockIdx.x & (kJoinTotalSlots - 1)), mine);   // (one of 32 words: a wave per 64 rows on ONE word is ~4.5 ns each, 22 us per 3e5 rows)
     }
 }
+// ---- semi / anti join (semi_rows): "is this key on the other side" is ONE BIT per probe row, so the right side is a SET, not a multimap -- no
+// claiming row, no chain, no pair rows -- and the probe is a filter of the LEFT side in the flag-tile geometry with either polarity (kAnti keeps
+// the rows that found nothing).  NULL rule (A-S4, relops.hpp): a NULL left key is "no match" -- dropped by Semi, KEPT by Anti; rows past the
+// column are never kept.
+// the lane's four rows r0 .. r0 + 3: bit j = row r0 + j is inside the column AND its key is valid
+__device__ __forceinline__ uint32_t semi_valid4(const uint8_t *__restrict__ valid, int64_t r0, int64_t n) {
+    if (r0 >= n) return 0u;
+    const uint32_t inside = r0 + 4 <= n ? 15u : (1u << (uint32_t)(n - r0)) - 1u;
+    if (!valid) return inside;
+    uint32_t m = 0;
+    if (inside == 15u && (reinterpret_cast<uintptr_t>(valid + r0) & 3u) == 0) {
+        const uint32_t w = *reinterpret_cast<const uint32_t *>(valid + r0);
+        m = (uint32_t)((w & 0xffu) != 0) | (uint32_t)((w & 0xff00u) != 0) << 1 | (uint32_t)((w & 0xff0000u) != 0) << 2 | (uint32_t)((w & 0xff000000u) != 0) << 3;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (r0 + j < n && valid[r0 + j]) m |= 1u << j;
+    }
+    return m;
+}
+// Dense right keys: a BITMAP, one bit per key value of [kmin, kmin + range).  The build reads the word before it ORs into it and skips the atomic
+// when the bit is there already: a hot key (NEXMark's hot auction takes a large share of the bids) costs one atomic for its first row and a cached
+// read for every further one, instead of a returning atomic per row on one word.
+__global__ __launch_bounds__(kBlock) void semi_bitmap_build_kernel(const void *__restrict__ keys, int32_t type, int64_t n, int64_t kmin, uint32_t range, uint32_t *bits,
+                                                                   uint32_t *err) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const uint64_t d = (uint64_t)load_as_i64(keys, type, i) - (uint64_t)kmin;
+        if (d >= range) {   // (outside the statistics the bitmap was sized from: the call is void)
+            atomicOr(err, 1u);
+            continue;
+        }
+        uint32_t *w = bits + (d >> 5);
+        const uint32_t b = 1u << (uint32_t)(d & 31);
+        if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & b)) atomicOr(w, b);
+    }
+}
+// A left key outside [kmin, kmin + range) is "no match", not an error.
+template <bool kI32, bool kAnti>
+__global__ __launch_bounds__(kBlock) void semi_probe_bitmap_flag_kernel(const void *__restrict__ keys, const uint8_t *__restrict__ valid, int64_t n, SegTiles st, int64_t kmin,
+                                                                        uint32_t range, const uint32_t *__restrict__ bits, uint32_t *__restrict__ flag_words,
+                                                                        uint32_t *__restrict__ counts) {
+    const int32_t tile = (int32_t)blockIdx.x;
+    const TileRange tr = locate_tile(st, tile, kFlagTile);
+    const int64_t wbase = tr.tile_begin + flag_rel0();
+    uint32_t flags = 0;
+    int32_t a[kFlagIters][4];
+    if (kI32) load_flag_tile(static_cast<const int32_t *>(keys), n, tr, a);
+#pragma unroll
+    for (int it = 0; it < kFlagIters; ++it) {
+        const int64_t r0 = wbase + it * 256;
+        const uint32_t vm = semi_valid4(valid, r0, n);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = r0 + j;
+            const uint64_t d = kI32 ? (uint64_t)((int64_t)a[it][j] - kmin) : (r < n ? (uint64_t)static_cast<const int64_t *>(keys)[r] - (uint64_t)kmin : ~0ull);
+            const bool in = d < (uint64_t)range;
+            const bool hit = in && ((bits[in ? d >> 5 : 0] >> (uint32_t)(d & 31)) & 1u) && ((vm >> j) & 1u);
+            flags |= (uint32_t)(r < n && hit != kAnti) << (it * 4 + j);
+        }
+    }
+    store_flags_and_counts(flags, tile, flag_words, counts);
+}
+// Right keys no dense range covers: a hashed key SET of 8-byte slots holding the key alone (join_hashed's hash and capacity; kEmptyKey free, the key
+// INT64_MIN itself in the extra slot `cap`, where any other value means "present").  Right keys repeat freely (bids per auction), so the build looks
+// before it swaps: a key that is there already costs a read.
+__global__ __launch_bounds__(kBlock) void semi_set_build_kernel(const void *__restrict__ keys, int32_t type, int64_t n, int64_t *slots, uint64_t cap, uint32_t *err) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t key = load_as_i64(keys, type, i);
+        if (key == kEmptyKey) {
+            slots[cap] = 0;   // (every writer stores the same value)
+            continue;
+        }
+        uint64_t s = mix64((uint64_t)key) & (cap - 1);
+        bool placed = false;
+        for (uint64_t probe = 0; probe < cap && !placed; ++probe) {
+            int64_t cur = __hip_atomic_load(&slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == kEmptyKey && __hip_atomic_compare_exchange_strong(&slots[s], &cur, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) cur = key;
+            placed = cur == key;
+            s = (s + 1) & (cap - 1);
+        }
+        if (!placed) atomicOr(err, 1u);   // (cannot happen in a table at most half full)
+    }
+}
+__device__ __forceinline__ bool semi_set_find(const int64_t *__restrict__ slots, uint64_t cap, int64_t key, int64_t v, uint64_t s) {
+    // v = the slot at s, already loaded (a lane's four rows request their home slots together)
+    if (key == kEmptyKey) return v != kEmptyKey;
+    for (uint64_t probe = 0; probe < cap; ++probe) {
+        if (v == key) return true;
+        if (v == kEmptyKey) return false;
+        s = (s + 1) & (cap - 1);
+        v = slots[s];
+    }
+    return false;
+}
+template <bool kI32, bool kAnti>
+__global__ __launch_bounds__(kBlock) void semi_probe_set_flag_kernel(const void *__restrict__ keys, const uint8_t *__restrict__ valid, int64_t n, SegTiles st,
+                                                                     const int64_t *__restrict__ slots, uint64_t cap, uint32_t *__restrict__ flag_words,
+                                                                     uint32_t *__restrict__ counts) {
+    const int32_t tile = (int32_t)blockIdx.x;
+    const TileRange tr = locate_tile(st, tile, kFlagTile);
+    const int64_t wbase = tr.tile_begin + flag_rel0();
+    uint32_t flags = 0;
+    int32_t a[kFlagIters][4];
+    if (kI32) load_flag_tile(static_cast<const int32_t *>(keys), n, tr, a);
+#pragma unroll
+    for (int it = 0; it < kFlagIters; ++it) {
+        const int64_t r0 = wbase + it * 256;
+        const uint32_t vm = semi_valid4(valid, r0, n);
+        int64_t key[4], v[4];
+        uint64_t home[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = r0 + j;
+            key[j] = kI32 ? (int64_t)a[it][j] : (r < n ? static_cast<const int64_t *>(keys)[r] : 0);
+            home[j] = join_hash_home(cap, key[j]);
+            v[j] = slots[home[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool hit = ((vm >> j) & 1u) && semi_set_find(slots, cap, key[j], v[j], home[j]);
+            flags |= (uint32_t)(r0 + j < n && hit != kAnti) << (it * 4 + j);
+        }
+    }
+    store_flags_and_counts(flags, tile, flag_words, counts);
+}
+// Utf8 and composite keys: utf8_codes / key_codes have already answered "absent" per left row (a negative id); ids -> flag words + wave counts.
+template <bool k64, bool kAnti>
+__global__ __launch_bounds__(kBlock) void semi_ids_flag_kernel(const void *__restrict__ ids, int64_t n, SegTiles st, uint32_t *__restrict__ flag_words,
+                                                               uint32_t *__restrict__ counts) {
+    const int32_t tile = (int32_t)blockIdx.x;
+    const TileRange tr = locate_tile(st, tile, kFlagTile);
+    const int64_t wbase = tr.tile_begin + flag_rel0();
+    uint32_t flags = 0;
+    int32_t a[kFlagIters][4];
+    if (!k64) load_flag_tile(static_cast<const int32_t *>(ids), n, tr, a);
+#pragma unroll
+    for (int it = 0; it < kFlagIters; ++it) {
+        const int64_t r0 = wbase + it * 256;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t r = r0 + j;
+            const int64_t id = k64 ? (r < n ? static_cast<const int64_t *>(ids)[r] : -1) : (int64_t)a[it][j];
+            const bool hit = id >= 0;
+            flags |= (uint32_t)(r < n && hit != kAnti) << (it * 4 + j);
+        }
+    }
+    store_flags_and_counts(flags, tile, flag_words, counts);
+}
 // ---- join, both sides small (join_tiny): ONE workgroup builds the smaller side's multimap in LDS -- keys, chain heads and the chain links
 // themselves -- and walks the other side through it in chunks of its own size: matches counted, scanned across the workgroup and written
 // at their final places in the same pass.  One launch and one host wait for a join of a stage plan's few thousand filtered rows (the
@@ -1124,6 +1272,82 @@ uint64_t pow2_at_least(uint64_t v) {
     uint64_t c = 1024;
     while (c < v) c <<= 1;
     return c;
+}
+
+// ---- semi / anti join, both sides small (semi_is_tiny): ONE workgroup -- the right keys as a set in LDS (join_tiny_kernel's table without heads and
+// links), the left rows walked in chunks of the workgroup's size, kept rows counted, scanned across the workgroup and written at their final places
+// in the same pass.  One launch and one host wait where the ordinary path is a fill, a build, a probe, an emit and a wait: a stage plan's few thousand
+// rows per partition.  Keys are read in their columns' own types; a NULL left key is "no match".  (64 KB + 72 B of static LDS: two such workgroups
+// per CU at most -- of no account for a grid of one, as for join_tiny_kernel's 114 KB.)
+__global__ __launch_bounds__(kTinyThreads) void semi_tiny_kernel(const void *__restrict__ rkeys, int32_t rtype, int32_t n_right, const void *__restrict__ lkeys, int32_t ltype,
+                                                                 const uint8_t *__restrict__ lvalid, int32_t n_left, int32_t anti, int32_t *__restrict__ out_rows,
+                                                                 unsigned long long *__restrict__ total) {
+    __shared__ int64_t s_key[kTinySlots];
+    __shared__ int32_t s_has_min;   // the key that doubles as the empty mark is on the right side
+    __shared__ uint32_t s_wave[kTinyThreads / 64];
+    for (int i = threadIdx.x; i < kTinySlots; i += kTinyThreads) s_key[i] = kEmptyKey;
+    if (threadIdx.x == 0) s_has_min = 0;
+    __syncthreads();
+    for (int32_t i = threadIdx.x; i < n_right; i += kTinyThreads) {
+        const int64_t key = load_as_i64(rkeys, rtype, i);
+        if (key == kEmptyKey) {
+            s_has_min = 1;
+            continue;
+        }
+        uint32_t s = (uint32_t)mix64((uint64_t)key) & (kTinySlots - 1);
+        for (;;) {   // at most half the slots are ever taken: an empty one is always reached
+            int64_t cur = __hip_atomic_load(&s_key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (cur == kEmptyKey) {
+                int64_t expected = kEmptyKey;
+                if (__hip_atomic_compare_exchange_strong(&s_key[s], &expected, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                cur = expected;
+            }
+            if (cur == key) break;
+            s = (s + 1) & (kTinySlots - 1);
+        }
+    }
+    __syncthreads();
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    uint32_t running = 0;   // kept rows of the chunks before this one (the same in every thread)
+    for (int32_t base = 0; base < n_left; base += kTinyThreads) {
+        const int32_t i = base + (int32_t)threadIdx.x;
+        bool keep = false;
+        if (i < n_left) {
+            bool hit = false;
+            if (!lvalid || lvalid[i]) {
+                const int64_t key = load_as_i64(lkeys, ltype, i);
+                if (key == kEmptyKey) {
+                    hit = s_has_min != 0;
+                } else {
+                    uint32_t s = (uint32_t)mix64((uint64_t)key) & (kTinySlots - 1);
+                    for (;;) {
+                        const int64_t cur = s_key[s];
+                        if (cur == key) {
+                            hit = true;
+                            break;
+                        }
+                        if (cur == kEmptyKey) break;
+                        s = (s + 1) & (kTinySlots - 1);
+                    }
+                }
+            }
+            keep = hit != (anti != 0);
+        }
+        const uint32_t c = keep ? 1u : 0u;
+        const uint32_t incl = wave_incl_scan_u32(c);
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, chunk = 0;
+#pragma unroll
+        for (int w = 0; w < kTinyThreads / 64; ++w) {
+            before += w < wave ? s_wave[w] : 0u;
+            chunk += s_wave[w];
+        }
+        if (keep) out_rows[running + before + (incl - c)] = i;   // (at most n_left rows: the buffer holds them all)
+        running += chunk;
+        __syncthreads();   // (s_wave is rewritten by the next chunk)
+    }
+    if (threadIdx.x == 0) *total = running;
 }
 
 #define RELOPS_LAUNCH(ctx, name, kernel, n, ...)                                                                      \
@@ -2026,6 +2250,8 @@ int reduce_max(flockgpu_ctx *ctx, const DevColumn &col, int64_t rows, int64_t *o
     return FLOCKGPU_OK;
 }
 
+bool semi_is_tiny(int64_t n_left, int64_t n_right) { return n_left > 0 && n_right > 0 && n_right <= kTinyBuild && n_left <= kTinyProbe; }
+
 bool join_is_tiny(int64_t n_left, int64_t n_right) {
     return n_left > 0 && n_right > 0 && std::min(n_left, n_right) <= kTinyBuild && std::max(n_left, n_right) <= kTinyProbe;
 }
@@ -2279,6 +2505,137 @@ int join_dense(flockgpu_ctx *ctx, const char *name, const DevColumn &left, int64
     *right_rows = orr;
     *n_pairs = total;
     return FLOCKGPU_OK;
+}
+
+// ---- semi / anti join: the flag-tile buffers of a probe over `n_left` rows, and the scan -> emit -> wait behind it
+namespace {
+struct SemiTiles {
+    SegTiles st;
+    uint32_t *flags = nullptr, *wcounts = nullptr;
+    uint64_t *tile_base = nullptr;
+    int64_t *h_off = nullptr;
+    int32_t *out = nullptr;
+};
+int semi_tiles_get(flockgpu_ctx *ctx, const std::string &base, int64_t n_left, SemiTiles *t) {
+    int64_t sb = 0, se = n_left;
+    FG_TRY(build_seg_tiles(ctx, (base + ".ptiles").c_str(), &sb, &se, 1, kFlagTile, &t->st));
+    FG_TRY(arena_get_t(ctx, (base + ".pflags").c_str(), (size_t)t->st.n_tiles * kBlock + 4, &t->flags));
+    FG_TRY(arena_get_t(ctx, (base + ".pcounts").c_str(), (size_t)t->st.n_tiles * kWavesPerBlock + 4, &t->wcounts));
+    FG_TRY(arena_get_t(ctx, (base + ".pbase").c_str(), (size_t)t->st.n_tiles + 1, &t->tile_base));
+    FG_TRY(pinned_get_t(ctx, (base + ".poff").c_str(), 2, &t->h_off));
+    FG_TRY(arena_get_t(ctx, (base + ".rows").c_str(), (size_t)n_left + 4, &t->out));
+    pinned_pending(reinterpret_cast<uint64_t *>(t->h_off), 2);
+    return FLOCKGPU_OK;
+}
+// h_err / d_err (may be null): the build's error word, published behind the probe and read with the row count -- one wait for both
+int semi_tiles_emit(flockgpu_ctx *ctx, const SemiTiles &t, uint32_t *h_err, const uint32_t *d_err, int64_t *n_out) {
+    if (h_err) {
+        pinned_pending32(h_err, 1);
+        FG_TRY(publish_words(ctx, PublishList().add(h_err, d_err, 1)));
+    }
+    if (t.st.n_tiles <= 2048) {
+        FG_TRY(emit_flagged_rows_self(ctx, t.st, t.flags, t.wcounts, t.out, t.h_off));
+    } else {
+        FG_TRY(launch_tile_scan(ctx, t.wcounts, t.st.n_tiles, t.tile_base, t.st.tile_first, t.st.n_seg, t.h_off));
+        FG_TRY(emit_flagged_rows(ctx, t.st, t.flags, t.wcounts, t.tile_base, t.out));
+    }
+    FG_TRY(wait_pinned(ctx, reinterpret_cast<const uint64_t *>(t.h_off), 2));
+    if (h_err) {
+        FG_TRY(wait_pinned32(ctx, h_err, 1));
+    }
+    *n_out = t.h_off[1];
+    return FLOCKGPU_OK;
+}
+#define SEMI_PROBE_LAUNCH(ctx, label, kernel, i32, anti, tiles, ...)                                                                             \
+    do {                                                                                                                                         \
+        {                                                                                                                                        \
+            LaunchScope ls_((ctx), label);                                                                                                       \
+            const dim3 g_((unsigned)(tiles)), b_(kBlock);                                                                                        \
+            if (i32 && anti) hipLaunchKernelGGL((kernel<true, true>), g_, b_, 0, (ctx)->stream, __VA_ARGS__);                                     \
+            else if (i32) hipLaunchKernelGGL((kernel<true, false>), g_, b_, 0, (ctx)->stream, __VA_ARGS__);                                       \
+            else if (anti) hipLaunchKernelGGL((kernel<false, true>), g_, b_, 0, (ctx)->stream, __VA_ARGS__);                                      \
+            else hipLaunchKernelGGL((kernel<false, false>), g_, b_, 0, (ctx)->stream, __VA_ARGS__);                                               \
+        }                                                                                                                                        \
+        FG_TRY(check_launch((ctx), label));                                                                                                      \
+    } while (0)
+}  // namespace
+
+int semi_rows(flockgpu_ctx *ctx, const char *name, const DevColumn &left, int64_t n_left, const DevColumn &right, int64_t n_right, bool dense, int64_t kmin,
+              int64_t kmax, bool anti, int32_t **rows, int64_t *n_out) {
+    const std::string base = name;
+    *rows = nullptr;
+    *n_out = 0;
+    auto is_int = [](const DevColumn &c) { return c.type == ColType::I32 || c.type == ColType::I64 || c.type == ColType::U64; };
+    if (!is_int(left) || !is_int(right) || right.valid || ((left.type == ColType::U64) != (right.type == ColType::U64)))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: semi join keys must be integer columns of one signedness, the right one without NULLs", name);
+    if (n_left >= (int64_t(1) << 31) || n_right >= (int64_t(1) << 30)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: relation too large for the generic join", name);
+    n_left = std::max<int64_t>(n_left, 0);
+    n_right = std::max<int64_t>(n_right, 0);
+    if (n_right == 0) dense = false;   // (an empty set: the hashed table of two free slots)
+    if (semi_is_tiny(n_left, n_right)) {   // both sides small: the whole operator is one workgroup's work (semi_tiny_kernel)
+        int32_t *out = nullptr;
+        unsigned long long *h_tot = nullptr;   // (pinned: the kernel's one thread stores the count where the host reads it)
+        FG_TRY(arena_get_t(ctx, (base + ".rows").c_str(), (size_t)n_left + 4, &out));
+        FG_TRY(pinned_get_t(ctx, (base + ".tot64").c_str(), 2, &h_tot));
+        pinned_pending(reinterpret_cast<uint64_t *>(h_tot), 1);
+        {
+            LaunchScope ls(ctx, "semi_tiny_kernel");
+            hipLaunchKernelGGL(semi_tiny_kernel, dim3(1), dim3(kTinyThreads), 0, ctx->stream, right.values, (int32_t)right.type, (int32_t)n_right, left.values, (int32_t)left.type,
+                               left.valid, (int32_t)n_left, anti ? 1 : 0, out, h_tot);
+        }
+        FG_TRY(check_launch(ctx, "semi_tiny_kernel"));
+        FG_TRY(wait_pinned(ctx, reinterpret_cast<const uint64_t *>(h_tot), 1));
+        *rows = out;
+        *n_out = (int64_t)h_tot[0];
+        return FLOCKGPU_OK;
+    }
+    if (dense && !dense_range_ok(kmin, kmax, n_right, right.type == ColType::U64)) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: not a dense integer join key", name);
+    SemiTiles t;
+    FG_TRY(semi_tiles_get(ctx, base, n_left, &t));
+    *rows = t.out;
+    if (n_left == 0) return FLOCKGPU_OK;
+    uint32_t *d_err = nullptr, *h_err = nullptr;
+    FG_TRY(arena_get_t(ctx, (base + ".scalars").c_str(), 4, &d_err));
+    FG_TRY(pinned_get_t(ctx, (base + ".scalars").c_str(), 4, &h_err));
+    const bool i32 = left.type == ColType::I32;
+    if (dense) {
+        const uint32_t range = (uint32_t)((uint64_t)kmax - (uint64_t)kmin + 1);
+        const uint64_t words = ((uint64_t)range + 31) / 32;
+        uint32_t *bits = nullptr;
+        FG_TRY(arena_get_t(ctx, (base + ".bits").c_str(), (size_t)words + 4, &bits));
+        FG_TRY(fill_words(ctx, FillList().add(d_err, 0u, 1).add(bits, 0u, words)));
+        RELOPS_LAUNCH(ctx, "semi_bitmap_build_kernel", semi_bitmap_build_kernel, n_right, right.values, (int32_t)right.type, n_right, kmin, range, bits, d_err);
+        SEMI_PROBE_LAUNCH(ctx, "semi_probe_bitmap_flag_kernel", semi_probe_bitmap_flag_kernel, i32, anti, t.st.n_tiles, left.values, left.valid, n_left, t.st, kmin, range,
+                          (const uint32_t *)bits, t.flags, t.wcounts);
+        FG_TRY(semi_tiles_emit(ctx, t, h_err, d_err, n_out));
+        if (h_err[0]) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: a right key outside the column statistics [%lld, %lld] the bitmap was sized from", name, (long long)kmin, (long long)kmax);
+        return FLOCKGPU_OK;
+    }
+    const uint64_t cap = pow2_at_least((uint64_t)std::max<int64_t>(n_right, 1) * 2);
+    int64_t *slots = nullptr;
+    FG_TRY(arena_get_t(ctx, (base + ".set").c_str(), (size_t)cap + 2, &slots));
+    FG_TRY(fill_words(ctx, FillList().add(d_err, 0u, 1)));
+    RELOPS_LAUNCH(ctx, "fill_u64_kernel", fill_u64_kernel, (int64_t)cap + 1, reinterpret_cast<uint64_t *>(slots), (int64_t)cap + 1, (uint64_t)kEmptyKey);
+    if (n_right > 0) RELOPS_LAUNCH(ctx, "semi_set_build_kernel", semi_set_build_kernel, n_right, right.values, (int32_t)right.type, n_right, slots, cap, d_err);
+    SEMI_PROBE_LAUNCH(ctx, "semi_probe_set_flag_kernel", semi_probe_set_flag_kernel, i32, anti, t.st.n_tiles, left.values, left.valid, n_left, t.st, (const int64_t *)slots, cap,
+                      t.flags, t.wcounts);
+    FG_TRY(semi_tiles_emit(ctx, t, h_err, d_err, n_out));
+    if (h_err[0]) return fail(ctx, FLOCKGPU_ERR_CAPACITY, "%s: key set overflow", name);
+    return FLOCKGPU_OK;
+}
+
+int semi_rows_from_ids(flockgpu_ctx *ctx, const char *name, const void *ids, bool ids64, int64_t n_left, bool anti, int32_t **rows, int64_t *n_out) {
+    const std::string base = name;
+    *rows = nullptr;
+    *n_out = 0;
+    if (n_left >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: relation too large for the generic join", name);
+    n_left = std::max<int64_t>(n_left, 0);
+    SemiTiles t;
+    FG_TRY(semi_tiles_get(ctx, base, n_left, &t));
+    *rows = t.out;
+    if (n_left == 0) return FLOCKGPU_OK;
+    SEMI_PROBE_LAUNCH(ctx, "semi_ids_flag_kernel", semi_ids_flag_kernel, ids64, anti, t.st.n_tiles, ids, n_left, t.st, t.flags, t.wcounts);
+    return semi_tiles_emit(ctx, t, nullptr, nullptr, n_out);
 }
 
 int key_run_starts(flockgpu_ctx *ctx, const char *name, const int64_t *keys, const int32_t *order, int64_t rows, int32_t **starts, int64_t *n_keys) {

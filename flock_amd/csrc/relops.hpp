@@ -159,6 +159,28 @@ bool join_is_tiny(int64_t n_left, int64_t n_right);
 int join_dense(flockgpu_ctx *ctx, const char *name, const DevColumn &left, int64_t n_left, int64_t kmin, int64_t kmax, const DevColumn &right, int64_t n_right,
                int32_t **left_rows, int32_t **right_rows, int64_t *n_pairs);
 
+// ---- semi / anti join (HashJoinExec join_type Semi / Anti): the rows of `left` -- ascending, each at most once -- for which at least one (Semi) or
+// no (Anti) row of `right` holds an equal key.  Assumptions (the fork's hash_join.rs is not in the reference tree; upstream DataFusion ~5/6, where
+// JoinType::{Semi, Anti} exist on HashJoinExec):
+//   A-S1  Semi: left rows with at least one right row equal in every key pair; Anti: left rows with none.
+//   A-S2  The output schema is the left input's; the right side contributes no column.
+//   A-S3  A left row appears at most once, however many right rows match it; left rows with equal keys are kept or dropped each on its own.
+//   A-S4  A NULL in any key column equals nothing: a NULL-keyed right row is never a match; a NULL-keyed left row is dropped by Semi and KEPT by
+//         Anti; with an empty right side Semi returns nothing and Anti every left row.
+//   A-S5  Rows come out in left input order (upstream emits from the build side's visited bitmap in index order): a stable filter of the left side.
+//   A-S6  Both modes (Partitioned, CollectLeft) are taken; which side carries the table is unobservable.
+// The right side is a SET -- a bitmap over [kmin, kmax] when `dense` (every right key inside it, dense_range_ok for n_right rows), else a hashed
+// table of 8-byte key slots -- and the left side is probed as a filter in the flag-tile geometry, then count -> scan -> emit.  Integer keys of one
+// signedness read in their columns' own types; `left.valid` is honoured (a NULL left key matches nothing), `right` holds no NULLs (the caller
+// drops them).  A left key outside [kmin, kmax] matches nothing.  *rows: ctx-owned.  One host wait.
+int semi_rows(flockgpu_ctx *ctx, const char *name, const DevColumn &left, int64_t n_left, const DevColumn &right, int64_t n_right, bool dense, int64_t kmin,
+              int64_t kmax, bool anti, int32_t **rows, int64_t *n_out);
+// semi_rows answers this pair of sizes with ONE workgroup and one launch (the right keys as a set in LDS): no statistics, no bitmap needed
+bool semi_is_tiny(int64_t n_left, int64_t n_right);
+// The same from per-left-row ids that already say "absent" with a negative value (utf8_codes' probe codes: int64; key_codes' probe ids: int32, -1
+// where a key column of the left row is NULL).
+int semi_rows_from_ids(flockgpu_ctx *ctx, const char *name, const void *ids, bool ids64, int64_t n_left, bool anti, int32_t **rows, int64_t *n_out);
+
 // ---- hash partition: rows grouped by destination (input order kept): dest = (fmix32(fold(key)) * n) >> 32, the
 // mix of flockgpu_partition_by_key.  part_offsets: host, n_parts + 1.
 int partition_rows_key64(flockgpu_ctx *ctx, const char *name, const int64_t *keys, int64_t rows, int32_t n_parts, int32_t **out_rows,

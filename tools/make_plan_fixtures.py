@@ -454,6 +454,16 @@ def main():
     with open(os.path.join(OUT, "unsupported_left_join.json"), "w") as f:
         json.dump(left_join, f, indent=1, sort_keys=True)
         f.write("\n")
+    # the golden join as a Semi / Anti join: the rows of t1 that have / lack a partner in t2 -- the left input's schema, nothing of t2
+    for name, jt in (("semi_join", "Semi"), ("anti_join", "Anti")):
+        p = golden_join()
+        j = p["input"]["input"]
+        j["join_type"] = jt
+        j["schema"] = schema(j["schema"]["fields"][:2])
+        p["expr"], p["schema"] = p["expr"][:2], schema(p["schema"]["fields"][:2])
+        with open(os.path.join(OUT, name + ".json"), "w") as f:
+            json.dump(p, f, indent=1, sort_keys=True)
+            f.write("\n")
     print("wrote", sorted(os.listdir(OUT)))
 
 
