@@ -700,6 +700,15 @@ bool holds_like(const Expr *e) {
         if (holds_like(x.get())) return true;
     return false;
 }
+// ... or a scalar function: `Filter(floor(f) > 3)`, `Project(p_time = now())`
+bool holds_func(const Expr *e) {
+    if (!e) return false;
+    if (e->kind == EKind::Func) return true;
+    if (holds_func(e->l.get()) || holds_func(e->r.get())) return true;
+    for (auto &x : e->list)
+        if (holds_func(x.get())) return true;
+    return false;
+}
 void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstream &os) {
     if (!e) { os << "?"; return; }
     static const std::pair<const char *, const char *> ops[] = {{"Eq", "="}, {"NotEq", "<>"}, {"Lt", "<"}, {"LtEq", "<="}, {"Gt", ">"}, {"GtEq", ">="}, {"And", "AND"}, {"Or", "OR"},
@@ -723,6 +732,14 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
             os << ")";
             return;
         case EKind::Case: os << "CASE ..."; return;
+        case EKind::Func: {
+            static const char *units[] = {"second", "minute", "hour", "day", "week", "month", "year", "dow", "doy"};
+            os << e->s << "(";
+            if (e->i >= 0 && e->i < 9) os << "'" << units[e->i] << "', ";
+            for (size_t i = 0; i < e->list.size(); ++i) { os << (i ? ", " : ""); pred_text(e->list[i].get(), schema, os); }
+            os << ")";
+            return;
+        }
         case EKind::Bin: {
             const char *sym = e->s.c_str();
             for (auto &o : ops)
@@ -753,10 +770,20 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
-    if (n->kind == NKind::Filter && holds_like(n->pred.get())) {
+    if (n->kind == NKind::Filter && (holds_like(n->pred.get()) || holds_func(n->pred.get()))) {
         os << "(";
         pred_text(n->pred.get(), n->schema, os);
         os << ")";
+    }
+    if (n->kind == NKind::Project) {   // the columns computed with a scalar function, as `name = expression`
+        bool any = false;
+        for (size_t i = 0; i < n->proj.size(); ++i) {
+            if (!holds_func(n->proj[i].first.get())) continue;
+            os << (any ? ", " : "(") << n->proj[i].second << " = ";
+            pred_text(n->proj[i].first.get(), n->in[0]->schema, os);
+            any = true;
+        }
+        if (any) os << ")";
     }
     if (n->kind == NKind::Window)
         for (size_t w = 0; w < n->win.size(); ++w) {
@@ -1085,6 +1112,9 @@ struct Exec {
     flockgpu_plan *pl;
     flockgpu_ctx *ctx;
     std::map<std::string, Table> memo;   // this execute's tables of the sub-trees that have twins (flockgpu_plan::twin_sig)
+    // now() (valprog.hpp A-F8): the UTC wall clock in milliseconds, read once -- here, as the execute begins
+    int64_t now_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
+    int fn_cols = 0;   // length columns written so far by this execute (octet_length / char_length: a buffer each, named by this count)
 
     // A relation the SQL scans twice (q5 and q7 read `bid` in both join inputs, q5_plan.fmt:6,13) has two MemoryExec leaves
     // but arrives as ONE source, which feed_data_sources hands to the first matching leaf (context.rs:273-300) -- the
@@ -1929,6 +1959,40 @@ struct Exec {
                 if (ta != ty || tb != ty) return val_unsupported("a binary operator over operands of different types");
                 *vt = is_cmp ? 5 : ty;
                 return b.push(is_cmp ? ck : arith_op(e->s), (ValType)(ty == 5 ? 1 : ty), 2) ? FLOCKGPU_OK : val_full();
+            }
+            case EKind::Func: {
+                if (e->fn == Fn::Now) {
+                    *vt = 1;
+                    return b.push(ValOpKind::Const, ValType::I64, 0, b.add_const((uint64_t)now_ms)) ? FLOCKGPU_OK : val_full();
+                }
+                if (e->fn == Fn::OctetLength || e->fn == Fn::CharLength) {   // a kernel of its own writes the lengths; the program reads them as an Int32 column
+                    const Expr *c = e->list[0].get();
+                    while (c->kind == EKind::Cast) c = c->l.get();
+                    if (c->kind != EKind::Col || in.cols[(size_t)c->col].c.type != ColType::UTF8) return val_unsupported("a text length of something that is not a Utf8 column");
+                    const TCol &col = in.cols[(size_t)c->col];
+                    *vt = 0;
+                    if (col.c.all_null) {
+                        *may_null = true;
+                        return b.push(ValOpKind::Null, ValType::I32, 0) ? FLOCKGPU_OK : val_full();
+                    }
+                    if (!col.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
+                    int32_t *len = nullptr;
+                    FG_TRY(utf8_lengths(ctx, node_key(pl, pl->ir.root.get(), "strlen", fn_cols++).c_str(), col.c, in.rows, e->fn == Fn::CharLength, &len));
+                    DevColumn d;
+                    d.type = ColType::I32;
+                    d.values = len;
+                    d.valid = col.c.valid;
+                    *may_null = *may_null || d.valid != nullptr;
+                    return b.push(ValOpKind::Col, ValType::I32, 0, b.add_col(d)) ? FLOCKGPU_OK : val_full();
+                }
+                const bool math = fn_is_math(e->fn);
+                int ta = -1;
+                FG_TRY(val_compile(e->list[0].get(), in, b, math ? 3 : 1, &ta, may_null));
+                if (ta != (math ? 3 : 1)) return val_unsupported("a scalar function over an argument of another type than it takes");
+                const ValFn fn = math ? (ValFn)((int)ValFn::Abs + (int)e->fn)
+                                      : (ValFn)((int)(e->fn == Fn::DateTrunc ? ValFn::TruncSecond : ValFn::PartSecond) + (int)e->i);
+                *vt = math ? 3 : e->fn == Fn::DateTrunc ? 1 : 0;
+                return b.push_func(fn, math ? ValType::F64 : ValType::I64) ? FLOCKGPU_OK : val_full();
             }
             case EKind::Case: {   // ELSE (or NULL), then from the LAST branch to the first: WHEN, THEN, Select -- the first TRUE WHEN wins
                 int ty = val_type_of(e, in);

@@ -32,7 +32,9 @@ struct Field {
 
 // Expression dialect (SURVEY.md appendix C + the unary / list expressions of the fork's expressions/*.rs, upstream DataFusion ~6:
 // IsNullExpr{arg}, IsNotNullExpr{arg}, NotExpr{arg}, NegativeExpr{arg}, InListExpr{expr, list, negated}).
-enum class EKind { Col, LitI, LitF, LitS, LitB, LitNull, Bin, Cast, Not, IsNull, IsNotNull, Neg, InList, Case };
+enum class EKind { Col, LitI, LitF, LitS, LitB, LitNull, Bin, Cast, Not, IsNull, IsNotNull, Neg, InList, Case, Func };
+// Scalar functions (`scalar_function_expr`; shape and semantics: valprog.hpp A-F1..A-F8)
+enum class Fn { Abs, Signum, Floor, Ceil, Round, Trunc, Sqrt, DateTrunc, DatePart, OctetLength, CharLength, Now };
 struct Expr {
     EKind kind = EKind::Col;
     int col = -1;  // Col: index into the input schema
@@ -47,7 +49,14 @@ struct Expr {
     bool cast_ts = false;                      // Cast: the target is Timestamp(Millisecond) (Int64 storage)
     bool try_cast = false;                     // Cast: try_cast_expr (a value that does not fit becomes NULL instead of failing the call)
     std::string lit_kind;                      // literals: the ScalarValue variant ("Int32", "Float64", ...; empty: a bare JSON value)
+    Fn fn = Fn::Abs;                           // Func: the function (`s`: its canonical name; `i`: the cal::Unit of date_trunc / date_part, else -1; `list`: the value
+                                               // arguments -- one, none for now(); the unit literal is folded into `i`)
 };
+inline bool fn_is_math(Fn f) { return f <= Fn::Sqrt; }
+// the result is a Timestamp(Millisecond): CAST(x AS Timestamp), date_trunc, now()
+inline bool expr_is_ts(const Expr *e) {
+    return (e->kind == EKind::Cast && e->cast_ts) || (e->kind == EKind::Func && (e->fn == Fn::DateTrunc || e->fn == Fn::Now));
+}
 
 // Static type of an expression over `schema`: 0..3 = ColType I32 / I64 / U64 / F64, 4 = Utf8, 5 = Boolean, -1 = an untyped literal (it takes
 // the type of whatever it meets), -2 = no consistent type.  (valprog.hpp: both operands of a binary operator have one type.)
@@ -73,6 +82,7 @@ inline int expr_static_type(const Expr *e, const std::vector<Field> &schema) {
             if (e->s == "Multiply" && (e->l->kind == EKind::LitF || e->r->kind == EKind::LitF)) return 3;
             return -2;
         }
+        case EKind::Func: return fn_is_math(e->fn) ? 3 : (e->fn == Fn::DateTrunc || e->fn == Fn::Now) ? 1 : 0;
         case EKind::Case: {
             int t = -1;
             for (size_t i = 1; i < e->list.size() && t == -1; i += 2) t = expr_static_type(e->list[i].get(), schema);
@@ -327,8 +337,114 @@ struct Builder {
             }
             return x;
         }
+        if (t == "scalar_function_expr") return func(e, schema);
         fail("physical_expr '" + t + "' is not supported");
         return nullptr;
+    }
+
+    // scalar_function_expr {name | fun, args, return_type} (valprog.hpp A-F1).  Every refusal starts with the node's tag and names its cause.
+    std::unique_ptr<Expr> func(const JValue *e, const std::vector<Field> &schema) {
+        auto refuse = [&](const std::string &why) -> std::unique_ptr<Expr> {
+            fail("scalar_function_expr: " + why);
+            return nullptr;
+        };
+        auto lower = [](std::string v) {
+            for (auto &ch : v) ch = (char)std::tolower((unsigned char)ch);
+            return v;
+        };
+        const JValue *nm = e->get("name");
+        if (!nm || nm->kind != JValue::Str) nm = e->get("fun");
+        if (!nm || nm->kind != JValue::Str || nm->str.empty()) return refuse("a node without a function name");
+        std::string name = lower(nm->str);
+        if (name == "character_length" || name == "length") name = "char_length";
+        static const std::pair<const char *, Fn> known[] = {{"abs", Fn::Abs}, {"signum", Fn::Signum}, {"floor", Fn::Floor}, {"ceil", Fn::Ceil}, {"round", Fn::Round},
+                                                            {"trunc", Fn::Trunc}, {"sqrt", Fn::Sqrt}, {"date_trunc", Fn::DateTrunc}, {"date_part", Fn::DatePart},
+                                                            {"octet_length", Fn::OctetLength}, {"char_length", Fn::CharLength}, {"now", Fn::Now}};
+        const std::pair<const char *, Fn> *k = nullptr;
+        for (auto &c : known)
+            if (name == c.first) k = &c;
+        if (!k) {
+            for (const char *f : {"exp", "ln", "log", "log2", "log10", "power", "sin", "cos", "tan", "asin", "acos", "atan"})
+                if (name == f) return refuse("function '" + name + "' has no bit-exact counterpart on the device");
+            for (const char *f : {"substr", "lower", "upper", "trim", "ltrim", "rtrim", "btrim", "concat", "concat_ws", "lpad", "rpad", "left", "right", "repeat", "replace",
+                                  "reverse", "split_part", "initcap", "translate", "to_hex", "chr", "md5", "sha256"})
+                if (name == f) return refuse("function '" + name + "' produces text: not yet");
+            if (name == "starts_with") return refuse("function 'starts_with' yields a Boolean (no Boolean columns at this boundary)");
+            return refuse("function '" + name + "' is not supported");
+        }
+        std::unique_ptr<Expr> x(new Expr());
+        x->kind = EKind::Func;
+        x->fn = k->second;
+        x->s = name;
+        x->i = -1;
+        const JValue *args = e->get("args");
+        std::vector<std::unique_ptr<Expr>> av;
+        if (args && args->kind == JValue::Arr)
+            for (auto &a : args->arr) {
+                auto ax = expr(a.get(), schema);
+                if (!ax) return nullptr;
+                av.push_back(std::move(ax));
+            }
+        else if (args && args->kind != JValue::Null) return refuse("function '" + name + "': args is not a list");
+        auto static_name = [&](const Expr *a) -> std::string {
+            if (expr_is_ts(a) || (a->kind == EKind::Col && schema[(size_t)a->col].is_ts)) return "Timestamp(ms)";
+            static const char *names[] = {"Int32", "Int64", "UInt64", "Float64", "Utf8", "Boolean"};
+            const int ty = expr_static_type(a, schema);
+            return ty >= 0 && ty <= 5 ? names[ty] : ty == -1 ? "an untyped literal" : "no consistent type";
+        };
+        auto no_utf8_cast = [](const Expr *a) {
+            while (a->kind == EKind::Cast && a->cast_to == ColType::UTF8) a = a->l.get();
+            return a;
+        };
+        ColType rt = ColType::F64;
+        bool rts = false;
+        if (fn_is_math(x->fn)) {
+            if (av.size() != 1) return refuse("function '" + name + "' with " + std::to_string(av.size()) + " arguments: it takes one (round(x, n) is not offered)");
+            const int ty = expr_static_type(av[0].get(), schema);
+            if (ty != 3 || expr_is_ts(av[0].get()))
+                return refuse("function '" + name + "': an argument of type " + static_name(av[0].get()) + ((ty >= 0 && ty <= 2) || ty == -1 ? " (an integer argument: the planner casts it to Float64)" : "") +
+                              ", it takes Float64");
+        } else if (x->fn == Fn::DateTrunc || x->fn == Fn::DatePart) {
+            if (av.size() != 2) return refuse("function '" + name + "' with " + std::to_string(av.size()) + " arguments: it takes (unit, timestamp)");
+            const Expr *u = no_utf8_cast(av[0].get());
+            if (u->kind != EKind::LitS) return refuse("function '" + name + "': the unit argument is not a Utf8 literal");
+            static const char *units[] = {"second", "minute", "hour", "day", "week", "month", "year", "dow", "doy"};
+            const std::string unit = lower(u->s);
+            for (int i = 0; i < 9; ++i)
+                if (unit == units[i]) x->i = i;
+            const bool trunc = x->fn == Fn::DateTrunc;
+            if (x->i < 0 || (trunc && x->i > 6) || (!trunc && x->i == 4))
+                return refuse("function '" + name + "': unit '" + u->s + "' (supported: " +
+                              (trunc ? "second, minute, hour, day, week, month, year" : "year, month, day, hour, minute, second, dow, doy") + ")");
+            const Expr *ts = av[1].get();
+            if (!(expr_is_ts(ts) || (ts->kind == EKind::Col && schema[(size_t)ts->col].is_ts)))
+                return refuse("function '" + name + "': an argument of type " + static_name(ts) + ", it takes a Timestamp(ms) column or a Timestamp-valued function");
+            av.erase(av.begin());
+            rt = trunc ? ColType::I64 : ColType::I32;
+            rts = trunc;
+        } else if (x->fn == Fn::Now) {
+            if (!av.empty()) return refuse("function 'now' with " + std::to_string(av.size()) + " arguments: it takes none");
+            rt = ColType::I64;
+            rts = true;
+        } else {
+            if (av.size() != 1) return refuse("function '" + name + "' with " + std::to_string(av.size()) + " arguments: it takes one");
+            const Expr *c = no_utf8_cast(av[0].get());
+            if (c->kind != EKind::Col || schema[(size_t)c->col].type != ColType::UTF8)
+                return refuse("function '" + name + "': an argument that is not a Utf8 column (" + (c->kind == EKind::Col ? static_name(c) : std::string("a computed value")) + ")");
+            rt = ColType::I32;
+        }
+        const JValue *rj = e->get("return_type");
+        if (rj && rj->kind != JValue::Null) {
+            ColType gt;
+            bool gts = false;
+            Field want;
+            want.type = rt;
+            want.is_ts = rts;
+            if (!parse_type(rj, &gt, &gts) || gt != rt || gts != rts)
+                return refuse("function '" + name + "': return_type is not the function's " + type_name(want));
+        }
+        x->list = std::move(av);
+        return x;
     }
 
     // LIKE / NOT LIKE (strmatch.hpp): a Utf8 column (a cast to Utf8 may sit in front of it) against a literal pattern without a backslash, within the
@@ -386,7 +502,7 @@ struct Builder {
         f.name = "#" + std::to_string(in->schema.size());
         f.type = (ColType)ty;
         f.nullable = true;
-        f.is_ts = x->kind == EKind::Cast && x->cast_ts;
+        f.is_ts = expr_is_ts(x.get());
         in->proj.emplace_back(std::move(x), f.name);
         in->schema.push_back(f);
         return (int)in->schema.size() - 1;
@@ -486,7 +602,7 @@ struct Builder {
                     if (!check_like(e.get(), in->schema, false)) return nullptr;
                     f.type = (ColType)ty;
                     f.nullable = true;
-                    f.is_ts = e->kind == EKind::Cast && e->cast_ts;   // CAST(x AS Timestamp(Millisecond))
+                    f.is_ts = expr_is_ts(e.get());   // CAST(x AS Timestamp(Millisecond)), date_trunc, now()
                 }
                 n->proj.emplace_back(std::move(e), f.name);
                 n->schema.push_back(f);
@@ -923,13 +1039,16 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
     }
 }
 
-// The columns whose NULL makes `e` NULL: reached through arithmetic, comparisons, casts and unary minus only.  A column under CASE, IS [NOT] NULL,
+// The columns whose NULL makes `e` NULL: reached through arithmetic, comparisons, casts, unary minus and scalar functions only.  A column under CASE, IS [NOT] NULL,
 // IN, NOT, AND / OR does not count -- `CASE WHEN f <= f THEN 100 ELSE i END` has a value where f is NULL.
 inline void strict_cols(const Expr *e, std::set<int> *out) {
     if (!e) return;
     switch (e->kind) {
         case EKind::Col: out->insert(e->col); return;
         case EKind::Cast: case EKind::Neg: strict_cols(e->l.get(), out); return;
+        case EKind::Func:   // a function of a NULL is NULL (A-F2)
+            for (auto &a : e->list) strict_cols(a.get(), out);
+            return;
         case EKind::Bin:
             if (e->s == "And" || e->s == "Or") return;
             strict_cols(e->l.get(), out);

@@ -1,6 +1,7 @@
 // The general expression evaluator of the plan layer: a postfix program per expression, interpreted per row (valprog.hpp).
 #include <type_traits>
 
+#include "calendar.hpp"
 #include "valprog.hpp"
 
 using namespace flockgpu;
@@ -182,6 +183,36 @@ template <class F> __device__ __forceinline__ void with_cmp(uint8_t k, F &&f) {
     }
 }
 
+// The scalar functions (valprog.hpp A-F3..A-F5), one value in its stack form to one value in its stack form.  FN is a compile-time constant: the
+// interpreter branches on the function once per operator and pass, the per-value code is straight-line.
+__device__ __forceinline__ double round_half_away(double x) {   // Rust's f64::round
+    const double t = trunc(x);   // (keeps the sign of a zero: round(-0.4) = -0.0)
+    return fabs(x - t) >= 0.5 ? t + copysign(1.0, x) : t;   // x - t is exact; NaN and +-inf compare false and pass through
+}
+template <uint8_t FN> __device__ __forceinline__ uint64_t apply_fn(uint64_t a) {
+    constexpr ValFn fn = (ValFn)FN;
+    if (fn < ValFn::TruncSecond) {
+        const double x = as_f64(a);
+        switch (fn) {
+            case ValFn::Abs: return f64_bits(fabs(x));
+            case ValFn::Signum: return f64_bits(x != x ? x : copysign(1.0, x));
+            case ValFn::Floor: return f64_bits(floor(x));
+            case ValFn::Ceil: return f64_bits(ceil(x));
+            case ValFn::Round: return f64_bits(round_half_away(x));
+            case ValFn::Trunc: return f64_bits(trunc(x));
+            default: return f64_bits(__dsqrt_rn(x));
+        }
+    }
+    if (fn < ValFn::PartSecond) return (uint64_t)cal::date_trunc<FN - (uint8_t)ValFn::TruncSecond>((int64_t)a);
+    return (uint64_t)(int64_t)cal::date_part<FN - (uint8_t)ValFn::PartSecond>((int64_t)a);
+}
+template <uint8_t FN, class F> __device__ __forceinline__ void with_fn_from(uint8_t fn, F &&f) {
+    if constexpr (FN < (uint8_t)ValFn::kCount) {
+        if (fn == FN) f(U8<FN>{});
+        else with_fn_from<FN + 1>(fn, f);
+    }
+}
+
 // One pass of the program over FOUR consecutive rows per lane.  Values on the stack: 4 x 64 bits + 4 validity bits; the top of the stack in
 // registers (tv / tok), what waits below it in the lane's own columns of `s_v` / `s_ok` (no bank conflicts, no barrier).  r0: the lane's
 // first row; rows at or beyond n load nothing and come out NULL.
@@ -226,7 +257,9 @@ __device__ __forceinline__ Vec4 load_col4(const ValCol &c, int64_t r0, int64_t n
 
 // kG: 16-byte groups per pass -- a pass of the program evaluates 4 kG rows per lane (kG = 4: a lane has four loads per column operand in
 // flight and one scalar dispatch per operator and sixteen rows; kG = 1 for programs whose operand stack would not fit the LDS otherwise).
-template <bool kMask, int kG>
+// kFunc: the instances that know the Func operator (scalar functions).  A program without one runs on the kFunc = false instances, whose code -- and
+// register allocation -- is what it was before the functions came.
+template <bool kMask, int kG, bool kFunc>
 __global__ __launch_bounds__(kBlock) void valprog_kernel(ValProgram p, int64_t n, int32_t n_tiles, void *__restrict__ out_values, uint8_t *__restrict__ out_valid,
                                                          int32_t out_type, uint32_t *__restrict__ flag_words, uint32_t *__restrict__ counts, uint32_t *err) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_dyn[];   // [max_stack - 1][kG][4][kBlock] values, then [max_stack - 1][kG][kBlock] validity nibbles
@@ -514,6 +547,17 @@ __global__ __launch_bounds__(kBlock) void valprog_kernel(ValProgram p, int64_t n
                         sp -= 2;
                         break;
                     }
+                    case ValOpKind::Func:
+                        if constexpr (kFunc) {   // the result of a NULL is NULL and its slot stays 0 (A-F2)
+                            with_fn_from<0>(op.to, [&](auto FNC) {
+                                constexpr uint8_t fn = decltype(FNC)::value;
+#pragma unroll
+                                for (int g = 0; g < kG; ++g)
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) top[g].v[j] = apply_fn<fn>(top[g].v[j]) & (0 - (uint64_t)((top[g].ok >> j) & 1u));
+                            });
+                        }
+                        break;
                 }
             }
 #pragma unroll
@@ -556,14 +600,25 @@ size_t stack_bytes(const ValProgram &prog);
 int groups_of(const ValProgram &prog) {
     return prog.max_stack <= 2 ? kValGroups : prog.max_stack <= 3 && kValGroups > 2 ? 2 : 1;
 }
+bool holds_func(const ValProgram &prog) {
+    for (int o = 0; o < prog.n_ops; ++o)
+        if (prog.ops[o].kind == (uint8_t)ValOpKind::Func) return true;
+    return false;
+}
+template <bool kMask, bool kFunc>
+void launch_as(flockgpu_ctx *ctx, const ValProgram &prog, unsigned grid, int64_t rows, int32_t n_tiles, void *out_values, uint8_t *out_valid, int32_t out_type, uint32_t *flags,
+               uint32_t *counts, uint32_t *d_err) {
+    const int g = groups_of(prog);
+    const size_t lds = stack_bytes(prog);
+    if (g == 4) hipLaunchKernelGGL((valprog_kernel<kMask, 4, kFunc>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
+    else if (g == 2) hipLaunchKernelGGL((valprog_kernel<kMask, 2, kFunc>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
+    else hipLaunchKernelGGL((valprog_kernel<kMask, 1, kFunc>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
+}
 template <bool kMask>
 void launch(flockgpu_ctx *ctx, const ValProgram &prog, unsigned grid, int64_t rows, int32_t n_tiles, void *out_values, uint8_t *out_valid, int32_t out_type, uint32_t *flags,
             uint32_t *counts, uint32_t *d_err) {
-    const int g = groups_of(prog);
-    const size_t lds = stack_bytes(prog);
-    if (g == 4) hipLaunchKernelGGL((valprog_kernel<kMask, 4>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
-    else if (g == 2) hipLaunchKernelGGL((valprog_kernel<kMask, 2>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
-    else hipLaunchKernelGGL((valprog_kernel<kMask, 1>), dim3(grid), dim3(kBlock), lds, ctx->stream, prog, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
+    if (holds_func(prog)) launch_as<kMask, true>(ctx, prog, grid, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
+    else launch_as<kMask, false>(ctx, prog, grid, rows, n_tiles, out_values, out_valid, out_type, flags, counts, d_err);
 }
 size_t stack_bytes(const ValProgram &prog) {
     const size_t below = prog.max_stack > 1 ? (size_t)prog.max_stack - 1 : 0;

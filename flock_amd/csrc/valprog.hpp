@@ -27,6 +27,26 @@
 //   A-V6 comparisons yield NULL when an operand is NULL; AND / OR / NOT are Kleene; IS [NOT] NULL never yields NULL;
 //   A-V7 CASE evaluates every branch for every row (as the fork's CaseExpr does over the whole batch) and picks the first WHEN that is
 //        TRUE, else ELSE, else NULL.
+//
+// Scalar functions (`scalar_function_expr`).  The fork's serde shape of ScalarFunctionExpr is not in the reference tree either; semantics are upstream
+// DataFusion ~5/6's, i.e. Rust `f64` methods and chrono (ASSUMPTIONS, checked against tests/scalar_fn_ref.py and, there, against pyarrow.compute):
+//   A-F1 the node is {"physical_expr": "scalar_function_expr", "name" | "fun": <name, any letter case>, "args": [<expr>, ...], "return_type": <data_type>};
+//        a return_type that is not the function's result type is refused, a missing one is taken as the result type;
+//   A-F2 a function of a NULL argument is NULL, and no function fails the call;
+//   A-F3 math, Float64 -> Float64, one argument of static type Float64 (the planner casts): abs, signum, floor, ceil, round, trunc, sqrt are Rust's
+//        f64::abs / signum / floor / ceil / round / trunc / sqrt: round takes halves away from zero; signum is 1.0 for +0.0 and +inf, -1.0 for -0.0
+//        and -inf, NaN for NaN; abs(-0.0) = +0.0; floor / ceil / trunc keep the sign of a zero result; sqrt is the correctly rounded IEEE root
+//        (NaN below zero, -0.0 for -0.0).  Every one of them is bit-exact on the device; exp, ln, log*, power and the trigonometric functions have no
+//        bit-exact counterpart there and are refused;
+//   A-F4 date_trunc(unit, ts) -> Timestamp(ms), unit a Utf8 literal among second, minute, hour, day, week (starts on Monday), month, year;
+//        proleptic Gregorian calendar, UTC; before 1970 towards minus infinity (date_trunc('day', -1 ms) = -86 400 000);
+//   A-F5 date_part(unit, ts) -> Int32, unit among year, month, day, hour, minute, second (whole seconds 0..59), dow (Sunday = 0), doy (from 1);
+//   A-F6 ts is a Timestamp(ms) column or a Timestamp-valued function (date_trunc, now()); an Int64 value is not one;
+//   A-F7 octet_length(s) -> Int32 bytes; char_length(s) = character_length = length -> Int32 code points = bytes that are not 10xxxxxx (strmatch.hpp
+//        A-L2); s is a Utf8 column (a cast to Utf8 may sit in front).  A kernel per (column, function) writes the lengths as an Int32 column
+//        (strlen.hip) which the program reads as any other column; the source's validity passes through;
+//   A-F8 now() -> Timestamp(ms): the UTC wall clock, read once on the host when an execute begins; one value for every row and every occurrence.
+//        The program holds it as a constant.
 #pragma once
 #include "relops.hpp"
 #include "divmagic.hpp"
@@ -45,7 +65,15 @@ enum class ValOpKind : uint8_t {
     Cast, TryCast,                                // `type` -> `to`
     Eq, Ne, Lt, Le, Gt, Ge,                       // compare in `type` -> BOOL
     And, Or, Not, IsNull, IsNotNull,              // BOOL (IsNull: any type)
-    Select                                        // pops THEN, WHEN, ELSE (pushed in the order ELSE, WHEN, THEN)
+    Select,                                       // pops THEN, WHEN, ELSE (pushed in the order ELSE, WHEN, THEN)
+    Func                                          // a unary scalar function of the top: `to` = ValFn, `type` = the operand's type (F64 / I64)
+};
+// The device functions (A-F3..A-F5).  A program that holds one runs on the interpreter's kFunc instances (valprog.hip): the others keep their registers.
+enum class ValFn : uint8_t {
+    Abs = 0, Signum, Floor, Ceil, Round, Trunc, Sqrt,                                              // Float64 -> Float64
+    TruncSecond, TruncMinute, TruncHour, TruncDay, TruncWeek, TruncMonth, TruncYear,             // Timestamp(ms) -> Timestamp(ms): + cal::Unit
+    PartSecond, PartMinute, PartHour, PartDay, PartWeekUnused, PartMonth, PartYear, PartDow, PartDoy,   // Timestamp(ms) -> Int32: + cal::Unit
+    kCount
 };
 struct ValOp {
     uint8_t kind, type, to, arg;   // ValOpKind; operand ValType; Cast target -- or, on a binary operator, kValImm: the right operand is consts[arg]
@@ -97,6 +125,13 @@ struct ValBuilder {
         if (depth > p.max_stack) p.max_stack = depth;
         if (depth >= 1 && depth <= kValMaxStack) set_narrow(depth - 1, fits);
         return depth >= 1 && depth <= kValMaxStack;
+    }
+    // a unary function of the top of the stack (never fused with a literal: its operand is no Const the builder may take back)
+    bool push_func(ValFn fn, ValType type) {
+        if (p.n_ops >= kValMaxOps || depth < 1) return false;
+        p.ops[p.n_ops++] = ValOp{(uint8_t)ValOpKind::Func, (uint8_t)type, (uint8_t)fn, 0};
+        set_narrow(depth - 1, fn >= ValFn::PartSecond);   // (date_part: an Int32)
+        return true;
     }
     void set_narrow(int slot, bool v) { narrow = v ? narrow | (1u << slot) : narrow & ~(1u << slot); }
     bool is_narrow(int slot) const { return slot >= 0 && ((narrow >> slot) & 1u); }
@@ -168,5 +203,8 @@ int valprog_to_column(flockgpu_ctx *ctx, const char *name, const ValProgram &pro
 // FilterExec: the rows where the BOOL result is TRUE (FALSE and NULL: dropped), in order -- flag words + wave counts from the evaluating
 // kernel itself, then the scan / emit of pred_to_rows.  One host wait (row count + error word).
 int valprog_to_rows(flockgpu_ctx *ctx, const char *name, const ValProgram &prog, int64_t rows, int32_t **out_rows, int64_t *n_out);
+// octet_length / char_length of a Utf8 column (A-F7; strlen.hip): one Int32 per row in an arena buffer called `name`, NULL rows included (their bytes are
+// whatever the column holds: the consumer reads the source's validity).  No host wait.
+int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out);
 
 }  // namespace flockgpu

@@ -204,6 +204,29 @@ def q11():
     return proj(final, [(col("bidder", 0), "bidder"), (col(names[0], 1), "bid_count"), (col(names[1], 2), "start_time"), (col(names[2], 3), "end_time")], out)
 
 
+def q12_p_time():
+    # benchmarks/src/nexmark/query/q12.sql, first statement: `SELECT *, now() AS p_time FROM bid` -- a projection over the scan whose last column is the
+    # scalar function now() (the node's shape: flock_amd/csrc/valprog.hpp A-F1)
+    now = {"physical_expr": "scalar_function_expr", "name": "now", "args": [], "return_type": TS}
+    return proj(rr(memory(BID, [0, 1, 2, 3], "bid")), [(col(f["name"], i), f["name"]) for i, f in enumerate(BID)] + [(now, "p_time")], BID + [field("p_time", TS, True)])
+
+
+def q12():
+    # q12.sql, second statement, over the first one's result (which the launcher registers as `bid` again):
+    # `SELECT bidder, COUNT(*) AS bid_count, MIN(p_time) AS start_time, MAX(p_time) AS end_time FROM bid GROUP BY bidder`
+    src = BID + [field("p_time", TS, True)]
+    inp = [field("bidder", "Int32"), field("p_time", TS, True)]
+    aggs = [{"aggregate_expr": "count", "name": "COUNT(UInt8(1))", "data_type": "UInt64", "nullable": True, "expr": lit("UInt8", 1)},
+            {"aggregate_expr": "min", "name": "MIN(bid.p_time)", "data_type": TS, "nullable": True, "expr": col("p_time", 1)},
+            {"aggregate_expr": "max", "name": "MAX(bid.p_time)", "data_type": TS, "nullable": True, "expr": col("p_time", 1)}]
+    part = [field("bidder", "Int32"), field("COUNT(UInt8(1))[count]", "UInt64", True), field("MIN(bid.p_time)[min]", TS, True), field("MAX(bid.p_time)[max]", TS, True)]
+    fin = [field("bidder", "Int32"), field("COUNT(UInt8(1))", "UInt64", True), field("MIN(bid.p_time)", TS, True), field("MAX(bid.p_time)", TS, True)]
+    partial = agg(rr(memory(src, [1, 4], "bid")), "Partial", [(col("bidder", 0), "bidder")], aggs, inp, part)
+    final = agg(coalesce(hashp(partial, [col("bidder", 0)])), "FinalPartitioned", [(col("bidder", 0), "bidder")], aggs, inp, fin)
+    out = [field("bidder", "Int32"), field("bid_count", "UInt64", True), field("start_time", TS, True), field("end_time", TS, True)]
+    return proj(final, [(col("bidder", 0), "bidder"), (col("COUNT(UInt8(1))", 1), "bid_count"), (col("MIN(bid.p_time)", 2), "start_time"), (col("MAX(bid.p_time)", 3), "end_time")], out)
+
+
 def q13():
     # benchmarks/src/nexmark/query/q13.sql + q13_plan.fmt (SURVEY.md section 8(f) "next" query):
     # Projection [auction, bidder, price, b_date_time, value] <- HashJoin(auction = key)
@@ -431,7 +454,8 @@ def main():
         with open(os.path.join(OUT, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1, sort_keys=True)
             f.write("\n")
-    for name, fn in (("q0", q0), ("q10", q0), ("q1", q1), ("q2", q2), ("q3", q3), ("q5", q5), ("q8", q8), ("q7", q7), ("q13", q13), ("q4", q4), ("q9", q9), ("q11", q11), ("ysb", ysb), ("q6", q6)):
+    for name, fn in (("q0", q0), ("q10", q0), ("q1", q1), ("q2", q2), ("q3", q3), ("q5", q5), ("q8", q8), ("q7", q7), ("q13", q13), ("q4", q4), ("q9", q9), ("q11", q11), ("ysb", ysb), ("q6", q6),
+                     ("q12_p_time", q12_p_time), ("q12", q12)):
         with open(os.path.join(OUT, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1, sort_keys=True)
             f.write("\n")
