@@ -21,6 +21,7 @@
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
 #include "pred.hpp"
+#include "reduce.hpp"
 #include "strmatch.hpp"
 #include "valprog.hpp"
 
@@ -2052,6 +2053,26 @@ struct Exec {
         return valprog_to_rows(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, rows, n_out);
     }
 
+    // The filter's predicate pass alone: flag words and wave counts over its INPUT table (pred.hpp pred_to_flags), for an ungrouped aggregate that
+    // reads the input columns under them -- no scan, no emit, no take.
+    int filter_flags(const Node *n, Table *in, const uint32_t **flags, const uint32_t **counts, int32_t *tiles) {
+        FG_TRY(exec(n->in[0].get(), in));
+        PredBuilder b;
+        words_node = n;
+        words_used = 0;
+        col_rows = in->rows;
+        const int rc = compile_pred(n->pred.get(), *in, b);
+        words_node = nullptr;
+        if (rc == FLOCKGPU_OK) return pred_to_flags(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, flags, counts, tiles);
+        if (rc != FLOCKGPU_ERR_UNSUPPORTED) return rc;
+        ValBuilder vb;
+        int vt = -1;
+        bool may_null = false;
+        FG_TRY(val_compile(n->pred.get(), *in, vb, 5, &vt, &may_null));
+        if (vt != 5) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a filter predicate that is not Boolean");
+        return valprog_to_flags(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, flags, counts, tiles);
+    }
+
     // A FilterExec directly under a join (round 6): the filter's surviving rows as a ROW LIST over its input table -- nothing is taken yet.  The
     // join reads the key column through the list, and its result rows compose with it (via[pair row]), so the columns that only travel
     // through -- q3's three Utf8 columns of a person -- are gathered ONCE, at the join's output, instead of after the filter and again after
@@ -2131,6 +2152,35 @@ struct Exec {
         z->rows = z->base.rows;
         return FLOCKGPU_OK;
     }
+    // `key` = column c of `z` as lazy_key returned it, with validity bytes: the rows whose key is not NULL become the side's row list (what a filter
+    // on `key IS NOT NULL` would leave), and the key is taken through it.  One host wait (the row count).
+    int drop_null_key_rows(const Node *n, Lazy *z, int c, const char *what, TCol *key) {
+        PredBuilder b;
+        PredLeafDesc d{};
+        d.kind = (uint8_t)PredLeafKind::IsNull;
+        d.negate = 1;
+        const int ia = b.add_col(key->c);
+        if (ia < 0) return pred_full();
+        d.a = (uint8_t)ia;
+        if (!b.add_leaf(d)) return pred_full();
+        int32_t *rows = nullptr;
+        int64_t n_out = 0;
+        FG_TRY(pred_to_rows(ctx, node_key(pl, n, what).c_str(), b.p, z->rows, &rows, &n_out));
+        if (z->via && n_out > 0) {
+            int32_t *composed = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, what, 1).c_str(), (size_t)n_out + 4, &composed));
+            FG_TRY(gather_i32(ctx, z->via, rows, n_out, composed));
+            rows = composed;
+        }
+        z->via = rows;
+        z->rows = n_out;
+        const TCol &src = z->base.cols[(size_t)c];
+        FG_TRY(take_column(ctx, node_key(pl, n, what, 2).c_str(), src.c, z->via, z->rows, &key->c));
+        key->c.valid = nullptr;   // (every row of the list has a key)
+        key->subset_of = src.subset_of ? src.subset_of : src.c.values;
+        return FLOCKGPU_OK;
+    }
+
     // column `c` of a lazy table as the join sees it: taken through the row list when there is one
     int lazy_key(const Node *n, const Lazy &z, int c, const char *what, TCol *out) {
         *out = z.base.cols[(size_t)c];
@@ -2376,6 +2426,10 @@ struct Exec {
                 if (!text_keys && ((lk.c.type == ColType::U64) != (rk.c.type == ColType::U64) || lk.c.type == ColType::UTF8 || rk.c.type == ColType::UTF8 ||
                                    lk.c.type == ColType::F64 || rk.c.type == ColType::F64))
                     return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
+                // one key pair, a side whose key is a computed column with validity bytes -- an ungrouped aggregate's row (MAX over nothing is NULL), which
+                // stays on the device: NULL keys never match, the side goes on as the row list of its valid keys
+                if (n->on_l2 < 0 && lk.c.valid && lk.present && !lk.c.all_null) FG_TRY(drop_null_key_rows(n, &ZL, n->on_l, "nnl", &lk));
+                if (n->on_l2 < 0 && rk.c.valid && rk.present && !rk.c.all_null) FG_TRY(drop_null_key_rows(n, &ZR, n->on_r, "nnr", &rk));
                 int64_t nl = ZL.rows, nr = ZR.rows;
                 if (lk.c.all_null) nl = 0;  // NULL keys never match
                 if (rk.c.all_null) nr = 0;
@@ -2715,6 +2769,162 @@ struct Exec {
         return FLOCKGPU_OK;
     }
 
+    // The FilterExec an ungrouped aggregate sits on, through repartitions and projections that only name columns; map[c] = the filter's column
+    // behind column c of `src`.  Null: something else is below (it is materialised as ever).
+    const Node *filter_below(const Node *src, std::vector<int> *map) const {
+        std::vector<int> m(src->schema.size());
+        for (size_t i = 0; i < m.size(); ++i) m[i] = (int)i;
+        for (const Node *c = src;;) {
+            // (a filter over bids the q2 pipeline would run -- and materialise -- is read under its flags like any other)
+            const Fused fk = pl->fused[(size_t)c->id].kind;
+            if (fk != kNone && !(fk == kQ2 && c->kind == NKind::Filter)) return nullptr;
+            if (c->kind == NKind::Repartition) {
+                c = c->in[0].get();
+            } else if (c->kind == NKind::Project) {
+                for (auto &pe : c->proj)
+                    if (pe.first->kind != EKind::Col) return nullptr;
+                for (int &x : m) {
+                    if ((size_t)x >= c->proj.size()) return nullptr;
+                    x = c->proj[(size_t)x].first->col;
+                }
+                c = c->in[0].get();
+            } else if (c->kind == NKind::Filter) {
+                for (int x : m)
+                    if (x < 0 || (size_t)x >= c->schema.size()) return nullptr;
+                *map = m;
+                return c;
+            } else {
+                return nullptr;
+            }
+        }
+    }
+
+    // ---- no GROUP BY: COUNT / SUM / MIN / MAX / AVG, any list of them, in Partial and Final mode -> ONE row in every case (reduce.hpp): one streaming
+    // pass for all accumulators, a fold that writes the row on the device, no wait.  Directly over a filter the filter is not materialised: its
+    // predicate pass leaves flag words and the pass reads the filter's input columns under them.
+    int exec_global_aggregate(const Node *n, Table *t) {
+        Table in;
+        const uint32_t *flags = nullptr, *wave_counts = nullptr;
+        int32_t flag_tiles = 0;
+        std::vector<int> map;
+        if (const Node *f = filter_below(n->in[0].get(), &map)) {
+            Table fin;
+            FG_TRY(filter_flags(f, &fin, &flags, &wave_counts, &flag_tiles));
+            in.rows = fin.rows;
+            in.cols.resize(map.size());
+            for (size_t i = 0; i < map.size(); ++i) in.cols[i] = fin.cols[(size_t)map[i]];
+        } else {
+            FG_TRY(exec(n->in[0].get(), &in));
+        }
+        const bool is_final = n->mode != "Partial";
+        ReduceProgram P;
+        // the program's column for input column c (*out = -1: the column holds nothing but NULLs)
+        auto col_of = [&](int c, const char *what, bool allow_f64, int *out) -> int {
+            if (c < 0 || (size_t)c >= in.cols.size() || in.cols[(size_t)c].c.type == ColType::UTF8 || (in.cols[(size_t)c].c.type == ColType::F64 && !allow_f64) ||
+                (!in.cols[(size_t)c].present && !in.cols[(size_t)c].c.all_null))
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", what);
+            const DevColumn &d = in.cols[(size_t)c].c;
+            *out = -1;
+            if (d.all_null) return FLOCKGPU_OK;
+            for (int i = 0; i < P.n_cols; ++i)
+                if (P.cols[i].values == d.values && P.cols[i].valid == d.valid && P.cols[i].type == (int32_t)d.type) *out = i;
+            if (*out >= 0) return FLOCKGPU_OK;
+            if (P.n_cols == kReduceMaxCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d argument columns in one ungrouped aggregate", kReduceMaxCols);
+            P.cols[P.n_cols].values = d.values;
+            P.cols[P.n_cols].valid = d.valid;
+            P.cols[P.n_cols].type = (int32_t)d.type;
+            *out = P.n_cols++;
+            return FLOCKGPU_OK;
+        };
+        auto slot_of = [&](ReduceKind kind, int col, uint64_t flip, bool f64, bool inv, int *out) -> int {
+            *out = -1;
+            if (col < 0) return FLOCKGPU_OK;
+            for (int i = 0; i < P.n_slots; ++i)
+                if (P.slots[i].kind == (int32_t)kind && P.slots[i].col == col && P.slots[i].flip == flip) *out = i;
+            if (*out >= 0) return FLOCKGPU_OK;
+            if (P.n_slots == kReduceMaxSlots) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one ungrouped aggregate", kReduceMaxSlots);
+            P.slots[P.n_slots].kind = (int32_t)kind;
+            P.slots[P.n_slots].col = col;
+            P.slots[P.n_slots].flip = flip;
+            P.slots[P.n_slots].f64 = f64;
+            P.slots[P.n_slots].inv = inv;
+            *out = P.n_slots++;
+            return FLOCKGPU_OK;
+        };
+        auto emit = [&](ReduceOutKind kind, int col, int a, int b) {
+            ReduceOut &o = P.outs[P.n_outs++];
+            o.kind = (int32_t)kind;
+            o.col = col;
+            o.a = a;
+            o.b = b;
+        };
+        if (ir::ungrouped_accumulators(n) > kReduceMaxSlots)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one ungrouped aggregate", kReduceMaxSlots);
+        constexpr uint64_t kSign = 0x8000000000000000ull;
+        for (auto &a : n->aggs) {
+            const size_t oc = (size_t)P.n_outs;
+            int c = -1, s = -1, s2 = -1;
+            if (a.fn == "count") {
+                if (is_final) {   // the sum of the count states; over no state row it is 0, not NULL
+                    FG_TRY(col_of(a.arg, "the COUNT state", false, &c));
+                    FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
+                    emit(ReduceOutKind::ValueAlways, c, s, -1);
+                } else if (a.arg < 0) {   // COUNT(*) / COUNT(UInt8(1))
+                    emit(ReduceOutKind::Rows, -1, -1, -1);
+                } else {
+                    if ((size_t)a.arg >= in.cols.size() || in.cols[(size_t)a.arg].c.type == ColType::UTF8)
+                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: count needs an integer column");
+                    const DevColumn &d = in.cols[(size_t)a.arg].c;
+                    if (!d.all_null && !d.valid) {   // no NULL among the values: the rows selected
+                        emit(ReduceOutKind::Rows, -1, -1, -1);
+                    } else {
+                        FG_TRY(col_of(a.arg, "count", true, &c));
+                        emit(ReduceOutKind::ColCount, c, -1, -1);
+                    }
+                }
+            } else if (a.fn == "sum") {
+                FG_TRY(col_of(a.arg, "sum", false, &c));
+                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
+                emit(ReduceOutKind::Value, c, s, -1);
+            } else if (a.fn == "max" || a.fn == "min") {
+                FG_TRY(col_of(a.arg, a.fn.c_str(), true, &c));
+                const ColType at = in.cols[(size_t)a.arg].c.type, want = n->schema[oc].type;
+                if ((want == ColType::F64) != (at == ColType::F64) || (want == ColType::I32) != (at == ColType::I32) || want == ColType::UTF8)
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", a.fn.c_str());
+                const bool inv = a.fn == "min";
+                FG_TRY(slot_of(ReduceKind::UMax, c, (at == ColType::U64 ? 0 : kSign) ^ (inv ? ~uint64_t(0) : 0), at == ColType::F64, inv, &s));
+                emit(ReduceOutKind::Value, c, s, -1);
+            } else if (is_final) {   // avg: (count, sum) states -> sum / count
+                FG_TRY(col_of(a.arg, "the AVG count state", false, &c));
+                int c2 = -1;
+                if (a.arg2 < 0 || (size_t)a.arg2 >= in.cols.size() || in.cols[(size_t)a.arg2].c.type != ColType::F64)
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: the AVG sum state must be Float64");
+                FG_TRY(col_of(a.arg2, "the AVG sum state", true, &c2));
+                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
+                FG_TRY(slot_of(ReduceKind::SumF64, c2, 0, true, false, &s2));
+                emit(ReduceOutKind::AvgFinal, c, s, s2);
+            } else {   // avg -> its state: [count UInt64, sum Float64]
+                FG_TRY(col_of(a.arg, "AVG", false, &c));
+                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
+                emit(ReduceOutKind::ColCount, c, -1, -1);
+                emit(ReduceOutKind::SumAsF64, c, s, in.cols[(size_t)a.arg].c.type == ColType::U64 ? 1 : 0);
+            }
+        }
+        if ((size_t)P.n_outs != n->schema.size()) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: an ungrouped aggregate whose schema is not its aggregates'");
+        uint64_t *out = nullptr;
+        FG_TRY(arena_get_t(ctx, node_key(pl, n, "gagg").c_str(), (size_t)kReduceMaxOuts + kReduceMaxOuts / 8 + 2, &out));
+        uint8_t *ov = reinterpret_cast<uint8_t *>(out + kReduceMaxOuts);
+        FG_TRY(reduce_global(ctx, node_key(pl, n, "gred").c_str(), P, in.rows, flags, wave_counts, flag_tiles, out, ov));
+        t->rows = 1;
+        t->cols.assign(n->schema.size(), TCol{});
+        for (size_t i = 0; i < n->schema.size(); ++i) {
+            t->cols[i] = dev_col(n->schema[i].type, out + i, nullptr, 0, n->schema[i].is_ts);
+            t->cols[i].c.valid = ov + i;
+            t->cols[i].c.nullable = true;
+        }
+        return FLOCKGPU_OK;
+    }
+
     int exec_aggregate(const Node *n, Table *t) {
         const Node *partial = nullptr;
         if (final_is_identity(n, &partial)) {
@@ -2725,6 +2935,7 @@ struct Exec {
             }
             return FLOCKGPU_OK;
         }
+        if (n->group.empty() && !ir::lone_integer_max(n)) return exec_global_aggregate(n, t);
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
         const bool is_final = n->mode != "Partial";

@@ -109,6 +109,7 @@ struct Agg {
 // State columns a Partial stage emits per aggregate, as DataFusion ~6 lays them out (Accumulator::state / state_fields,
 // SURVEY.md appendix D): COUNT -> [count UInt64]; MAX / MIN / SUM -> [value]; AVG -> [count UInt64, sum Float64].
 inline int agg_state_cols(const std::string &fn) { return fn == "avg" ? 2 : 1; }
+constexpr int kMaxUngroupedAccumulators = 8;   // of one aggregate without GROUP BY (AVG takes two)
 // key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
 constexpr int kMaxJoinPairs = 8;
 // One column of a WindowAggExec: ROW_NUMBER(), or an aggregate over the default frame (RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: the
@@ -152,6 +153,21 @@ struct Node {
     std::vector<WinExpr> win;       // Window: one per window column (they come FIRST in the schema)
     std::vector<char> required;     // per output column: needed by an ancestor (or by the plan output)
 };
+
+// Aggregate without GROUP BY: a lone MAX over one integer column (q5 / q7's MAX(num)) keeps the path and the feed-time NULL dropping it has had
+// from the start; every other list of aggregates is one streaming pass (reduce.hpp).
+inline bool lone_integer_max(const Node *n) {
+    if (!n->group.empty() || n->aggs.size() != 1 || n->aggs[0].fn != "max" || n->aggs[0].arg < 0 || n->in.empty()) return false;
+    const std::vector<Field> &sch = n->in[0]->schema;
+    if ((size_t)n->aggs[0].arg >= sch.size()) return false;
+    const ColType at = sch[(size_t)n->aggs[0].arg].type;
+    return at != ColType::UTF8 && at != ColType::F64;
+}
+inline int ungrouped_accumulators(const Node *n) {
+    int accs = 0;
+    for (auto &a : n->aggs) accs += agg_state_cols(a.fn);
+    return accs;
+}
 
 struct Leaf {
     std::vector<Field> schema;  // the columns the MemoryExec scans (after its projection)
@@ -692,6 +708,17 @@ struct Builder {
                     }
                     n->aggs.push_back(a);
                 }
+            // no GROUP BY (reduce.hpp): the argument types of the GROUP BY path, refused in its words; up to eight accumulators (AVG takes two)
+            if (n->group.empty()) {
+                int accs = 0;
+                for (auto &a : n->aggs) {
+                    accs += agg_state_cols(a.fn);
+                    if (a.arg < 0) continue;
+                    const ColType at = in->schema[(size_t)a.arg].type;
+                    if (at == ColType::UTF8 || (at == ColType::F64 && (a.fn == "sum" || a.fn == "avg"))) { fail(a.fn + " needs an integer column"); return nullptr; }
+                }
+                if (accs > kMaxUngroupedAccumulators) { fail("more than " + std::to_string(kMaxUngroupedAccumulators) + " accumulators in one ungrouped aggregate"); return nullptr; }
+            }
             n->in.push_back(std::move(in));
         } else if (t == "hash_join_exec") {
             n->kind = NKind::Join;
@@ -1093,9 +1120,16 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
         }
         case NKind::Aggregate: {
             std::vector<char> d(n->in[0]->schema.size(), 0);
-            if (n->group.empty())  // MAX ignores NULLs; over nothing but NULLs it is NULL, as over no rows
-                for (auto &a : n->aggs)
-                    if (a.fn == "max" && a.arg >= 0) d[(size_t)a.arg] = 1;
+            if (lone_integer_max(n)) {  // MAX ignores NULLs; over nothing but NULLs it is NULL, as over no rows
+                d[(size_t)n->aggs[0].arg] = 1;
+            } else if (n->group.empty() && !n->aggs.empty()) {
+                // every other list: a row may go only when EVERY aggregate skips it -- all of them take this one column (COUNT(*) counts the
+                // row whatever it holds; SUM(a), COUNT(b) would lose b's row with a's NULL).  Otherwise the column travels with validity bytes.
+                const int c = n->aggs[0].arg;
+                bool all = c >= 0;
+                for (auto &a : n->aggs) all = all && a.arg == c && a.arg2 < 0;
+                if (all) d[(size_t)c] = 1;
+            }
             mark_null_droppable(p, n->in[0].get(), d);
             break;
         }

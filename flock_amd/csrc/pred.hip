@@ -364,26 +364,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kFull ? 
 
 namespace flockgpu {
 
-int pred_to_rows(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, int32_t **out_rows, int64_t *n_out) {
+namespace {
+// The predicate pass alone: flag words and wave counts of the relation's tiles (one segment from row 0: tile t = rows [8192 t, 8192 (t + 1))).
+int pred_flag_pass(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, SegTiles *tiles, uint32_t **out_flags, uint32_t **out_counts) {
     const std::string base = name;
-    int32_t *o_rows = nullptr;
-    FG_TRY(arena_get_t(ctx, (base + ".rows").c_str(), (size_t)std::max<int64_t>(rows, 0) + 4, &o_rows));
-    *out_rows = o_rows;
-    *n_out = 0;
-    if (rows <= 0) return FLOCKGPU_OK;
     if (rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^31 rows", name);
     if (prog.n_ops < 1 || prog.max_stack > kPredMaxStack) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: malformed predicate program", name);
     int64_t sb = 0, se = rows;
     SegTiles st;
     FG_TRY(build_seg_tiles(ctx, (base + ".tiles").c_str(), &sb, &se, 1, kFlagTile, &st));
     uint32_t *flags = nullptr, *counts = nullptr;
-    uint64_t *tile_base = nullptr;
-    int64_t *h_off = nullptr;
     FG_TRY(arena_get_t(ctx, (base + ".flags").c_str(), (size_t)st.n_tiles * kBlock + 4, &flags));
     FG_TRY(arena_get_t(ctx, (base + ".counts").c_str(), (size_t)st.n_tiles * kWavesPerBlock + 4, &counts));
-    FG_TRY(arena_get_t(ctx, (base + ".base").c_str(), (size_t)st.n_tiles + 1, &tile_base));
-    FG_TRY(pinned_get_t(ctx, (base + ".off").c_str(), 2, &h_off));
-    pinned_pending(reinterpret_cast<uint64_t *>(h_off), 2);   // (wait_pinned below)
+    *tiles = st;
+    *out_flags = flags;
+    *out_counts = counts;
     bool wide = false, words = false;
     for (int i = 0; i < prog.n_leaves; ++i) {
         const PredLeafDesc &l = prog.leaves[i];
@@ -418,7 +413,38 @@ int pred_to_rows(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, i
         if (n_full > 0) launch(true, false, dim3((unsigned)n_full), 0);
         if (st.n_tiles > n_full) launch(false, false, dim3((unsigned)(st.n_tiles - n_full)), n_full);
     }
-    FG_TRY(check_launch(ctx, "pred_flag_kernel"));
+    return check_launch(ctx, "pred_flag_kernel");
+}
+}  // namespace
+
+int pred_to_flags(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, const uint32_t **flag_words, const uint32_t **wave_counts, int32_t *n_tiles) {
+    *flag_words = *wave_counts = nullptr;
+    *n_tiles = 0;
+    if (rows <= 0) return FLOCKGPU_OK;
+    SegTiles st;
+    uint32_t *flags = nullptr, *counts = nullptr;
+    FG_TRY(pred_flag_pass(ctx, name, prog, rows, &st, &flags, &counts));
+    *flag_words = flags;
+    *wave_counts = counts;
+    *n_tiles = st.n_tiles;
+    return FLOCKGPU_OK;
+}
+
+int pred_to_rows(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, int32_t **out_rows, int64_t *n_out) {
+    const std::string base = name;
+    int32_t *o_rows = nullptr;
+    FG_TRY(arena_get_t(ctx, (base + ".rows").c_str(), (size_t)std::max<int64_t>(rows, 0) + 4, &o_rows));
+    *out_rows = o_rows;
+    *n_out = 0;
+    if (rows <= 0) return FLOCKGPU_OK;
+    SegTiles st;
+    uint32_t *flags = nullptr, *counts = nullptr;
+    uint64_t *tile_base = nullptr;
+    int64_t *h_off = nullptr;
+    FG_TRY(pred_flag_pass(ctx, name, prog, rows, &st, &flags, &counts));
+    FG_TRY(arena_get_t(ctx, (base + ".base").c_str(), (size_t)st.n_tiles + 1, &tile_base));
+    FG_TRY(pinned_get_t(ctx, (base + ".off").c_str(), 2, &h_off));
+    pinned_pending(reinterpret_cast<uint64_t *>(h_off), 2);   // (wait_pinned below)
     if (st.n_tiles <= 2048) {   // a relation of up to 1.7e7 rows: the emit sums the lower tiles' counts itself (one launch less; 16 B per lower tile from L2)
         FG_TRY(emit_flagged_rows_self(ctx, st, flags, counts, o_rows, h_off));
     } else {

@@ -97,5 +97,8 @@ struct PredBuilder {
 
 // rows of [0, rows) the program keeps, in input order.  *out_rows: ctx-owned (arena key `name`); n_out through ONE synchronisation.
 int pred_to_rows(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, int32_t **out_rows, int64_t *n_out);
+// The predicate pass alone, for a consumer that reads the rows under the flags instead of a row list (reduce.hpp): one flag word per lane and
+// tile (bit it * 4 + j, scan.hpp "flag tiles"; tile t = rows [8192 t, 8192 (t + 1))) and one count per wave.  Launches only.  No rows: nulls, 0 tiles.
+int pred_to_flags(flockgpu_ctx *ctx, const char *name, const PredProgram &prog, int64_t rows, const uint32_t **flag_words, const uint32_t **wave_counts, int32_t *n_tiles);
 
 }  // namespace flockgpu

@@ -704,4 +704,34 @@ int valprog_to_rows(flockgpu_ctx *ctx, const char *name, const ValProgram &prog,
     return FLOCKGPU_OK;
 }
 
+int valprog_to_flags(flockgpu_ctx *ctx, const char *name, const ValProgram &prog, int64_t rows, const uint32_t **flag_words, const uint32_t **wave_counts, int32_t *n_tiles) {
+    *flag_words = *wave_counts = nullptr;
+    *n_tiles = 0;
+    if (prog.n_ops < 1 || prog.max_stack > kValMaxStack) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: malformed expression program", name);
+    if (rows <= 0) return FLOCKGPU_OK;
+    if (rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^31 rows", name);
+    const std::string base = name;
+    const int32_t tiles = (int32_t)div_up(rows, (int64_t)kFlagTile);
+    uint32_t *flags = nullptr, *counts = nullptr, *d_err = nullptr, *h_err = nullptr;
+    FG_TRY(arena_get_t(ctx, (base + ".flags").c_str(), (size_t)tiles * kBlock + 4, &flags));
+    FG_TRY(arena_get_t(ctx, (base + ".counts").c_str(), (size_t)tiles * kWavesPerBlock + 4, &counts));
+    FG_TRY(arena_get_t(ctx, (base + ".err").c_str(), 4, &d_err));
+    FG_TRY(pinned_get_t(ctx, (base + ".err").c_str(), 4, &h_err));
+    FG_TRY(fill_words(ctx, FillList().add(d_err, 0u, 1)));
+    const unsigned grid = (unsigned)std::min<int64_t>(tiles, (int64_t)ctx->num_cus * 8);
+    {
+        LaunchScope ls(ctx, "valprog_kernel");
+        launch<true>(ctx, prog, grid, rows, tiles, nullptr, nullptr, 0, flags, counts, d_err);
+    }
+    FG_TRY(check_launch(ctx, "valprog_kernel"));
+    pinned_pending32(h_err, 1);
+    FG_TRY(publish_words(ctx, PublishList().add(h_err, d_err, 1)));
+    FG_TRY(wait_pinned32(ctx, h_err, 1));
+    FG_TRY(report(ctx, name, *h_err));
+    *flag_words = flags;
+    *wave_counts = counts;
+    *n_tiles = tiles;
+    return FLOCKGPU_OK;
+}
+
 }  // namespace flockgpu

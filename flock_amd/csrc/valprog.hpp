@@ -203,6 +203,9 @@ int valprog_to_column(flockgpu_ctx *ctx, const char *name, const ValProgram &pro
 // FilterExec: the rows where the BOOL result is TRUE (FALSE and NULL: dropped), in order -- flag words + wave counts from the evaluating
 // kernel itself, then the scan / emit of pred_to_rows.  One host wait (row count + error word).
 int valprog_to_rows(flockgpu_ctx *ctx, const char *name, const ValProgram &prog, int64_t rows, int32_t **out_rows, int64_t *n_out);
+// The predicate form's flag words and wave counts alone (pred.hpp pred_to_flags), for a consumer that reads the rows under them.  One host wait:
+// the error word (a division by zero voids the call).
+int valprog_to_flags(flockgpu_ctx *ctx, const char *name, const ValProgram &prog, int64_t rows, const uint32_t **flag_words, const uint32_t **wave_counts, int32_t *n_tiles);
 // octet_length / char_length of a Utf8 column (A-F7; strlen.hip): one Int32 per row in an arena buffer called `name`, NULL rows included (their bytes are
 // whatever the column holds: the consumer reads the source's validity).  No host wait.
 int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out);

@@ -84,7 +84,8 @@ typedef struct flockgpu_plan flockgpu_plan;
 /* Parses the plan JSON and builds the operator tree.  FLOCKGPU_ERR_PLAN: not JSON; FLOCKGPU_ERR_UNSUPPORTED: a node,
  * expression or type the engine does not execute (flockgpu_last_error names it).
  * Nodes (`execution_plan` tags): memory_exec, filter_exec, projection_exec, hash_aggregate_exec (Partial / Final / FinalPartitioned: count, max, min,
- * sum, avg), hash_join_exec (Inner; Semi / Anti: the left input's rows that have / lack a partner, left schema), repartition_exec, coalesce_batches_exec / coalesce_partitions_exec / merge_exec (transparent), sort_exec,
+ * sum, avg; without GROUP BY any list of them over Int32 / Int64 / UInt64 / Timestamp / Float64 columns -- SUM / AVG of integer columns only, up to
+ * eight accumulators, AVG taking two -- gives exactly one row in every mode, also over no rows), hash_join_exec (Inner; Semi / Anti: the left input's rows that have / lack a partner, left schema), repartition_exec, coalesce_batches_exec / coalesce_partitions_exec / merge_exec (transparent), sort_exec,
  * global_limit_exec / local_limit_exec, window_agg_exec (ROW_NUMBER()).
  * Expressions (`physical_expr` tags): column, literal, cast_expr, try_cast_expr, binary_expr (Eq NotEq Lt LtEq Gt GtEq And Or Plus Minus
  * Multiply Divide Modulo), not_expr, is_null_expr, is_not_null_expr, negative_expr, in_list_expr, case_expr -- over Int32 / Int64 / UInt64 /
@@ -131,7 +132,7 @@ int flockgpu_plan_output_partitions(const flockgpu_plan *plan);
  * NULLs in projected / joined-along columns come back as NULLs (validity bitmap + null_count on the exported arrays).  The fused
  * NEXMark pipelines read plain columns: an invocation whose leaf holds such NULLs runs on the generic operators.  Handed back
  * as FLOCKGPU_ERR_UNSUPPORTED at execute: NULLs in a two-column GROUP BY key, in DISTINCT
- * columns, in a computed join key; FLOCKGPU_ERR_UNSUPPORTED at feed: such NULLs on the q5 plan with an open pane ring (its ring keeps
+ * columns, in a computed key of a two-pair Int32 join (a one-pair join drops such a side's NULL-keyed rows itself); FLOCKGPU_ERR_UNSUPPORTED at feed: such NULLs on the q5 plan with an open pane ring (its ring keeps
  * Partial COUNT groups of plain columns; every other plan's ring keeps rows, validity included). */
 int flockgpu_plan_feed(flockgpu_plan *plan, int input, const struct ArrowSchema *schema,
                        const struct ArrowArray *const *batches, int n_batches);
