@@ -269,15 +269,15 @@ bool is_bin(const Expr *e, const char *op) { return e && e->kind == EKind::Bin &
 struct LogicalAgg {
     const Node *below = nullptr;
     std::vector<int> group;
-    std::vector<std::string> fns;
+    std::vector<AggFn> fns;
     std::vector<int> args;
 };
 bool logical_agg(const Node *n, LogicalAgg *out) {
     if (n->kind != NKind::Aggregate) return false;
     const Node *low = n;
-    if (n->mode != "Partial") {
+    if (n->mode != AggMode::Partial) {
         Peeled p = peel(n->in[0].get());
-        if (p.n->kind == NKind::Aggregate && p.n->mode == "Partial" && p.n->group.size() == n->group.size() && p.n->aggs.size() == n->aggs.size()) {
+        if (p.n->kind == NKind::Aggregate && p.n->mode == AggMode::Partial && p.n->group.size() == n->group.size() && p.n->aggs.size() == n->aggs.size()) {
             // the final stage must read the partial stage's columns in place
             for (size_t g = 0; g < n->group.size(); ++g)
                 if (p.map[(size_t)n->group[g]] != (int)g) return false;
@@ -321,11 +321,11 @@ struct WinningBids {
 };
 bool match_winning_bids(const Node *agg, bool with_category, WinningBids *w) {
     LogicalAgg la;
-    if (!logical_agg(agg, &la) || la.fns != std::vector<std::string>{"max"} || la.group.size() != (with_category ? 2u : 1u)) return false;
+    if (!logical_agg(agg, &la) || la.fns != std::vector<AggFn>{AggFn::Max} || la.group.size() != (with_category ? 2u : 1u)) return false;
     Peeled pf = peel(la.below);
     if (pf.n->kind != NKind::Filter) return false;
     Peeled pj = peel(pf.n->in[0].get());
-    if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on_l2 >= 0) return false;
+    if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on.size() != 1) return false;
     const Node *J = pj.n;
     const int nl = (int)J->in[0]->schema.size();
     auto to_join = [&](int below_col) {  // column of la.below -> column of the join's output
@@ -352,16 +352,16 @@ bool match_winning_bids(const Node *agg, bool with_category, WinningBids *w) {
     if (x < 0 || lo < 0 || hi < 0) return false;
     x = pj.map[(size_t)x]; lo = pj.map[(size_t)lo]; hi = pj.map[(size_t)hi];
     const int key = to_join(la.group[0]), cat = with_category ? to_join(la.group[1]) : -1, price = to_join(la.args[0]);
-    if (x < nl || lo < 0 || lo >= nl || hi < 0 || hi >= nl || price < nl || key != J->on_l || (with_category && (cat < 0 || cat >= nl))) return false;
+    if (x < nl || lo < 0 || lo >= nl || hi < 0 || hi >= nl || price < nl || key != J->on[0].l || (with_category && (cat < 0 || cat >= nl))) return false;
     std::vector<int> lmap, rmap;
     w->auction_scan = as_scan(J->in[0].get(), &lmap);
     w->bid_scan = as_scan(J->in[1].get(), &rmap);
     if (!w->auction_scan || !w->bid_scan) return false;
-    w->a_id = lmap[(size_t)J->on_l];
+    w->a_id = lmap[(size_t)J->on[0].l];
     w->a_dt = lmap[(size_t)lo];
     w->a_exp = lmap[(size_t)hi];
     w->a_cat = with_category ? lmap[(size_t)cat] : -1;
-    w->b_auction = rmap[(size_t)J->on_r];
+    w->b_auction = rmap[(size_t)J->on[0].r];
     w->b_price = rmap[(size_t)(price - nl)];
     w->b_dt = rmap[(size_t)(x - nl)];
     auto is = [](const Node *scan, int c, ColType t, bool ts) { return c >= 0 && scan->schema[(size_t)c].type == t && scan->schema[(size_t)c].is_ts == ts; };
@@ -406,7 +406,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         // ---- Partial COUNT GROUP BY one Int32 column of a scan (stage 0 of q5.dag)
         std::vector<int> map;
         const Node *scan = as_scan(n->in[0].get(), &map);
-        if (scan && n->mode == "Partial" && n->group.size() == 1 && n->aggs.size() == 1 && n->aggs[0].fn == "count" &&
+        if (scan && n->mode == AggMode::Partial && n->group.size() == 1 && n->aggs.size() == 1 && n->aggs[0].fn == AggFn::Count &&
             n->in[0]->schema[(size_t)n->group[0]].type == ColType::I32 && map[(size_t)n->group[0]] >= 0) {
             fi.kind = kPartialCount;
             fi.leaf_a = scan->leaf;
@@ -415,9 +415,9 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
             return;
         }
         LogicalAgg top;
-        if (n->mode == "Partial" || !logical_agg(n, &top) || top.group.size() != 1 || top.fns.size() != 1) return;
+        if (n->mode == AggMode::Partial || !logical_agg(n, &top) || top.group.size() != 1 || top.fns.size() != 1) return;
         // ---- q4: AVG(final) GROUP BY category over Q (q4.sql; planner.rs:218-256)
-        if (top.fns[0] == "avg") {
+        if (top.fns[0] == AggFn::Avg) {
             Peeled pq = peel(top.below);
             WinningBids w;
             if (match_winning_bids(pq.n, true, &w) && pq.map[(size_t)top.group[0]] == 1 && pq.map[(size_t)top.args[0]] == 2) {
@@ -432,9 +432,9 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         }
         // ---- YSB: COUNT(*) GROUP BY campaign_id over Filter(event_type = lit)(ad_event) JOIN campaign ON ad_id = c_ad_id
         // (ysb.sql; planner.rs:298-346)
-        if (top.fns[0] == "count" && top.below->schema[(size_t)top.group[0]].type == ColType::UTF8) {
+        if (top.fns[0] == AggFn::Count && top.below->schema[(size_t)top.group[0]].type == ColType::UTF8) {
             Peeled pj = peel(top.below);
-            if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on_l2 >= 0) return;
+            if (pj.n->kind != NKind::Join || pj.n->join_type != JoinType::Inner || pj.n->on.size() != 1) return;
             const Node *J = pj.n;
             const int nl = (int)J->in[0]->schema.size();
             Peeled pl_ = peel(J->in[0].get());
@@ -445,9 +445,9 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
             const Expr *p = pl_.n->pred.get();
             if (!ls || !is_bin(p, "Eq") || p->l->kind != EKind::Col || p->r->kind != EKind::LitS || p->r->s.size() > 40) return;
             const int grp = pj.map[(size_t)top.group[0]];
-            const int ev_key = pl_.map[(size_t)J->on_l];
+            const int ev_key = pl_.map[(size_t)J->on[0].l];
             if (grp < nl || ev_key < 0) return;
-            const int ad = lmap[(size_t)ev_key], ty = lmap[(size_t)p->l->col], cad = rmap[(size_t)J->on_r], camp = rmap[(size_t)(grp - nl)];
+            const int ad = lmap[(size_t)ev_key], ty = lmap[(size_t)p->l->col], cad = rmap[(size_t)J->on[0].r], camp = rmap[(size_t)(grp - nl)];
             auto text = [](const Node *scan, int c) { return c >= 0 && scan->schema[(size_t)c].type == ColType::UTF8; };
             if (!text(ls, ad) || !text(ls, ty) || !text(rs, cad) || !text(rs, camp)) return;
             fi.kind = kYsb;
@@ -463,9 +463,10 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
     if (n->kind != NKind::Join || n->join_type != JoinType::Inner) return;   // (a Semi / Anti look-alike of q3 / q8 / q9 runs on the generic operators)
     const Node *L = n->in[0].get(), *R = n->in[1].get();
     const size_t nl = L->schema.size();
-    const Field &lk = L->schema[(size_t)n->on_l], &rk = R->schema[(size_t)n->on_r];
-    if (!n->on_lx.empty()) return;   // (more than two key pairs: no fused pipeline reads a third one)
-    if (n->on_l2 >= 0) {
+    const KeyPair on = n->on[0];
+    const Field &lk = L->schema[(size_t)on.l], &rk = R->schema[(size_t)on.r];
+    if (n->on.size() > 2) return;   // (more than two key pairs: no fused pipeline reads a third one)
+    if (n->on.size() == 2) {
         // ---- q9: bid JOIN Q ON auction = id AND price = final (q9.sql, q9_plan.fmt)
         std::vector<int> lmap;
         const Node *ls = as_scan(L, &lmap);
@@ -478,7 +479,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         for (int i = 0; ok && i < 4; ++i)
             ok = bs[(size_t)i].name == names[i] && lmap[(size_t)i] == i && n->required[(size_t)i] && bs[(size_t)i].type == (i == 3 ? ColType::I64 : ColType::I32);
         // the pairs in either order: (auction, id = the group key) and (price, final = the maximum)
-        int k_auction = n->on_l, k_id = pr.map[(size_t)n->on_r], k_price = n->on_l2, k_final = pr.map[(size_t)n->on_r2];
+        int k_auction = on.l, k_id = pr.map[(size_t)on.r], k_price = n->on[1].l, k_final = pr.map[(size_t)n->on[1].r];
         if (k_auction == 2) { std::swap(k_auction, k_price); std::swap(k_id, k_final); }
         ok = ok && k_auction == 0 && k_price == 2 && k_id == 0 && k_final == 1;
         // the inner bid scan must be the same relation (the SQL scans `bid` twice)
@@ -535,7 +536,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
                     }
                 }
                 ok = ok && texts.size() <= 2;
-                const int lkey = pl_.map[(size_t)n->on_l], rkey = pr.map[(size_t)n->on_r];
+                const int lkey = pl_.map[(size_t)on.l], rkey = pr.map[(size_t)on.r];
                 ok = ok && lkey >= 0 && rkey >= 0;
                 if (ok) {
                     if (a_id < 0) a_id = lkey;
@@ -572,7 +573,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
         if (logical_agg(pl_.n, &la) && logical_agg(pr.n, &ra) && la.fns.empty() && ra.fns.empty() && la.group.size() == 2 && ra.group.size() == 1) {
             std::vector<int> lmap, rmap;
             const Node *ls = as_scan(la.below, &lmap), *rs = as_scan(ra.below, &rmap);
-            const int lkey = pl_.map[(size_t)n->on_l], rkey = pr.map[(size_t)n->on_r];
+            const int lkey = pl_.map[(size_t)on.l], rkey = pr.map[(size_t)on.r];
             if (ls && rs && lkey == 0 && rkey == 0 && la.below->schema[(size_t)la.group[0]].type == ColType::I32 &&
                 la.below->schema[(size_t)la.group[1]].type == ColType::UTF8 && ra.below->schema[(size_t)ra.group[0]].type == ColType::I32 &&
                 lmap[(size_t)la.group[0]] >= 0 && lmap[(size_t)la.group[1]] >= 0 && rmap[(size_t)ra.group[0]] >= 0) {
@@ -600,16 +601,16 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
     {
         Peeled pl_ = peel(L), pr = peel(R);
         LogicalAgg cnt, mx, cnt2;
-        if (logical_agg(pl_.n, &cnt) && cnt.group.size() == 1 && cnt.fns == std::vector<std::string>{"count"} && logical_agg(pr.n, &mx) &&
-            mx.group.empty() && mx.fns == std::vector<std::string>{"max"}) {
+        if (logical_agg(pl_.n, &cnt) && cnt.group.size() == 1 && cnt.fns == std::vector<AggFn>{AggFn::Count} && logical_agg(pr.n, &mx) &&
+            mx.group.empty() && mx.fns == std::vector<AggFn>{AggFn::Max}) {
             Peeled below = peel(mx.below);
             std::vector<int> lmap, rmap;
             const Node *ls = as_scan(cnt.below, &lmap);
-            if (ls && logical_agg(below.n, &cnt2) && cnt2.group.size() == 1 && cnt2.fns == std::vector<std::string>{"count"} &&
+            if (ls && logical_agg(below.n, &cnt2) && cnt2.group.size() == 1 && cnt2.fns == std::vector<AggFn>{AggFn::Count} &&
                 below.map[(size_t)mx.args[0]] == 1 /* MAX over the count column */) {
                 const Node *rs = as_scan(cnt2.below, &rmap);
-                const int lkey = pl_.map[(size_t)n->on_l];
-                if (rs && lkey == 1 && pr.map[(size_t)n->on_r] == 0 && cnt.below->schema[(size_t)cnt.group[0]].type == ColType::I32 &&
+                const int lkey = pl_.map[(size_t)on.l];
+                if (rs && lkey == 1 && pr.map[(size_t)on.r] == 0 && cnt.below->schema[(size_t)cnt.group[0]].type == ColType::I32 &&
                     lmap[(size_t)cnt.group[0]] >= 0 && rmap[(size_t)cnt2.group[0]] >= 0 &&
                     leaf_schema(ls)[(size_t)lmap[(size_t)cnt.group[0]]].name == leaf_schema(rs)[(size_t)rmap[(size_t)cnt2.group[0]]].name) {
                     bool ok = true;
@@ -653,7 +654,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
             Peeled pr = peel(R);
             LogicalAgg mx;
             const bool all_bid = n->required[0] && n->required[1] && n->required[2] && n->required[3];  // the entry points read all four
-            if (all_bid && n->on_l == 2 && logical_agg(pr.n, &mx) && mx.group.empty() && mx.fns == std::vector<std::string>{"max"} && pr.map[(size_t)n->on_r] == 0) {
+            if (all_bid && on.l == 2 && logical_agg(pr.n, &mx) && mx.group.empty() && mx.fns == std::vector<AggFn>{AggFn::Max} && pr.map[(size_t)on.r] == 0) {
                 const Node *rs = as_scan(mx.below, &rmap);
                 if (rs && rmap[(size_t)mx.args[0]] >= 0 && leaf_schema(rs)[(size_t)rmap[(size_t)mx.args[0]]].name == "price" &&
                     leaf_schema(rs)[(size_t)rmap[(size_t)mx.args[0]]].type == ColType::I32) {
@@ -665,7 +666,7 @@ void recognise_fused(flockgpu_plan *pl, const Node *n) {
                 }
             }
             const Node *rs = as_scan(R, &rmap);
-            if (all_bid && n->required.size() == 6 && n->required[5] && n->on_l == 0 && rs && names_are(rs, {"key", "value"}) && n->on_r == 0 && rmap == std::vector<int>{0, 1} &&
+            if (all_bid && n->required.size() == 6 && n->required[5] && on.l == 0 && rs && names_are(rs, {"key", "value"}) && on.r == 0 && rmap == std::vector<int>{0, 1} &&
                 leaf_schema(rs)[0].type == ColType::I32 && leaf_schema(rs)[1].type == ColType::I32) {
                 fi.kind = kQ13;
                 fi.leaf_a = ls->leaf;
@@ -767,7 +768,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Join && n->join_type == JoinType::Semi) kind = "SemiJoin";
     if (n->kind == NKind::Join && n->join_type == JoinType::Anti) kind = "AntiJoin";
     os << std::string((size_t)depth * 2, ' ') << kind;
-    if (n->kind == NKind::Aggregate) os << "(" << n->mode << ")";
+    if (n->kind == NKind::Aggregate) os << "(" << agg_mode_name(n->mode) << ")";
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
@@ -790,7 +791,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
         for (size_t w = 0; w < n->win.size(); ++w) {
             const WinExpr &x = n->win[w];
             const auto &ins = n->in[0]->schema;
-            std::string fn = x.fn;
+            std::string fn = agg_fn_name(x.fn);
             for (auto &ch : fn) ch = (char)std::toupper((unsigned char)ch);
             os << (w ? ", " : "(");
             if (x.row_number) os << "ROW_NUMBER";
@@ -869,18 +870,18 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     for (size_t i = 0; i < n->schema.size(); ++i)
         *o += n->schema[i].name + "/" + std::to_string((int)n->schema[i].type) + (n->schema[i].is_ts ? "t" : "") + (n->schema[i].nullable ? "?" : "") +
               (!top && i < n->required.size() && n->required[i] ? "!" : "") + ",";   // (an Aggregate computes every output column: its own `required` does not matter)
-    *o += "|" + n->mode + "|";
+    *o += "|" + std::to_string((int)n->mode) + "|";
     for (int c : n->group) *o += std::to_string(c) + ",";
-    for (auto &a : n->aggs) *o += a.fn + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
-    *o += "|" + std::to_string(n->on_l) + "," + std::to_string(n->on_r) + "," + std::to_string(n->on_l2) + "," + std::to_string(n->on_r2) + (n->join_partitioned ? "p" : "") +
-          (n->join_type == JoinType::Semi ? "s" : n->join_type == JoinType::Anti ? "a" : "") + "|";
-    for (size_t k = 0; k < n->on_lx.size(); ++k) *o += std::to_string(n->on_lx[k]) + "=" + std::to_string(n->on_rx[k]) + ",";   // (pairs after the second)
+    for (auto &a : n->aggs) *o += std::to_string((int)a.fn) + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
+    *o += "|";
+    for (auto &k : n->on) *o += std::to_string(k.l) + "=" + std::to_string(k.r) + ",";   // (every key pair)
+    *o += std::string(n->join_partitioned ? "p" : "") + (n->join_type == JoinType::Semi ? "s" : n->join_type == JoinType::Anti ? "a" : "") + "|";
     for (int c : n->hash_cols) *o += std::to_string(c) + ",";
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
     for (auto &k : n->sort_cols) *o += std::to_string(k.col) + (k.descending ? "d" : "a") + (k.nulls_first ? "f" : "l") + ",";
     *o += std::to_string(n->limit) + "|";
     for (auto &x : n->win) {   // (Window: each column's function, argument, PARTITION BY and ORDER BY)
-        *o += (x.row_number ? std::string("rn") : x.fn + "." + std::to_string(x.arg) + "." + std::to_string((int)x.type)) + ":";
+        *o += (x.row_number ? std::string("rn") : std::to_string((int)x.fn) + "." + std::to_string(x.arg) + "." + std::to_string((int)x.type)) + ":";
         for (int c : x.part) *o += std::to_string(c) + ",";
         *o += "/";
         for (auto &k : x.order) *o += std::to_string(k.col) + ",";
@@ -1608,7 +1609,7 @@ struct Exec {
         return b.push(v ? PredOpKind::Or : PredOpKind::And) ? FLOCKGPU_OK : pred_full();
     }
     // A leaf whose TRUE bits a kernel of its own writes (strmatch.hip): launched here, read by the program's Words leaf
-    const Node *words_node = nullptr;   // the filter being compiled (filter_rows)
+    const Node *words_node = nullptr;   // the filter being compiled (compile_filter)
     int words_used = 0;
     int pred_words(const TCol *col, const StrPattern &sp, PredBuilder &b) {
         if (!words_node) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a string-match leaf outside a filter");
@@ -1799,10 +1800,7 @@ struct Exec {
             *mx = it->second.mx;
             return FLOCKGPU_OK;
         }
-        DevColumn c;
-        c.type = type;
-        c.values = values;
-        FG_TRY(column_minmax(ctx, c, rows, mn, mx));
+        FG_TRY(column_minmax(ctx, plain_col(type, values), rows, mn, mx));
         pl->col_stats[values] = flockgpu_plan::ColStat{rows, *mn, *mx};
         return FLOCKGPU_OK;
     }
@@ -1822,7 +1820,6 @@ struct Exec {
         return widen_to_i64(ctx, c.c, rows, *out);
     }
 
-    // FilterExec as a row selection: the input table and the rows of it the predicate keeps (input order)
     // ---- the general expression evaluator (valprog.hpp): an expression tree -> its postfix program over the columns of `in`
     int val_unsupported(const char *what) { return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s", what); }
     int val_full() { return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: expression too large for one program (%d operators, %d columns, %d constants, depth %d)", kValMaxOps, kValMaxCols, kValMaxConsts, kValMaxStack); }
@@ -2033,44 +2030,42 @@ struct Exec {
         return val_unsupported("an expression of an unknown kind");
     }
 
-    int filter_rows(const Node *n, Table *in, int32_t **rows, int64_t *n_out) {
+    // A filter's input table and its predicate compiled for it: the one-pass program of pred.hpp (*general = false, `b`), or -- a predicate that
+    // program has no leaf for (arithmetic inside a comparison, CASE, casts of computed values) -- the general evaluator's (*general = true, `vb`),
+    // which writes the same flag words + wave counts
+    int compile_filter(const Node *n, Table *in, PredBuilder &b, ValBuilder &vb, bool *general) {
         FG_TRY(exec(n->in[0].get(), in));
-        PredBuilder b;
         words_node = n;
         words_used = 0;
         col_rows = in->rows;
         const int rc = compile_pred(n->pred.get(), *in, b);
         words_node = nullptr;
-        if (rc == FLOCKGPU_OK) return pred_to_rows(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, rows, n_out);
-        if (rc != FLOCKGPU_ERR_UNSUPPORTED) return rc;
-        // a predicate the one-pass program has no leaf for (arithmetic inside a comparison, CASE, casts of computed values): the general
-        // evaluator writes the same flag words + wave counts, which go through the same scan -> emit
-        ValBuilder vb;
+        *general = rc == FLOCKGPU_ERR_UNSUPPORTED;
+        if (!*general) return rc;
         int vt = -1;
         bool may_null = false;
         FG_TRY(val_compile(n->pred.get(), *in, vb, 5, &vt, &may_null));
         if (vt != 5) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a filter predicate that is not Boolean");
-        return valprog_to_rows(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, rows, n_out);
+        return FLOCKGPU_OK;
     }
-
+    // FilterExec as a row selection: the input table and the rows of it the predicate keeps (input order) -- flags, scan, emit
+    int filter_rows(const Node *n, Table *in, int32_t **rows, int64_t *n_out) {
+        PredBuilder b;
+        ValBuilder vb;
+        bool general = false;
+        FG_TRY(compile_filter(n, in, b, vb, &general));
+        if (general) return valprog_to_rows(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, rows, n_out);
+        return pred_to_rows(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, rows, n_out);
+    }
     // The filter's predicate pass alone: flag words and wave counts over its INPUT table (pred.hpp pred_to_flags), for an ungrouped aggregate that
     // reads the input columns under them -- no scan, no emit, no take.
     int filter_flags(const Node *n, Table *in, const uint32_t **flags, const uint32_t **counts, int32_t *tiles) {
-        FG_TRY(exec(n->in[0].get(), in));
         PredBuilder b;
-        words_node = n;
-        words_used = 0;
-        col_rows = in->rows;
-        const int rc = compile_pred(n->pred.get(), *in, b);
-        words_node = nullptr;
-        if (rc == FLOCKGPU_OK) return pred_to_flags(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, flags, counts, tiles);
-        if (rc != FLOCKGPU_ERR_UNSUPPORTED) return rc;
         ValBuilder vb;
-        int vt = -1;
-        bool may_null = false;
-        FG_TRY(val_compile(n->pred.get(), *in, vb, 5, &vt, &may_null));
-        if (vt != 5) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a filter predicate that is not Boolean");
-        return valprog_to_flags(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, flags, counts, tiles);
+        bool general = false;
+        FG_TRY(compile_filter(n, in, b, vb, &general));
+        if (general) return valprog_to_flags(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, flags, counts, tiles);
+        return pred_to_flags(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, flags, counts, tiles);
     }
 
     // A FilterExec directly under a join (round 6): the filter's surviving rows as a ROW LIST over its input table -- nothing is taken yet.  The
@@ -2152,6 +2147,16 @@ struct Exec {
         z->rows = z->base.rows;
         return FLOCKGPU_OK;
     }
+    // out[i] = via[rows[i]]: rows of a side's row list -> rows of its base table (`via` null, or no rows: `rows` themselves)
+    int compose_rows(const Node *n, const char *what, const int32_t *via, const int32_t *rows, int64_t count, const int32_t **out) {
+        *out = rows;
+        if (!via || count <= 0) return FLOCKGPU_OK;
+        int32_t *composed = nullptr;
+        FG_TRY(arena_get_t(ctx, node_key(pl, n, what).c_str(), (size_t)count + 4, &composed));
+        FG_TRY(gather_i32(ctx, via, rows, count, composed));
+        *out = composed;
+        return FLOCKGPU_OK;
+    }
     // `key` = column c of `z` as lazy_key returned it, with validity bytes: the rows whose key is not NULL become the side's row list (what a filter
     // on `key IS NOT NULL` would leave), and the key is taken through it.  One host wait (the row count).
     int drop_null_key_rows(const Node *n, Lazy *z, int c, const char *what, TCol *key) {
@@ -2166,13 +2171,7 @@ struct Exec {
         int32_t *rows = nullptr;
         int64_t n_out = 0;
         FG_TRY(pred_to_rows(ctx, node_key(pl, n, what).c_str(), b.p, z->rows, &rows, &n_out));
-        if (z->via && n_out > 0) {
-            int32_t *composed = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, what, 1).c_str(), (size_t)n_out + 4, &composed));
-            FG_TRY(gather_i32(ctx, z->via, rows, n_out, composed));
-            rows = composed;
-        }
-        z->via = rows;
+        FG_TRY(compose_rows(n, (std::string(what) + "v").c_str(), z->via, rows, n_out, &z->via));
         z->rows = n_out;
         const TCol &src = z->base.cols[(size_t)c];
         FG_TRY(take_column(ctx, node_key(pl, n, what, 2).c_str(), src.c, z->via, z->rows, &key->c));
@@ -2182,23 +2181,18 @@ struct Exec {
     }
 
     // column `c` of a lazy table as the join sees it: taken through the row list when there is one
-    int lazy_key(const Node *n, const Lazy &z, int c, const char *what, TCol *out) {
+    int lazy_key(const Node *n, const Lazy &z, int c, const char *what, int pair, TCol *out) {
         *out = z.base.cols[(size_t)c];
         if (!z.via || !out->present) return FLOCKGPU_OK;
         const TCol &src = z.base.cols[(size_t)c];
-        FG_TRY(take_column(ctx, node_key(pl, n, what).c_str(), src.c, z.via, z.rows, &out->c));
+        FG_TRY(take_column(ctx, node_key(pl, n, what, pair).c_str(), src.c, z.via, z.rows, &out->c));
         out->subset_of = src.subset_of ? src.subset_of : src.c.values;
         return FLOCKGPU_OK;
     }
     // the join's result rows of one side: the pair rows composed with the side's row list, then ONE take of what the output needs
     int take_lazy(const Node *n, const Lazy &z, const int32_t *pair_rows, int64_t pairs, int first_out, const char *what, Table *t) {
-        const int32_t *rows = pair_rows;
-        if (z.via && pairs > 0) {
-            int32_t *composed = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, what).c_str(), (size_t)pairs + 4, &composed));
-            FG_TRY(gather_i32(ctx, z.via, pair_rows, pairs, composed));
-            rows = composed;
-        }
+        const int32_t *rows = nullptr;
+        FG_TRY(compose_rows(n, what, z.via, pair_rows, pairs, &rows));
         return take_table(n, z.base, n->required, rows, pairs, first_out, t);
     }
 
@@ -2212,65 +2206,14 @@ struct Exec {
             *t = Table{};
         }
         switch (n->kind) {
-            case NKind::Scan:
-                return scan_table(n, t);
-            case NKind::Repartition:
-                return exec(n->in[0].get(), t);  // placement is unobservable in one process; the root case is handled by the caller
-            case NKind::Filter: {
-                Table in;
-                int32_t *rows = nullptr;
-                int64_t n_out = 0;
-                FG_TRY(filter_rows(n, &in, &rows, &n_out));
-                t->rows = n_out;
-                t->cols.assign(n->schema.size(), TCol{});
-                return take_table(n, in, n->required, rows, n_out, 0, t);
-            }
-            case NKind::Project: {
-                Table in;
-                FG_TRY(exec(n->in[0].get(), &in));
-                t->rows = in.rows;
-                t->cols.assign(n->schema.size(), TCol{});
-                for (size_t i = 0; i < n->proj.size(); ++i) {
-                    const Expr *e = n->proj[i].first.get();
-                    TCol &o = t->cols[i];
-                    o.c.type = n->schema[i].type;
-                    o.c.is_ts = n->schema[i].is_ts;
-                    if (!n->required[i]) continue;
-                    if (e->kind == EKind::Col) {
-                        o = in.cols[(size_t)e->col];
-                        continue;
-                    }
-                    // literal * CAST(Int32 column AS Float64): q1's currency conversion (planner.rs:90), one IEEE multiply
-                    const Expr *l = is_bin(e, "Multiply") ? e->l.get() : nullptr, *r = l ? e->r.get() : nullptr;
-                    if (l && l->kind != EKind::LitF && l->kind != EKind::LitI) std::swap(l, r);
-                    const Expr *c = r ? uncast(r) : nullptr;
-                    if (!l || n->schema[i].type != ColType::F64 || (l->kind != EKind::LitF && l->kind != EKind::LitI) || c->kind != EKind::Col ||
-                        in.cols[(size_t)c->col].c.type != ColType::I32 || !in.cols[(size_t)c->col].present) {
-                        // anything else: the general evaluator (valprog.hpp), one kernel per output column
-                        ValBuilder vb;
-                        int vt = -1;
-                        bool may_null = false;
-                        FG_TRY(val_compile(e, in, vb, (int)n->schema[i].type, &vt, &may_null));
-                        if (vt != (int)n->schema[i].type) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a computed projection whose type is not its column's");
-                        void *vals = nullptr;
-                        uint8_t *vv = nullptr;
-                        FG_TRY(arena_get(ctx, node_key(pl, n, "val", (int)i).c_str(), ((size_t)std::max<int64_t>(in.rows, 0) + 2) * 8, &vals));
-                        if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, "valv", (int)i).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 16, &vv));
-                        FG_TRY(valprog_to_column(ctx, node_key(pl, n, "vprog", (int)i).c_str(), vb.p, in.rows, n->schema[i].type, vals, vv));
-                        o = dev_col(n->schema[i].type, vals, nullptr, 0, n->schema[i].is_ts);
-                        o.c.valid = vv;
-                        o.c.nullable = true;
-                        continue;
-                    }
-                    double *d = nullptr;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "f64", (int)i).c_str(), (size_t)in.rows + 2, &d));
-                    flockgpu_bid_cols bc{nullptr, nullptr, static_cast<const int32_t *>(in.cols[(size_t)c->col].c.values), nullptr, in.rows};
-                    FG_TRY(flockgpu_q1_project(ctx, &bc, l->kind == EKind::LitF ? l->f : (double)l->i, d));
-                    o = dev_col(ColType::F64, d);
-                    o.c.valid = in.cols[(size_t)c->col].c.valid;   // literal * NULL is NULL
-                }
-                return FLOCKGPU_OK;
-            }
+            case NKind::Scan: return scan_table(n, t);
+            case NKind::Repartition: return exec(n->in[0].get(), t);  // placement is unobservable in one process; the root case is handled by the caller
+            case NKind::Filter: return exec_filter(n, t);
+            case NKind::Project: return exec_project(n, t);
+            case NKind::Sort: return exec_sort(n, -1, t);
+            case NKind::Window: return exec_window(n, t);
+            case NKind::Limit: return exec_limit(n, t);
+            case NKind::Join: return exec_join(n, t);
             case NKind::Aggregate: {
                 const std::string &sig = pl->twin_sig[(size_t)n->id];
                 if (sig.empty()) return exec_aggregate(n, t);
@@ -2287,242 +2230,334 @@ struct Exec {
                 memo[key] = *t;
                 return FLOCKGPU_OK;
             }
-            case NKind::Sort:
-                return exec_sort(n, -1, t);
-            case NKind::Window: {   // the window columns first, then the input's (q6_plan.fmt: the WindowAggr schemas)
-                Table in;
-                FG_TRY(exec(n->in[0].get(), &in));
-                const size_t nw = n->win.size();
-                t->rows = in.rows;
-                t->cols.assign(n->schema.size(), TCol{});
-                auto key_of = [&](int col, DevColumn *out) -> int {
-                    const TCol &k = in.cols[(size_t)col];
-                    if (!k.present && !k.c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window key column was not materialised");
-                    *out = k.c;
-                    if (k.c.all_null) { out->type = ColType::I32; out->values = nullptr; }   // every row NULL: one run as far as this key goes
-                    return FLOCKGPU_OK;
-                };
-                for (size_t w = 0; w < nw; ++w) {
-                    if (!n->win[w].row_number) continue;
-                    t->cols[w].c.type = ColType::U64;
-                    t->cols[w].c.nullable = true;
-                    if (!n->required[w]) continue;
-                    DevColumn keys[4];
-                    if (n->win[w].part.size() > 4) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: PARTITION BY more than four columns");
-                    for (size_t c = 0; c < n->win[w].part.size(); ++c) FG_TRY(key_of(n->win[w].part[c], &keys[c]));
-                    int nk = 0;
-                    DevColumn live[4];
-                    for (size_t c = 0; c < n->win[w].part.size(); ++c)
-                        if (keys[c].values) live[nk++] = keys[c];
-                    uint64_t *rank = nullptr;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "rank", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 2, &rank));
-                    FG_TRY(row_number_runs(ctx, node_key(pl, n, "rn", (int)w).c_str(), live, nk, in.rows, rank));
-                    t->cols[w] = dev_col(ColType::U64, rank);
-                    t->cols[w].c.nullable = true;
-                }
-                // aggregate columns: one window_aggregates call per distinct (PARTITION BY, ORDER BY) -- its keys are compared once
-                std::vector<char> done(nw, 0);
-                for (size_t w0 = 0; w0 < nw; ++w0) {
-                    if (n->win[w0].row_number || done[w0]) continue;
-                    const WinExpr &x0 = n->win[w0];
-                    auto same_keys = [&](const WinExpr &y) {
-                        if (y.row_number || y.part != x0.part || y.order.size() != x0.order.size()) return false;
-                        for (size_t k = 0; k < y.order.size(); ++k)
-                            if (y.order[k].col != x0.order[k].col) return false;
-                        return true;
-                    };
-                    DevColumn live[2 * kMaxWindowKeys];   // (an all-NULL key splits nothing: left out)
-                    int np = 0, no = 0;
-                    for (int c : x0.part) {
-                        DevColumn k;
-                        FG_TRY(key_of(c, &k));
-                        if (k.values) live[np++] = k;
-                    }
-                    for (auto &o : x0.order) {
-                        DevColumn k;
-                        FG_TRY(key_of(o.col, &k));
-                        if (k.values) live[np + no++] = k;
-                    }
-                    std::vector<WinAgg> aggs;
-                    for (size_t w = w0; w < nw; ++w) {
-                        const WinExpr &x = n->win[w];
-                        if (!same_keys(x)) continue;
-                        done[w] = 1;
-                        const size_t width = x.type == ColType::I32 ? 4 : 8;
-                        TCol &oc = t->cols[w];
-                        oc.c.type = x.type;
-                        oc.c.is_ts = x.is_ts;
-                        oc.c.nullable = true;
-                        if (!n->required[w]) continue;
-                        WinAgg g;
-                        if (x.arg >= 0) {
-                            const TCol &a = in.cols[(size_t)x.arg];
-                            if (!a.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window argument column was not materialised");
-                            if (x.fn != "count" && (a.c.type == ColType::UTF8 || (a.c.type == ColType::F64 && x.fn != "min" && x.fn != "max")))
-                                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", x.fn.c_str());
-                            g.values = a.c.values;
-                            g.type = a.c.type;
-                            g.valid = a.c.valid;
-                        }
-                        const bool uns = g.type == ColType::U64, f64 = g.type == ColType::F64;
-                        if (x.fn == "count") g.op = AggOp::COUNT;
-                        else if (x.fn == "sum") g.op = AggOp::SUM_INT;
-                        else if (x.fn == "avg") g.avg = true;
-                        else if (x.fn == "max") g.op = f64 ? AggOp::MAX_F64 : uns ? AggOp::MAX_U : AggOp::MAX_S;
-                        else g.op = f64 ? AggOp::MIN_F64 : uns ? AggOp::MIN_U : AggOp::MIN_S;
-                        g.out_type = x.type;
-                        void *out = nullptr;
-                        FG_TRY(arena_get(ctx, node_key(pl, n, "wv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) * width + 64, &out));
-                        g.out = out;
-                        if (x.fn != "count") FG_TRY(arena_get_t(ctx, node_key(pl, n, "wvv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 64, &g.out_valid));
-                        aggs.push_back(g);
-                        oc = dev_col(x.type, out, nullptr, 0, x.is_ts);
-                        oc.c.nullable = true;
-                        oc.c.valid = g.out_valid;
-                    }
-                    FG_TRY(window_aggregates(ctx, node_key(pl, n, "wa", (int)w0).c_str(), live, np, no, in.rows, aggs.data(), (int)aggs.size()));
-                }
-                for (size_t i = 0; i < in.cols.size(); ++i) t->cols[nw + i] = in.cols[i];
-                return FLOCKGPU_OK;
-            }
-            case NKind::Limit: {
-                // ORDER BY ... LIMIT n (context.rs:549-550): the order is computed for every row, only the first n are taken
-                const Node *c = n->in[0].get();
-                if (c->kind == NKind::Sort && pl->fused[(size_t)c->id].kind == kNone) return exec_sort(c, n->limit, t);
-                FG_TRY(exec(c, t));
-                t->rows = std::min<int64_t>(t->rows, n->limit);   // (Utf8 columns keep their byte buffers: the first rows' offsets still hold)
-                return FLOCKGPU_OK;
-            }
-            case NKind::Join: {
-                if (n->join_type != JoinType::Inner) {   // Semi / Anti: the kept left rows, then ONE take of the left columns somebody reads
-                    Lazy z;
-                    FG_TRY(exec_semi_lazy(n, &z));
-                    t->rows = z.rows;
-                    t->cols.assign(n->schema.size(), TCol{});
-                    if (!z.via) {   // (every row kept and no row list below: the left table itself)
-                        for (size_t i = 0; i < t->cols.size() && i < z.base.cols.size(); ++i) t->cols[i] = z.base.cols[i];
-                        return FLOCKGPU_OK;
-                    }
-                    return take_table(n, z.base, n->required, z.via, z.rows, 0, t);
-                }
-                Lazy ZL, ZR;
-                FG_TRY(exec_lazy(n->in[0].get(), &ZL));
-                FG_TRY(exec_lazy(n->in[1].get(), &ZR));
-                const Table &L = ZL.base, &R = ZR.base;
-                t->cols.assign(n->schema.size(), TCol{});
-                TCol lk, rk;
-                FG_TRY(lazy_key(n, ZL, n->on_l, "lzkl", &lk));
-                FG_TRY(lazy_key(n, ZR, n->on_r, "lzkr", &rk));
-                // key pairs no path below takes -- more than two, or two that are not both Int32 without NULLs -- join on composite-key ids
-                // (two pairs of which one cannot compare -- a Float64 column, Utf8 against an integer, signed against UInt64 -- keep today's path and message)
-                if (n->on_l2 >= 0) {
-                    const TCol &l2 = L.cols[(size_t)n->on_l2], &r2 = R.cols[(size_t)n->on_r2];
-                    const bool i32_pairs = lk.c.type == ColType::I32 && rk.c.type == ColType::I32 && l2.c.type == ColType::I32 && r2.c.type == ColType::I32 &&
-                                           !lk.c.valid && !rk.c.valid && !l2.c.valid && !r2.c.valid;
-                    if (!n->on_lx.empty() || (!i32_pairs && keys_comparable(lk.c.type, rk.c.type) && keys_comparable(l2.c.type, r2.c.type)))
-                        return exec_join_composite(n, ZL, ZR, lk, rk, t);
-                }
-                const bool text_keys = lk.c.type == ColType::UTF8 && rk.c.type == ColType::UTF8 && n->on_l2 < 0;
-                if (!text_keys && ((lk.c.type == ColType::U64) != (rk.c.type == ColType::U64) || lk.c.type == ColType::UTF8 || rk.c.type == ColType::UTF8 ||
-                                   lk.c.type == ColType::F64 || rk.c.type == ColType::F64))
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
-                // one key pair, a side whose key is a computed column with validity bytes -- an ungrouped aggregate's row (MAX over nothing is NULL), which
-                // stays on the device: NULL keys never match, the side goes on as the row list of its valid keys
-                if (n->on_l2 < 0 && lk.c.valid && lk.present && !lk.c.all_null) FG_TRY(drop_null_key_rows(n, &ZL, n->on_l, "nnl", &lk));
-                if (n->on_l2 < 0 && rk.c.valid && rk.present && !rk.c.all_null) FG_TRY(drop_null_key_rows(n, &ZR, n->on_r, "nnr", &rk));
-                int64_t nl = ZL.rows, nr = ZR.rows;
-                if (lk.c.all_null) nl = 0;  // NULL keys never match
-                if (rk.c.all_null) nr = 0;
-                // (NULLs in a LEAF's key column were left out at feed: inner-join keys are null-droppable.  A computed key column that carries
-                // validity bytes -- a grouped MIN / MAX over nothing but NULLs joined on -- is not taken)
-                if (lk.c.valid || rk.c.valid || (n->on_l2 >= 0 && (L.cols[(size_t)n->on_l2].c.valid || R.cols[(size_t)n->on_r2].c.valid)))
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join on a computed column that holds NULLs");
-                int32_t *lrows = nullptr, *rrows = nullptr;
-                int64_t pairs = 0;
-                // one integer key pair whose build side is dense: chain heads addressed by key - min (relops.hpp "dense integer keys").  The
-                // table goes on the smaller side, as in join_key64 (which side is hashed is unobservable in the pair multiset).
-                if (!text_keys && n->on_l2 < 0 && lk.present && rk.present && nl > 0 && nr > 0) {
-                    bool build_right = nl > 4 * nr && nl > 4096;
-                    // Which side is a primary key nothing says -- except the previous executes of this node: a build side that repeated keys
-                    // (auctions by seller in q3) while the other side never did (persons by id) hands the table to the other side when that one is
-                    // not much larger: unique build keys are probed as a filter, one pass and no chains (relops.hpp).  Each orientation keeps its own
-                    // finding (".dups" under its own name).
-                    const std::string nm_l = node_key(pl, n, "join"), nm_r = node_key(pl, n, "joinr");
-                    auto had_dups = [&](const std::string &nm) {
-                        auto it = ctx->host_i64.find(nm + ".dups");
-                        return it != ctx->host_i64.end() && !it->second.empty();
-                    };
-                    if (!build_right && had_dups(nm_l) && !had_dups(nm_r) && nr <= 4 * nl) build_right = true;
-                    else if (build_right && had_dups(nm_r) && !had_dups(nm_l) && nl <= 16 * nr) build_right = false;
-                    const TCol &bk = build_right ? rk : lk, &pk = build_right ? lk : rk;
-                    const int64_t nb = build_right ? nr : nl, np = build_right ? nl : nr;
-                    int64_t kmin = 0, kmax = 0;
-                    // (a join the one-workgroup LDS kernel takes is ONE launch and one wait -- the dense path's fill, build, count, scan and emit
-                    // are eight and a wait, whatever the statistics cost; anything larger is worth the pass, leaf or not)
-                    const bool look = !join_is_tiny(nl, nr);
-                    if (look) FG_TRY(int_col_stats(bk, nb, &kmin, &kmax));
-                    if (look && dense_range_ok(kmin, kmax, nb, bk.c.type == ColType::U64)) {
-                        FG_TRY(join_dense(ctx, (build_right ? nm_r : nm_l).c_str(), bk.c, nb, kmin, kmax, pk.c, np, build_right ? &rrows : &lrows, build_right ? &lrows : &rrows,
-                                          &pairs));
-                        t->rows = pairs;
-                        FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
-                        return take_lazy(n, ZR, rrows, pairs, (int)L.cols.size(), "lzrr", t);
-                    }
-                }
-                int64_t *kl = nullptr, *kr = nullptr;
-                if (text_keys) {  // equal strings <-> equal dictionary codes (exact: full byte compare inside utf8_codes)
-                    if (!lk.present || !rk.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &kl));
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "kr").c_str(), (size_t)nr + 2, &kr));
-                    FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), lk.c, nl, kl, &rk.c, nr, kr));
-                    // the codes are row numbers of the left relation -- dense by construction, [0, nl) -- and a right string the left does not
-                    // hold gets a negative one: chain heads addressed by the code itself, no second hash table behind the dictionary's
-                    if (nl > 0 && nr > 0 && !join_is_tiny(nl, nr)) {
-                        DevColumn cl, cr;
-                        cl.type = cr.type = ColType::I64;
-                        cl.values = kl;
-                        cr.values = kr;
-                        FG_TRY(join_dense(ctx, node_key(pl, n, "join").c_str(), cl, nl, 0, nl - 1, cr, nr, &lrows, &rrows, &pairs));
-                        t->rows = pairs;
-                        FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
-                        return take_lazy(n, ZR, rrows, pairs, (int)L.cols.size(), "lzrr", t);
-                    }
-                } else if (n->on_l2 >= 0) {  // two Int32 pairs compare as one 64-bit key
-                    TCol lk2, rk2;
-                    FG_TRY(lazy_key(n, ZL, n->on_l2, "lzkl2", &lk2));
-                    FG_TRY(lazy_key(n, ZR, n->on_r2, "lzkr2", &rk2));
-                    if (lk.c.type != ColType::I32 || rk.c.type != ColType::I32 || lk2.c.type != ColType::I32 || rk2.c.type != ColType::I32)
-                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a two-key join needs Int32 key columns");
-                    if (!lk.present || !rk.present || !lk2.present || !rk2.present)
-                        return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-                    if (lk2.c.all_null) nl = 0;
-                    if (rk2.c.all_null) nr = 0;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &kl));
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "kr").c_str(), (size_t)nr + 2, &kr));
-                    FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(lk.c.values), static_cast<const int32_t *>(lk2.c.values), nl, kl));
-                    FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(rk.c.values), static_cast<const int32_t *>(rk2.c.values), nr, kr));
-                } else if (!join_is_tiny(nl, nr) && nl > 0 && nr > 0 && (lk.c.type == ColType::I32 || lk.c.type == ColType::I64 || lk.c.type == ColType::U64) &&
-                           (rk.c.type == ColType::I32 || rk.c.type == ColType::I64 || rk.c.type == ColType::U64)) {   // one integer key pair, not dense: the hashed table, keys read in their own types
-                    if (!lk.present || !rk.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-                    FG_TRY(join_hashed(ctx, node_key(pl, n, "join").c_str(), lk.c, nl, rk.c, nr, &lrows, &rrows, &pairs));
-                    t->rows = pairs;
-                    FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
-                    return take_lazy(n, ZR, rrows, pairs, (int)L.cols.size(), "lzrr", t);
-                } else {
-                    FG_TRY(key_i64(n, lk, nl, "kl", &kl));
-                    FG_TRY(key_i64(n, rk, nr, "kr", &kr));
-                }
-                FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), kl, nl, kr, nr, &lrows, &rrows, &pairs));
-                t->rows = pairs;
-                FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
-                return take_lazy(n, ZR, rrows, pairs, (int)L.cols.size(), "lzrr", t);
-            }
         }
         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: unknown node");
     }
 
+    int exec_filter(const Node *n, Table *t) {
+        Table in;
+        int32_t *rows = nullptr;
+        int64_t n_out = 0;
+        FG_TRY(filter_rows(n, &in, &rows, &n_out));
+        t->rows = n_out;
+        t->cols.assign(n->schema.size(), TCol{});
+        return take_table(n, in, n->required, rows, n_out, 0, t);
+    }
+
+    int exec_project(const Node *n, Table *t) {
+        Table in;
+        FG_TRY(exec(n->in[0].get(), &in));
+        t->rows = in.rows;
+        t->cols.assign(n->schema.size(), TCol{});
+        for (size_t i = 0; i < n->proj.size(); ++i) {
+            const Expr *e = n->proj[i].first.get();
+            TCol &o = t->cols[i];
+            o.c.type = n->schema[i].type;
+            o.c.is_ts = n->schema[i].is_ts;
+            if (!n->required[i]) continue;
+            if (e->kind == EKind::Col) {
+                o = in.cols[(size_t)e->col];
+                continue;
+            }
+            // literal * CAST(Int32 column AS Float64): q1's currency conversion (planner.rs:90), one IEEE multiply
+            const Expr *l = is_bin(e, "Multiply") ? e->l.get() : nullptr, *r = l ? e->r.get() : nullptr;
+            if (l && l->kind != EKind::LitF && l->kind != EKind::LitI) std::swap(l, r);
+            const Expr *c = r ? uncast(r) : nullptr;
+            if (!l || n->schema[i].type != ColType::F64 || (l->kind != EKind::LitF && l->kind != EKind::LitI) || c->kind != EKind::Col ||
+                in.cols[(size_t)c->col].c.type != ColType::I32 || !in.cols[(size_t)c->col].present) {
+                // anything else: the general evaluator (valprog.hpp), one kernel per output column
+                ValBuilder vb;
+                int vt = -1;
+                bool may_null = false;
+                FG_TRY(val_compile(e, in, vb, (int)n->schema[i].type, &vt, &may_null));
+                if (vt != (int)n->schema[i].type) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a computed projection whose type is not its column's");
+                void *vals = nullptr;
+                uint8_t *vv = nullptr;
+                FG_TRY(arena_get(ctx, node_key(pl, n, "val", (int)i).c_str(), ((size_t)std::max<int64_t>(in.rows, 0) + 2) * 8, &vals));
+                if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, "valv", (int)i).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 16, &vv));
+                FG_TRY(valprog_to_column(ctx, node_key(pl, n, "vprog", (int)i).c_str(), vb.p, in.rows, n->schema[i].type, vals, vv));
+                o = dev_col(n->schema[i].type, vals, nullptr, 0, n->schema[i].is_ts);
+                o.c.valid = vv;
+                o.c.nullable = true;
+                continue;
+            }
+            double *d = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "f64", (int)i).c_str(), (size_t)in.rows + 2, &d));
+            flockgpu_bid_cols bc{nullptr, nullptr, static_cast<const int32_t *>(in.cols[(size_t)c->col].c.values), nullptr, in.rows};
+            FG_TRY(flockgpu_q1_project(ctx, &bc, l->kind == EKind::LitF ? l->f : (double)l->i, d));
+            o = dev_col(ColType::F64, d);
+            o.c.valid = in.cols[(size_t)c->col].c.valid;   // literal * NULL is NULL
+        }
+        return FLOCKGPU_OK;
+    }
+
+    // WindowAggExec: the window columns first, then the input's (q6_plan.fmt: the WindowAggr schemas)
+    int exec_window(const Node *n, Table *t) {
+        Table in;
+        FG_TRY(exec(n->in[0].get(), &in));
+        const size_t nw = n->win.size();
+        t->rows = in.rows;
+        t->cols.assign(n->schema.size(), TCol{});
+        auto key_of = [&](int col, DevColumn *out) -> int {
+            const TCol &k = in.cols[(size_t)col];
+            if (!k.present && !k.c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window key column was not materialised");
+            *out = k.c;
+            if (k.c.all_null) { out->type = ColType::I32; out->values = nullptr; }   // every row NULL: one run as far as this key goes
+            return FLOCKGPU_OK;
+        };
+        for (size_t w = 0; w < nw; ++w) {
+            if (!n->win[w].row_number) continue;
+            t->cols[w].c.type = ColType::U64;
+            t->cols[w].c.nullable = true;
+            if (!n->required[w]) continue;
+            DevColumn keys[4];
+            if (n->win[w].part.size() > 4) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: PARTITION BY more than four columns");
+            for (size_t c = 0; c < n->win[w].part.size(); ++c) FG_TRY(key_of(n->win[w].part[c], &keys[c]));
+            int nk = 0;
+            DevColumn live[4];
+            for (size_t c = 0; c < n->win[w].part.size(); ++c)
+                if (keys[c].values) live[nk++] = keys[c];
+            uint64_t *rank = nullptr;
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "rank", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 2, &rank));
+            FG_TRY(row_number_runs(ctx, node_key(pl, n, "rn", (int)w).c_str(), live, nk, in.rows, rank));
+            t->cols[w] = dev_col(ColType::U64, rank);
+            t->cols[w].c.nullable = true;
+        }
+        // aggregate columns: one window_aggregates call per distinct (PARTITION BY, ORDER BY) -- its keys are compared once
+        std::vector<char> done(nw, 0);
+        for (size_t w0 = 0; w0 < nw; ++w0) {
+            if (n->win[w0].row_number || done[w0]) continue;
+            const WinExpr &x0 = n->win[w0];
+            auto same_keys = [&](const WinExpr &y) {
+                if (y.row_number || y.part != x0.part || y.order.size() != x0.order.size()) return false;
+                for (size_t k = 0; k < y.order.size(); ++k)
+                    if (y.order[k].col != x0.order[k].col) return false;
+                return true;
+            };
+            DevColumn live[2 * kMaxWindowKeys];   // (an all-NULL key splits nothing: left out)
+            int np = 0, no = 0;
+            for (int c : x0.part) {
+                DevColumn k;
+                FG_TRY(key_of(c, &k));
+                if (k.values) live[np++] = k;
+            }
+            for (auto &o : x0.order) {
+                DevColumn k;
+                FG_TRY(key_of(o.col, &k));
+                if (k.values) live[np + no++] = k;
+            }
+            std::vector<WinAgg> aggs;
+            for (size_t w = w0; w < nw; ++w) {
+                const WinExpr &x = n->win[w];
+                if (!same_keys(x)) continue;
+                done[w] = 1;
+                const size_t width = x.type == ColType::I32 ? 4 : 8;
+                TCol &oc = t->cols[w];
+                oc.c.type = x.type;
+                oc.c.is_ts = x.is_ts;
+                oc.c.nullable = true;
+                if (!n->required[w]) continue;
+                WinAgg g;
+                if (x.arg >= 0) {
+                    const TCol &a = in.cols[(size_t)x.arg];
+                    if (!a.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window argument column was not materialised");
+                    if (x.fn != AggFn::Count && (a.c.type == ColType::UTF8 || (a.c.type == ColType::F64 && !agg_is_minmax(x.fn))))
+                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", agg_fn_name(x.fn));
+                    g.values = a.c.values;
+                    g.type = a.c.type;
+                    g.valid = a.c.valid;
+                }
+                if (x.fn == AggFn::Avg) g.avg = true;
+                else g.op = agg_op_for(x.fn, g.type);
+                g.out_type = x.type;
+                void *out = nullptr;
+                FG_TRY(arena_get(ctx, node_key(pl, n, "wv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) * width + 64, &out));
+                g.out = out;
+                if (x.fn != AggFn::Count) FG_TRY(arena_get_t(ctx, node_key(pl, n, "wvv", (int)w).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 64, &g.out_valid));
+                aggs.push_back(g);
+                oc = dev_col(x.type, out, nullptr, 0, x.is_ts);
+                oc.c.nullable = true;
+                oc.c.valid = g.out_valid;
+            }
+            FG_TRY(window_aggregates(ctx, node_key(pl, n, "wa", (int)w0).c_str(), live, np, no, in.rows, aggs.data(), (int)aggs.size()));
+        }
+        for (size_t i = 0; i < in.cols.size(); ++i) t->cols[nw + i] = in.cols[i];
+        return FLOCKGPU_OK;
+    }
+
+    // ORDER BY ... LIMIT n (context.rs:549-550): the order is computed for every row, only the first n are taken
+    int exec_limit(const Node *n, Table *t) {
+        const Node *c = n->in[0].get();
+        if (c->kind == NKind::Sort && pl->fused[(size_t)c->id].kind == kNone) return exec_sort(c, n->limit, t);
+        FG_TRY(exec(c, t));
+        t->rows = std::min<int64_t>(t->rows, n->limit);   // (Utf8 columns keep their byte buffers: the first rows' offsets still hold)
+        return FLOCKGPU_OK;
+    }
+
+    // ---- HashJoinExec.  The key columns of every pair as the join sees them -- taken through the sides' row lists (lazy_key) -- and what its paths
+    // ask about them.
+    struct JoinKeys {
+        int np = 0;
+        TCol l[kMaxKeyCols], r[kMaxKeyCols];
+        bool l_null = false, r_null = false;     // per side: some key column holds nothing but NULLs (NULL keys never match: the side has no partner)
+        bool l_valid = false, r_valid = false;   // per side: some key column carries validity bytes
+        bool all_i32 = true;                     // every pair is Int32 = Int32
+        bool any_text = false;                   // some pair is Utf8 = Utf8
+        bool comparable = true;                  // (false: the second pair of an inner join on two -- it keeps a message of its own, exec_join)
+    };
+    int gather_join_keys(const Node *n, const Lazy &ZL, const Lazy &ZR, JoinKeys *k) {
+        k->np = (int)n->on.size();
+        if (k->np > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a join on more than %d key pairs", kMaxKeyCols);
+        for (int p = 0; p < k->np; ++p) {
+            TCol &a = k->l[p], &b = k->r[p];
+            FG_TRY(lazy_key(n, ZL, n->on[(size_t)p].l, "jkl", p, &a));
+            FG_TRY(lazy_key(n, ZR, n->on[(size_t)p].r, "jkr", p, &b));
+            if (!join_keys_comparable(a.c.type, b.c.type)) {   // (plan_ir.hpp: the rule Semi / Anti are refused by at create)
+                // (an inner join on two pairs whose second cannot compare -- a Float64 column next to an integer pair -- keeps a message of its own)
+                if (n->join_type != JoinType::Inner || k->np != 2 || p == 0 || k->any_text)
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
+                k->comparable = false;
+            }
+            if ((!a.present && !a.c.all_null) || (!b.present && !b.c.all_null)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
+            k->l_null = k->l_null || a.c.all_null;
+            k->r_null = k->r_null || b.c.all_null;
+            k->l_valid = k->l_valid || a.c.valid;
+            k->r_valid = k->r_valid || b.c.valid;
+            k->all_i32 = k->all_i32 && a.c.type == ColType::I32 && b.c.type == ColType::I32;
+            k->any_text = k->any_text || a.c.type == ColType::UTF8;
+        }
+        return FLOCKGPU_OK;
+    }
+    // two Int32 key columns compare as one 64-bit key
+    int packed_pair_keys(const Node *n, const char *what, const TCol &a, const TCol &b, int64_t rows, int64_t **out) {
+        FG_TRY(arena_get_t(ctx, node_key(pl, n, what).c_str(), (size_t)rows + 2, out));
+        return pack_i32_pair(ctx, static_cast<const int32_t *>(a.c.values), static_cast<const int32_t *>(b.c.values), rows, *out);
+    }
+    // a column of plain values of one type: ids, dictionary codes
+    static DevColumn plain_col(ColType t, const void *values) {
+        DevColumn c;
+        c.type = t;
+        c.values = values;
+        return c;
+    }
+    // the join's result: the pair rows of each side composed with the side's row list, then ONE take per side of what the output needs
+    int emit_pairs(const Node *n, const Lazy &ZL, const Lazy &ZR, const int32_t *lrows, const int32_t *rrows, int64_t pairs, Table *t) {
+        t->rows = pairs;
+        FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
+        return take_lazy(n, ZR, rrows, pairs, (int)ZL.base.cols.size(), "lzrr", t);
+    }
+
+    int exec_join(const Node *n, Table *t) {
+        if (n->join_type != JoinType::Inner) {   // Semi / Anti: the kept left rows, then ONE take of the left columns somebody reads
+            Lazy z;
+            FG_TRY(exec_semi_lazy(n, &z));
+            t->rows = z.rows;
+            t->cols.assign(n->schema.size(), TCol{});
+            if (!z.via) {   // (every row kept and no row list below: the left table itself)
+                for (size_t i = 0; i < t->cols.size() && i < z.base.cols.size(); ++i) t->cols[i] = z.base.cols[i];
+                return FLOCKGPU_OK;
+            }
+            return take_table(n, z.base, n->required, z.via, z.rows, 0, t);
+        }
+        Lazy ZL, ZR;
+        FG_TRY(exec_lazy(n->in[0].get(), &ZL));
+        FG_TRY(exec_lazy(n->in[1].get(), &ZR));
+        t->cols.assign(n->schema.size(), TCol{});
+        JoinKeys k;
+        FG_TRY(gather_join_keys(n, ZL, ZR, &k));
+        TCol &lk = k.l[0], &rk = k.r[0];
+        int32_t *lrows = nullptr, *rrows = nullptr;
+        int64_t pairs = 0;
+        // Key pairs no path below takes -- more than two, or two that are not both Int32 without NULLs -- join on composite-key ids, NULLs allowed (a
+        // NULL in any key column matches nothing): the smaller side's tuples get dense ids (relops.hpp key_codes), the other side looks its tuples
+        // up among them, and the dense join pairs the ids -- the way the one-pair Utf8 join pairs dictionary codes.
+        // (two pairs of which one cannot compare -- a Float64 column, Utf8 against an integer, signed against UInt64 -- keep today's path and message)
+        if (k.np > 2 || (k.np == 2 && k.comparable && !(k.all_i32 && !k.l_valid && !k.r_valid))) {
+            const int64_t nl = k.l_null ? 0 : ZL.rows, nr = k.r_null ? 0 : ZR.rows;
+            if (nl > 0 && nr > 0) {
+                DevColumn kl[kMaxKeyCols], kr[kMaxKeyCols];
+                for (int p = 0; p < k.np; ++p) { kl[p] = k.l[p].c; kr[p] = k.r[p].c; }
+                const bool build_right = nr < nl;   // (the ids go on the smaller side; which side is hashed is unobservable in the pair multiset)
+                const int64_t nb = build_right ? nr : nl, npr = build_right ? nl : nr;
+                int32_t *bg = nullptr, *pg = nullptr, *first = nullptr;
+                int64_t groups = 0;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcb").c_str(), (size_t)nb + 4, &bg));
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcp").c_str(), (size_t)npr + 4, &pg));
+                FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), build_right ? kr : kl, k.np, nb, bg, &groups, &first, build_right ? kl : kr, npr, pg));
+                FG_TRY(join_dense(ctx, node_key(pl, n, "join").c_str(), plain_col(ColType::I32, bg), nb, 0, groups - 1, plain_col(ColType::I32, pg), npr,
+                                  build_right ? &rrows : &lrows, build_right ? &lrows : &rrows, &pairs));
+            } else {   // an empty side: no pairs (the one-key join's answer to it)
+                int64_t *none = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "kc0").c_str(), 2, &none));
+                FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), none, 0, none, 0, &lrows, &rrows, &pairs));
+            }
+            return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+        }
+        const bool text_keys = k.np == 1 && k.any_text;
+        // one key pair, a side whose key is a computed column with validity bytes -- an ungrouped aggregate's row (MAX over nothing is NULL), which
+        // stays on the device: NULL keys never match, the side goes on as the row list of its valid keys
+        if (k.np == 1 && k.l_valid && lk.present && !k.l_null) { FG_TRY(drop_null_key_rows(n, &ZL, n->on[0].l, "nnl", &lk)); k.l_valid = false; }
+        if (k.np == 1 && k.r_valid && rk.present && !k.r_null) { FG_TRY(drop_null_key_rows(n, &ZR, n->on[0].r, "nnr", &rk)); k.r_valid = false; }
+        const int64_t nl = k.l_null ? 0 : ZL.rows, nr = k.r_null ? 0 : ZR.rows;   // NULL keys never match
+        // (NULLs in a LEAF's key column were left out at feed: inner-join keys are null-droppable.  A computed key column that carries
+        // validity bytes -- a grouped MIN / MAX over nothing but NULLs joined on -- is not taken)
+        if (k.l_valid || k.r_valid) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join on a computed column that holds NULLs");
+        // one integer key pair whose build side is dense: chain heads addressed by key - min (relops.hpp "dense integer keys").  The
+        // table goes on the smaller side, as in join_key64 (which side is hashed is unobservable in the pair multiset).
+        if (!text_keys && k.np == 1 && lk.present && rk.present && nl > 0 && nr > 0) {
+            bool build_right = nl > 4 * nr && nl > 4096;
+            // Which side is a primary key nothing says -- except the previous executes of this node: a build side that repeated keys
+            // (auctions by seller in q3) while the other side never did (persons by id) hands the table to the other side when that one is
+            // not much larger: unique build keys are probed as a filter, one pass and no chains (relops.hpp).  Each orientation keeps its own
+            // finding (".dups" under its own name).
+            const std::string nm_l = node_key(pl, n, "join"), nm_r = node_key(pl, n, "joinr");
+            auto had_dups = [&](const std::string &nm) {
+                auto it = ctx->host_i64.find(nm + ".dups");
+                return it != ctx->host_i64.end() && !it->second.empty();
+            };
+            if (!build_right && had_dups(nm_l) && !had_dups(nm_r) && nr <= 4 * nl) build_right = true;
+            else if (build_right && had_dups(nm_r) && !had_dups(nm_l) && nl <= 16 * nr) build_right = false;
+            const TCol &bk = build_right ? rk : lk, &pk = build_right ? lk : rk;
+            const int64_t nb = build_right ? nr : nl, np = build_right ? nl : nr;
+            int64_t kmin = 0, kmax = 0;
+            // (a join the one-workgroup LDS kernel takes is ONE launch and one wait -- the dense path's fill, build, count, scan and emit
+            // are eight and a wait, whatever the statistics cost; anything larger is worth the pass, leaf or not)
+            const bool look = !join_is_tiny(nl, nr);
+            if (look) FG_TRY(int_col_stats(bk, nb, &kmin, &kmax));
+            if (look && dense_range_ok(kmin, kmax, nb, bk.c.type == ColType::U64)) {
+                FG_TRY(join_dense(ctx, (build_right ? nm_r : nm_l).c_str(), bk.c, nb, kmin, kmax, pk.c, np, build_right ? &rrows : &lrows, build_right ? &lrows : &rrows,
+                                  &pairs));
+                return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+            }
+        }
+        int64_t *kl = nullptr, *kr = nullptr;
+        if (text_keys) {  // equal strings <-> equal dictionary codes (exact: full byte compare inside utf8_codes)
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &kl));
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kr").c_str(), (size_t)nr + 2, &kr));
+            FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), lk.c, nl, kl, &rk.c, nr, kr));
+            // the codes are row numbers of the left relation -- dense by construction, [0, nl) -- and a right string the left does not
+            // hold gets a negative one: chain heads addressed by the code itself, no second hash table behind the dictionary's
+            if (nl > 0 && nr > 0 && !join_is_tiny(nl, nr)) {
+                FG_TRY(join_dense(ctx, node_key(pl, n, "join").c_str(), plain_col(ColType::I64, kl), nl, 0, nl - 1, plain_col(ColType::I64, kr), nr, &lrows, &rrows, &pairs));
+                return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+            }
+        } else if (k.np == 2) {  // two Int32 pairs compare as one 64-bit key
+            if (!k.all_i32) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a two-key join needs Int32 key columns");
+            FG_TRY(packed_pair_keys(n, "kl", lk, k.l[1], nl, &kl));
+            FG_TRY(packed_pair_keys(n, "kr", rk, k.r[1], nr, &kr));
+        } else if (!join_is_tiny(nl, nr) && nl > 0 && nr > 0) {   // one integer key pair, not dense: the hashed table, keys read in their own types
+            FG_TRY(join_hashed(ctx, node_key(pl, n, "join").c_str(), lk.c, nl, rk.c, nr, &lrows, &rrows, &pairs));
+            return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+        } else {
+            FG_TRY(key_i64(n, lk, nl, "kl", &kl));
+            FG_TRY(key_i64(n, rk, nr, "kr", &kr));
+        }
+        FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), kl, nl, kr, nr, &lrows, &rrows, &pairs));
+        return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+    }
+
     // HashJoinExec join_type Semi / Anti (relops.hpp A-S1..6) as a LAZY table: the left input's base table and the list of its rows that have
-    // (Semi) / lack (Anti) a partner on the right.  The left side arrives lazily itself, its key columns are read through lazy_key, and the
+    // (Semi) / lack (Anti) a partner on the right.  The left side arrives lazily itself, its key columns are read through gather_join_keys, and the
     // kept rows compose with its row list -- no right-side take, no pair rows, no `.dups` bookkeeping.  Key shapes: one integer pair goes to
     // semi_rows (a bitmap when the right keys are dense, a hashed key set otherwise), two Int32 pairs as one packed 64-bit key to the same, one
     // Utf8 pair through utf8_codes, anything else -- more pairs, mixed types, NULLs in a multi-column key or on a computed right side -- through
@@ -2532,31 +2567,12 @@ struct Exec {
         Lazy ZL, ZR;
         FG_TRY(exec_lazy(n->in[0].get(), &ZL));
         FG_TRY(exec_lazy(n->in[1].get(), &ZR));
-        std::vector<int> on_l{n->on_l}, on_r{n->on_r};
-        if (n->on_l2 >= 0) { on_l.push_back(n->on_l2); on_r.push_back(n->on_r2); }
-        on_l.insert(on_l.end(), n->on_lx.begin(), n->on_lx.end());
-        on_r.insert(on_r.end(), n->on_rx.begin(), n->on_rx.end());
-        const int np = (int)on_l.size();
-        if (np > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a join on more than %d key pairs", kMaxKeyCols);
         const int64_t nl = ZL.rows, nr = ZR.rows;
-        TCol lk[kMaxKeyCols], rk[kMaxKeyCols];
-        bool l_null = false, r_null = false, l_valid = false, r_valid = false, all_i32 = true, any_text = false;
-        for (int p = 0; p < np; ++p) {
-            FG_TRY(lazy_key(n, ZL, on_l[(size_t)p], ("skl" + std::to_string(p)).c_str(), &lk[p]));
-            FG_TRY(lazy_key(n, ZR, on_r[(size_t)p], ("skr" + std::to_string(p)).c_str(), &rk[p]));
-            if (!keys_comparable(lk[p].c.type, rk[p].c.type))
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
-            if ((!lk[p].present && !lk[p].c.all_null) || (!rk[p].present && !rk[p].c.all_null)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-            l_null = l_null || lk[p].c.all_null;
-            r_null = r_null || rk[p].c.all_null;
-            l_valid = l_valid || lk[p].c.valid;
-            r_valid = r_valid || rk[p].c.valid;
-            all_i32 = all_i32 && lk[p].c.type == ColType::I32 && rk[p].c.type == ColType::I32;
-            any_text = any_text || lk[p].c.type == ColType::UTF8;
-        }
+        JoinKeys k;
+        FG_TRY(gather_join_keys(n, ZL, ZR, &k));
         z->base = ZL.base;
         // (A-S4) nothing on the left, nothing that could match on the right, or nothing but NULL keys on the left: no probe
-        if (nl <= 0 || nr <= 0 || r_null || l_null) {
+        if (nl <= 0 || nr <= 0 || k.r_null || k.l_null) {
             const bool keep_all = anti && nl > 0;
             z->rows = keep_all ? nl : 0;
             z->via = ZL.via;
@@ -2570,104 +2586,37 @@ struct Exec {
         int32_t *rows = nullptr;
         int64_t n_out = 0;
         const std::string nm = node_key(pl, n, "semi");
-        if (np == 1 && !any_text && !r_valid) {
+        if (k.np == 1 && !k.any_text && !k.r_valid) {
             int64_t kmin = 0, kmax = 0;
             bool dense = false;
             // (a pair of sizes the one-workgroup kernel takes is ONE launch and one wait, whatever the statistics say; a leaf's statistics are cached)
             if (!semi_is_tiny(nl, nr)) {
-                FG_TRY(int_col_stats(rk[0], nr, &kmin, &kmax));
-                dense = dense_range_ok(kmin, kmax, nr, rk[0].c.type == ColType::U64);
+                FG_TRY(int_col_stats(k.r[0], nr, &kmin, &kmax));
+                dense = dense_range_ok(kmin, kmax, nr, k.r[0].c.type == ColType::U64);
             }
-            FG_TRY(semi_rows(ctx, nm.c_str(), lk[0].c, nl, rk[0].c, nr, dense, kmin, kmax, anti, &rows, &n_out));
-        } else if (np == 2 && all_i32 && !l_valid && !r_valid) {   // two Int32 pairs compare as one 64-bit key
+            FG_TRY(semi_rows(ctx, nm.c_str(), k.l[0].c, nl, k.r[0].c, nr, dense, kmin, kmax, anti, &rows, &n_out));
+        } else if (k.np == 2 && k.all_i32 && !k.l_valid && !k.r_valid) {
             int64_t *kl = nullptr, *kr = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &kl));
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kr").c_str(), (size_t)nr + 2, &kr));
-            FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(lk[0].c.values), static_cast<const int32_t *>(lk[1].c.values), nl, kl));
-            FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(rk[0].c.values), static_cast<const int32_t *>(rk[1].c.values), nr, kr));
-            DevColumn cl, cr;
-            cl.type = cr.type = ColType::I64;
-            cl.values = kl;
-            cr.values = kr;
-            FG_TRY(semi_rows(ctx, nm.c_str(), cl, nl, cr, nr, false, 0, 0, anti, &rows, &n_out));
-        } else if (np == 1 && any_text && !l_valid && !r_valid) {   // equal strings <-> a dictionary code of the right side (exact: full byte compare inside utf8_codes)
+            FG_TRY(packed_pair_keys(n, "kl", k.l[0], k.l[1], nl, &kl));
+            FG_TRY(packed_pair_keys(n, "kr", k.r[0], k.r[1], nr, &kr));
+            FG_TRY(semi_rows(ctx, nm.c_str(), plain_col(ColType::I64, kl), nl, plain_col(ColType::I64, kr), nr, false, 0, 0, anti, &rows, &n_out));
+        } else if (k.np == 1 && k.any_text && !k.l_valid && !k.r_valid) {   // equal strings <-> a dictionary code of the right side (exact: full byte compare inside utf8_codes)
             int64_t *codes = nullptr;
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "kl").c_str(), (size_t)nl + 2, &codes));
-            FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), rk[0].c, nr, nullptr, &lk[0].c, nl, codes));
+            FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), k.r[0].c, nr, nullptr, &k.l[0].c, nl, codes));
             FG_TRY(semi_rows_from_ids(ctx, nm.c_str(), codes, true, nl, anti, &rows, &n_out));
         } else {
             DevColumn kl[kMaxKeyCols], kr[kMaxKeyCols];
-            for (int p = 0; p < np; ++p) { kl[p] = lk[p].c; kr[p] = rk[p].c; }
+            for (int p = 0; p < k.np; ++p) { kl[p] = k.l[p].c; kr[p] = k.r[p].c; }
             int32_t *bg = nullptr, *pg = nullptr, *first = nullptr;
             int64_t groups = 0;
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcb").c_str(), (size_t)nr + 4, &bg));
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcp").c_str(), (size_t)nl + 4, &pg));
-            FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), kr, np, nr, bg, &groups, &first, kl, nl, pg));
+            FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), kr, k.np, nr, bg, &groups, &first, kl, nl, pg));
             FG_TRY(semi_rows_from_ids(ctx, nm.c_str(), pg, false, nl, anti, &rows, &n_out));
         }
         z->rows = n_out;
-        z->via = rows;
-        if (ZL.via && n_out > 0) {   // rows of the left input's own row list -> rows of its base table
-            int32_t *composed = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "semiv").c_str(), (size_t)n_out + 4, &composed));
-            FG_TRY(gather_i32(ctx, ZL.via, rows, n_out, composed));
-            z->via = composed;
-        }
-        return FLOCKGPU_OK;
-    }
-
-    // A join on several key pairs of any integer / Utf8 types, NULLs allowed (a NULL in any key column matches nothing): the smaller side's
-    // tuples get dense ids (relops.hpp key_codes), the other side looks its tuples up among them, and the dense join pairs the ids -- the way
-    // the one-pair Utf8 join pairs dictionary codes.
-    // a join key pair the composite ids can compare: two Utf8 columns, or two integer columns of one signedness
-    static bool keys_comparable(ColType x, ColType y) { return join_keys_comparable(x, y); }   // (plan_ir.hpp: the rule Semi / Anti are refused by at create)
-    // lk0 / rk0: pair 0's key columns, already taken by the caller
-    int exec_join_composite(const Node *n, const Lazy &ZL, const Lazy &ZR, const TCol &lk0, const TCol &rk0, Table *t) {
-        std::vector<int> on_l{n->on_l, n->on_l2}, on_r{n->on_r, n->on_r2};
-        on_l.insert(on_l.end(), n->on_lx.begin(), n->on_lx.end());
-        on_r.insert(on_r.end(), n->on_rx.begin(), n->on_rx.end());
-        const int np = (int)on_l.size();
-        if (np > kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: a join on more than %d key pairs", kMaxKeyCols);
-        DevColumn kl[kMaxKeyCols], kr[kMaxKeyCols];
-        int64_t nl = ZL.rows, nr = ZR.rows;
-        for (int p = 0; p < np; ++p) {
-            TCol a = lk0, b = rk0;
-            if (p > 0) {
-                FG_TRY(lazy_key(n, ZL, on_l[(size_t)p], ("ckl" + std::to_string(p)).c_str(), &a));
-                FG_TRY(lazy_key(n, ZR, on_r[(size_t)p], ("ckr" + std::to_string(p)).c_str(), &b));
-            }
-            if (!keys_comparable(a.c.type, b.c.type))
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: join keys must be integer columns of one signedness, or two Utf8 columns");
-            if (a.c.all_null) nl = 0;   // NULL keys never match
-            if (b.c.all_null) nr = 0;
-            if ((!a.present && !a.c.all_null) || (!b.present && !b.c.all_null)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-            kl[p] = a.c;
-            kr[p] = b.c;
-        }
-        int32_t *lrows = nullptr, *rrows = nullptr;
-        int64_t pairs = 0;
-        if (nl > 0 && nr > 0) {
-            const bool build_right = nr < nl;   // (the ids go on the smaller side; which side is hashed is unobservable in the pair multiset)
-            const int64_t nb = build_right ? nr : nl, npr = build_right ? nl : nr;
-            int32_t *bg = nullptr, *pg = nullptr, *first = nullptr;
-            int64_t groups = 0;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcb").c_str(), (size_t)nb + 4, &bg));
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kcp").c_str(), (size_t)npr + 4, &pg));
-            FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), build_right ? kr : kl, np, nb, bg, &groups, &first, build_right ? kl : kr, npr, pg));
-            DevColumn cb, cp;
-            cb.type = cp.type = ColType::I32;
-            cb.values = bg;
-            cp.values = pg;
-            FG_TRY(join_dense(ctx, node_key(pl, n, "join").c_str(), cb, nb, 0, groups - 1, cp, npr, build_right ? &rrows : &lrows, build_right ? &lrows : &rrows,
-                              &pairs));
-        } else {   // an empty side: no pairs (the one-key join's answer to it)
-            int64_t *none = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "kc0").c_str(), 2, &none));
-            FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), none, 0, none, 0, &lrows, &rrows, &pairs));
-        }
-        t->rows = pairs;
-        FG_TRY(take_lazy(n, ZL, lrows, pairs, 0, "lzrl", t));
-        return take_lazy(n, ZR, rrows, pairs, (int)ZL.base.cols.size(), "lzrr", t);
+        return compose_rows(n, "semiv", ZL.via, rows, n_out, &z->via);   // rows of the left input's own row list -> rows of its base table
     }
 
     // SortExec [+ GlobalLimitExec]: the stable order of relops.hpp's sort_rows, then one take of the columns somebody reads
@@ -2704,22 +2653,28 @@ struct Exec {
     // (COUNT / SUM / MAX / MIN states have the result's type; AVG's (count, sum) state does not).  The stage plans stage.rs cuts keep
     // Partial -> Hash repartition -> FinalPartitioned in one plan (q5.dag, q8.dag): a second hash pass over the groups for nothing.
     bool final_is_identity(const Node *n, const Node **partial) const {
-        if (n->mode == "Partial" || n->group.empty()) return false;
+        if (n->mode == AggMode::Partial || n->group.empty()) return false;
         const Node *c = n->in[0].get();
         while (c->kind == NKind::Repartition) c = c->in[0].get();
-        if (c->kind != NKind::Aggregate || c->mode != "Partial" || c->group.size() != n->group.size() || c->aggs.size() != n->aggs.size() ||
+        if (c->kind != NKind::Aggregate || c->mode != AggMode::Partial || c->group.size() != n->group.size() || c->aggs.size() != n->aggs.size() ||
             c->schema.size() != n->schema.size())
             return false;
         for (size_t i = 0; i < n->group.size(); ++i)
             if (n->group[i] != (int)i) return false;
         for (size_t a = 0; a < n->aggs.size(); ++a)
-            if (n->aggs[a].fn != c->aggs[a].fn || n->aggs[a].fn == "avg" || n->aggs[a].arg != (int)(n->group.size() + a)) return false;
+            if (n->aggs[a].fn != c->aggs[a].fn || n->aggs[a].fn == AggFn::Avg || n->aggs[a].arg != (int)(n->group.size() + a)) return false;
         for (size_t i = 0; i < n->schema.size(); ++i)
             if (c->schema[i].type != n->schema[i].type) return false;
         *partial = c;
         return true;
     }
 
+    // these accumulators may take the dense (direct-address) table: integer ones over arguments without NULLs
+    static bool specs_fit_dense(const AggSpec *specs, int n_specs) {
+        for (int a = 0; a < n_specs; ++a)
+            if (specs[a].valid || specs[a].op == AggOp::SUM_F64 || specs[a].op == AggOp::MAX_F64 || specs[a].op == AggOp::MIN_F64) return false;
+        return true;
+    }
     // GROUP BY on composite-key ids: gid in [0, G) in order of first appearance, then the dense GROUP BY over the ids (groups come out in id
     // order) where its accumulators allow, else the hashed one with its groups put back in id order.  g->first_row: the groups' first rows.
     int group_composite(const Node *n, const Table &in, const AggSpec *specs, int n_specs, GroupResultN *g) {
@@ -2736,21 +2691,12 @@ struct Exec {
         FG_TRY(key_codes(ctx, node_key(pl, n, "kc").c_str(), kc, nk, in.rows, gid, &groups, &first, nullptr, 0, nullptr));
         *g = GroupResultN{};
         if (n_specs > 0) {
-            bool dense = groups > 0;
-            for (int a = 0; a < n_specs && dense; ++a)
-                dense = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
-            if (dense) {
-                DevColumn ids;
-                ids.type = ColType::I32;
-                ids.values = gid;
-                FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), ids, in.rows, 0, groups - 1, specs, n_specs, g));
+            if (groups > 0 && specs_fit_dense(specs, n_specs)) {
+                FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), plain_col(ColType::I32, gid), in.rows, 0, groups - 1, specs, n_specs, g));
             } else {
                 int64_t *ids = nullptr;
                 FG_TRY(arena_get_t(ctx, node_key(pl, n, "gid64").c_str(), (size_t)in.rows + 2, &ids));
-                DevColumn gc;
-                gc.type = ColType::I32;
-                gc.values = gid;
-                if (in.rows > 0) FG_TRY(widen_to_i64(ctx, gc, in.rows, ids));
+                if (in.rows > 0) FG_TRY(widen_to_i64(ctx, plain_col(ColType::I32, gid), in.rows, ids));
                 GroupResultN h;
                 FG_TRY(group_by_key64_n(ctx, node_key(pl, n, "grp").c_str(), ids, in.rows, specs, n_specs, &h, nullptr));
                 // (every id in [0, G) is one group: the accumulators go to position id)
@@ -2816,7 +2762,7 @@ struct Exec {
         } else {
             FG_TRY(exec(n->in[0].get(), &in));
         }
-        const bool is_final = n->mode != "Partial";
+        const bool is_final = n->mode != AggMode::Partial;
         ReduceProgram P;
         // the program's column for input column c (*out = -1: the column holds nothing but NULLs)
         auto col_of = [&](int c, const char *what, bool allow_f64, int *out) -> int {
@@ -2864,7 +2810,7 @@ struct Exec {
         for (auto &a : n->aggs) {
             const size_t oc = (size_t)P.n_outs;
             int c = -1, s = -1, s2 = -1;
-            if (a.fn == "count") {
+            if (a.fn == AggFn::Count) {
                 if (is_final) {   // the sum of the count states; over no state row it is 0, not NULL
                     FG_TRY(col_of(a.arg, "the COUNT state", false, &c));
                     FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
@@ -2882,16 +2828,16 @@ struct Exec {
                         emit(ReduceOutKind::ColCount, c, -1, -1);
                     }
                 }
-            } else if (a.fn == "sum") {
+            } else if (a.fn == AggFn::Sum) {
                 FG_TRY(col_of(a.arg, "sum", false, &c));
                 FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
                 emit(ReduceOutKind::Value, c, s, -1);
-            } else if (a.fn == "max" || a.fn == "min") {
-                FG_TRY(col_of(a.arg, a.fn.c_str(), true, &c));
+            } else if (agg_is_minmax(a.fn)) {
+                FG_TRY(col_of(a.arg, agg_fn_name(a.fn), true, &c));
                 const ColType at = in.cols[(size_t)a.arg].c.type, want = n->schema[oc].type;
                 if ((want == ColType::F64) != (at == ColType::F64) || (want == ColType::I32) != (at == ColType::I32) || want == ColType::UTF8)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", a.fn.c_str());
-                const bool inv = a.fn == "min";
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
+                const bool inv = a.fn == AggFn::Min;
                 FG_TRY(slot_of(ReduceKind::UMax, c, (at == ColType::U64 ? 0 : kSign) ^ (inv ? ~uint64_t(0) : 0), at == ColType::F64, inv, &s));
                 emit(ReduceOutKind::Value, c, s, -1);
             } else if (is_final) {   // avg: (count, sum) states -> sum / count
@@ -2938,7 +2884,7 @@ struct Exec {
         if (n->group.empty() && !ir::lone_integer_max(n)) return exec_global_aggregate(n, t);
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
-        const bool is_final = n->mode != "Partial";
+        const bool is_final = n->mode != AggMode::Partial;
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->schema.size(); ++i) {
             t->cols[i].c.type = n->schema[i].type;
@@ -2948,7 +2894,7 @@ struct Exec {
         // ---- no GROUP BY: MAX of one integer column -> one row (NULL over no input)
         if (n->group.empty()) {
             const ColType at = n->aggs.size() == 1 && n->aggs[0].arg >= 0 ? in.cols[(size_t)n->aggs[0].arg].c.type : ColType::UTF8;
-            if (n->aggs.size() != 1 || n->aggs[0].fn != "max" || at == ColType::UTF8 || at == ColType::F64 || !in.cols[(size_t)n->aggs[0].arg].present)
+            if (n->aggs.size() != 1 || n->aggs[0].fn != AggFn::Max || at == ColType::UTF8 || at == ColType::F64 || !in.cols[(size_t)n->aggs[0].arg].present)
                 return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: global aggregate other than MAX over an integer column");
             const TCol &a = in.cols[(size_t)n->aggs[0].arg];
             int64_t mx = 0;
@@ -3043,10 +2989,10 @@ struct Exec {
         for (auto &a : n->aggs) {
             Out o;
             o.first = n_specs;
-            o.count = a.fn == "avg" ? 2 : 1;
+            o.count = agg_state_cols(a.fn);
             if (n_specs + o.count > kMaxGroupAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxGroupAggs);
             // (every accumulator carries its argument's validity: NULLs are skipped, a group without a valid value comes out NULL)
-            if (a.fn == "count") {
+            if (a.fn == AggFn::Count) {
                 if (is_final) {
                     const TCol *st = int_col(a.arg, "the COUNT state");
                     if (!st) return FLOCKGPU_ERR_UNSUPPORTED;
@@ -3054,14 +3000,11 @@ struct Exec {
                 } else {   // COUNT(*) / COUNT(UInt8(1)) counts rows, COUNT(col) the rows whose col is not NULL
                     specs[n_specs++] = AggSpec{AggOp::COUNT, nullptr, ColType::I64, a.arg >= 0 ? in.cols[(size_t)a.arg].c.valid : nullptr};
                 }
-            } else if ((a.fn == "max" || a.fn == "min") && a.arg >= 0 && in.cols[(size_t)a.arg].present && in.cols[(size_t)a.arg].c.type == ColType::F64) {
-                specs[n_specs++] = AggSpec{a.fn == "max" ? AggOp::MAX_F64 : AggOp::MIN_F64, in.cols[(size_t)a.arg].c.values, ColType::F64, in.cols[(size_t)a.arg].c.valid};
-            } else if (a.fn == "max" || a.fn == "min" || a.fn == "sum") {
-                const TCol *v = int_col(a.arg, a.fn.c_str());
+            } else if (a.fn != AggFn::Avg) {   // SUM of an integer column; MIN / MAX of an integer or a Float64 one
+                const bool f64 = agg_is_minmax(a.fn) && a.arg >= 0 && in.cols[(size_t)a.arg].present && in.cols[(size_t)a.arg].c.type == ColType::F64;
+                const TCol *v = f64 ? &in.cols[(size_t)a.arg] : int_col(a.arg, agg_fn_name(a.fn));
                 if (!v) return FLOCKGPU_ERR_UNSUPPORTED;
-                const bool uns = v->c.type == ColType::U64;
-                const AggOp op = a.fn == "sum" ? AggOp::SUM_INT : (a.fn == "max" ? (uns ? AggOp::MAX_U : AggOp::MAX_S) : (uns ? AggOp::MIN_U : AggOp::MIN_S));
-                specs[n_specs++] = AggSpec{op, v->c.values, v->c.type, v->c.valid};
+                specs[n_specs++] = AggSpec{agg_op_for(a.fn, v->c.type), v->c.values, v->c.type, v->c.valid};
             } else {  // avg: (count, sum)
                 if (is_final) {
                     const TCol *cnt = int_col(a.arg, "the AVG count state");
@@ -3084,9 +3027,8 @@ struct Exec {
         // A dense integer key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer
         // keys") -- slot = key - min over the column's exact range, no hashing, no int64 copy of the key column.  Everything else (Utf8 /
         // two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
-        bool dense = !composite && !pair && !null_keys && k.present && in.rows > 0 && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64);
-        for (int a = 0; a < n_specs && dense; ++a)
-            dense = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
+        const bool fit = specs_fit_dense(specs, n_specs);
+        bool dense = fit && !composite && !pair && !null_keys && k.present && in.rows > 0 && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64);
         int64_t kmin = 0, kmax = 0;
         if (dense && !stats_worth_it(k, in.rows)) dense = false;
         if (dense) {
@@ -3095,15 +3037,10 @@ struct Exec {
         }
         // A Utf8 key's dictionary codes are row numbers of its own relation: dense by construction.  The code of a group IS a row that
         // carries the group's string, so it also stands in for the first row the key column is taken from.
-        bool dense_codes = !composite && !pair && !null_keys && k.present && k.c.type == ColType::UTF8 && in.rows > 0 && in.rows < (int64_t(1) << 31);
-        for (int a = 0; a < n_specs && dense_codes; ++a)
-            dense_codes = !specs[a].valid && specs[a].op != AggOp::SUM_F64 && specs[a].op != AggOp::MAX_F64 && specs[a].op != AggOp::MIN_F64;
+        const bool dense_codes = fit && !composite && !pair && !null_keys && k.present && k.c.type == ColType::UTF8 && in.rows > 0 && in.rows < (int64_t(1) << 31);
         if (dense_codes) {
             FG_TRY(prepare_keys());   // (utf8_codes)
-            DevColumn codes;
-            codes.type = ColType::I64;
-            codes.values = keys;
-            FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), codes, in.rows, 0, in.rows - 1, specs, n_specs, &g));
+            FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), plain_col(ColType::I64, keys), in.rows, 0, in.rows - 1, specs, n_specs, &g));
             int32_t *rep = nullptr;
             FG_TRY(arena_get_t(ctx, node_key(pl, n, "rep").c_str(), (size_t)g.n_groups + 4, &rep));
             FG_TRY(narrow_i64_to_i32(ctx, g.keys, g.n_groups, rep));
@@ -3170,7 +3107,7 @@ struct Exec {
                 t->cols[col].c.nullable = true;
                 return FLOCKGPU_OK;
             };
-            if (a.fn == "avg") {
+            if (a.fn == AggFn::Avg) {
                 if (is_final) {
                     double *avg = nullptr;
                     uint8_t *av = nullptr;
@@ -3195,9 +3132,9 @@ struct Exec {
                 const ColType want = n->schema[oc].type;
                 const bool f64_acc = specs[o.first].op == AggOp::MAX_F64 || specs[o.first].op == AggOp::MIN_F64;
                 if (want == ColType::UTF8 || (want == ColType::F64) != f64_acc)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", a.fn.c_str());
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
                 FG_TRY(narrow_if_i32(g.agg[o.first], want, n->schema[oc].is_ts, oc));
-                if (a.fn != "count") t->cols[oc].c.valid = g.agg_valid[o.first];   // MIN / MAX / SUM over nothing but NULLs is NULL; COUNT(col) is 0
+                if (a.fn != AggFn::Count) t->cols[oc].c.valid = g.agg_valid[o.first];   // MIN / MAX / SUM over nothing but NULLs is NULL; COUNT(col) is 0
                 oc += 1;
             }
         }

@@ -99,8 +99,41 @@ struct SortCol {
     bool descending = false;
     bool nulls_first = false;  // parsed and carried; device columns hold no NULLs (a NULL that could reach a sort is refused at feed)
 };
+// Aggregate functions and stage modes: a name becomes its enum once, where the parser validates it (parse_agg_fn / parse_agg_mode)
+enum class AggFn { Count, Sum, Min, Max, Avg };
+enum class AggMode { Partial, Final, FinalPartitioned };
+inline const char *agg_fn_name(AggFn f) {   // the lower-case name, as the messages print it
+    static const char *names[] = {"count", "sum", "min", "max", "avg"};
+    return names[(int)f];
+}
+inline const char *agg_mode_name(AggMode m) {
+    static const char *names[] = {"Partial", "Final", "FinalPartitioned"};
+    return names[(int)m];
+}
+inline bool parse_agg_fn(const std::string &name, AggFn *out) {
+    for (AggFn f : {AggFn::Count, AggFn::Sum, AggFn::Min, AggFn::Max, AggFn::Avg})
+        if (name == agg_fn_name(f)) { *out = f; return true; }
+    return false;
+}
+inline bool parse_agg_mode(const std::string &name, AggMode *out) {
+    for (AggMode m : {AggMode::Partial, AggMode::Final, AggMode::FinalPartitioned})
+        if (name == agg_mode_name(m)) { *out = m; return true; }
+    return false;
+}
+inline bool agg_is_minmax(AggFn f) { return f == AggFn::Min || f == AggFn::Max; }
+// The 64-bit accumulator of COUNT / SUM / MIN / MAX over a column of type `t` (GROUP BY's and the window aggregates'; AVG: its sum -- the count
+// beside it is the caller's)
+inline AggOp agg_op_for(AggFn f, ColType t) {
+    const bool uns = t == ColType::U64, f64 = t == ColType::F64;
+    switch (f) {
+        case AggFn::Count: return AggOp::COUNT;
+        case AggFn::Max: return f64 ? AggOp::MAX_F64 : uns ? AggOp::MAX_U : AggOp::MAX_S;
+        case AggFn::Min: return f64 ? AggOp::MIN_F64 : uns ? AggOp::MIN_U : AggOp::MIN_S;
+        default: return AggOp::SUM_INT;
+    }
+}
 struct Agg {
-    std::string fn;  // "count" | "max" | "min" | "sum" | "avg"
+    AggFn fn = AggFn::Count;
     int arg = -1;    // Partial: input column of the argument (-1: a literal, COUNT(UInt8(1))); Final: the first state column
     int arg2 = -1;   // Final AVG: its second state column (the sum; `arg` is the count)
     std::string name;
@@ -108,7 +141,7 @@ struct Agg {
 };
 // State columns a Partial stage emits per aggregate, as DataFusion ~6 lays them out (Accumulator::state / state_fields,
 // SURVEY.md appendix D): COUNT -> [count UInt64]; MAX / MIN / SUM -> [value]; AVG -> [count UInt64, sum Float64].
-inline int agg_state_cols(const std::string &fn) { return fn == "avg" ? 2 : 1; }
+inline int agg_state_cols(AggFn fn) { return fn == AggFn::Avg ? 2 : 1; }
 constexpr int kMaxUngroupedAccumulators = 8;   // of one aggregate without GROUP BY (AVG takes two)
 // key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
 constexpr int kMaxJoinPairs = 8;
@@ -116,7 +149,7 @@ constexpr int kMaxJoinPairs = 8;
 // partition's rows up to the last PEER of the current row -- equal ORDER BY values; the whole partition without ORDER BY).
 struct WinExpr {
     bool row_number = true;
-    std::string fn;                // aggregate: "count" | "sum" | "min" | "max" | "avg"
+    AggFn fn = AggFn::Count;       // aggregate: the function
     int arg = -1;                  // aggregate: input column of the argument (-1: COUNT(*))
     ColType type = ColType::U64;   // the window column's type (the aggregate's data_type; COUNT UInt64, AVG Float64)
     bool is_ts = false;            // MIN / MAX of a Timestamp
@@ -129,6 +162,7 @@ enum class JoinType { Inner, Semi, Anti };
 inline bool join_keys_comparable(ColType x, ColType y) {
     return x != ColType::F64 && y != ColType::F64 && (x == ColType::UTF8) == (y == ColType::UTF8) && (x == ColType::U64) == (y == ColType::U64);
 }
+struct KeyPair { int l = -1, r = -1; };   // one `left column = right column` of a join
 struct Node {
     NKind kind = NKind::Scan;
     int id = 0;
@@ -137,12 +171,10 @@ struct Node {
     int leaf = -1;                  // Scan: index into Plan::leaves
     std::unique_ptr<Expr> pred;     // Filter
     std::vector<std::pair<std::unique_ptr<Expr>, std::string>> proj;  // Project
-    std::string mode;               // Aggregate: Partial | Final | FinalPartitioned
+    AggMode mode = AggMode::Partial;   // Aggregate
     std::vector<int> group;         // Aggregate: input columns of the group keys
     std::vector<Agg> aggs;
-    int on_l = -1, on_r = -1;       // Join: key columns (left input, right input)
-    int on_l2 = -1, on_r2 = -1;     // Join: second key pair (q9: auction = id AND price = final), -1 when there is one
-    std::vector<int> on_lx, on_rx;  // Join: the key pairs after the second (at most kMaxJoinPairs in all)
+    std::vector<KeyPair> on;        // Join: the key pairs, 1 to kMaxJoinPairs (q9 has two: auction = id AND price = final)
     bool join_partitioned = false;  // Join: mode=Partitioned (both inputs arrive hash-partitioned on the keys)
     JoinType join_type = JoinType::Inner;   // Join: Semi / Anti return rows of the LEFT input only (schema = the left input's)
     std::vector<int> hash_cols;     // Repartition
@@ -157,7 +189,7 @@ struct Node {
 // Aggregate without GROUP BY: a lone MAX over one integer column (q5 / q7's MAX(num)) keeps the path and the feed-time NULL dropping it has had
 // from the start; every other list of aggregates is one streaming pass (reduce.hpp).
 inline bool lone_integer_max(const Node *n) {
-    if (!n->group.empty() || n->aggs.size() != 1 || n->aggs[0].fn != "max" || n->aggs[0].arg < 0 || n->in.empty()) return false;
+    if (!n->group.empty() || n->aggs.size() != 1 || n->aggs[0].fn != AggFn::Max || n->aggs[0].arg < 0 || n->in.empty()) return false;
     const std::vector<Field> &sch = n->in[0]->schema;
     if ((size_t)n->aggs[0].arg >= sch.size()) return false;
     const ColType at = sch[(size_t)n->aggs[0].arg].type;
@@ -626,11 +658,10 @@ struct Builder {
             n->in.push_back(std::move(in));
         } else if (t == "hash_aggregate_exec") {
             n->kind = NKind::Aggregate;
-            n->mode = j->s("mode");
-            if (n->mode != "Partial" && n->mode != "Final" && n->mode != "FinalPartitioned") { fail("aggregate mode '" + n->mode + "'"); return nullptr; }
+            if (!parse_agg_mode(j->s("mode"), &n->mode)) { fail("aggregate mode '" + j->s("mode") + "'"); return nullptr; }
             auto in = node(j->get("input"), depth + 1);
             if (!in) return nullptr;
-            const bool is_final = n->mode != "Partial";
+            const bool is_final = n->mode != AggMode::Partial;
             // A group key or an aggregate argument that is an EXPRESSION (GROUP BY a % 10, SUM(price * 2)): the stage that evaluates it
             // (Partial) gets a projection underneath that carries every input column through and the expression's value beside them
             // (the general evaluator, valprog.hpp); the aggregate then reads a column, as ever.  -1: refused (plan->why says why).
@@ -659,17 +690,17 @@ struct Builder {
             if (ae && ae->kind == JValue::Arr)
                 for (auto &x : ae->arr) {
                     Agg a;
-                    a.fn = x->s("aggregate_expr");
                     a.name = x->s("name");
                     bool ts = false;
                     if (!parse_type(x->get("data_type"), &a.type, &ts)) { fail("aggregate '" + a.name + "' of an unsupported type"); return nullptr; }
-                    if (a.fn != "count" && a.fn != "max" && a.fn != "min" && a.fn != "sum" && a.fn != "avg") {
-                        fail("aggregate function '" + a.fn + "' (supported: count, max, min, sum, avg)");
+                    if (!parse_agg_fn(x->s("aggregate_expr"), &a.fn)) {
+                        fail("aggregate function '" + x->s("aggregate_expr") + "' (supported: count, max, min, sum, avg)");
                         return nullptr;
                     }
+                    const std::string fn = agg_fn_name(a.fn);
                     if (is_final) {
                         a.arg = state_at;  // state columns, by position
-                        if (a.fn == "avg") a.arg2 = state_at + 1;
+                        if (a.fn == AggFn::Avg) a.arg2 = state_at + 1;
                         state_at += agg_state_cols(a.fn);
                         if ((size_t)state_at > in->schema.size()) { fail("final aggregate without its state column"); return nullptr; }
                     } else {
@@ -678,23 +709,23 @@ struct Builder {
                             a.arg = resolve(arg, in->schema);
                             if (a.arg < 0) { fail("aggregate argument not in the input schema"); return nullptr; }
                         } else if (arg && etag(arg) != "literal") {   // SUM(price * 2), COUNT(CASE ...): the expression becomes a column underneath
-                            a.arg = computed(arg, ("aggregate '" + a.fn + "'").c_str());
+                            a.arg = computed(arg, ("aggregate '" + fn + "'").c_str());
                             if (a.arg < 0) return nullptr;
-                        } else if (a.fn != "count") {
-                            fail("aggregate '" + a.fn + "' over a literal");
+                        } else if (a.fn != AggFn::Count) {
+                            fail("aggregate '" + fn + "' over a literal");
                             return nullptr;
                         }
                     }
-                    if (a.fn == "count") a.type = ColType::U64;
-                    if (a.fn == "avg") a.type = ColType::F64;
+                    if (a.fn == AggFn::Count) a.type = ColType::U64;
+                    if (a.fn == AggFn::Avg) a.type = ColType::F64;
                     Field f;
                     f.nullable = true;
-                    f.is_ts = ts && (a.fn == "max" || a.fn == "min");   // MIN / MAX of a Timestamp column is a Timestamp (q11's start_time / end_time)
+                    f.is_ts = ts && agg_is_minmax(a.fn);   // MIN / MAX of a Timestamp column is a Timestamp (q11's start_time / end_time)
                     if (is_final) {
                         f.name = a.name;
                         f.type = a.type;
                         n->schema.push_back(f);
-                    } else if (a.fn == "avg") {
+                    } else if (a.fn == AggFn::Avg) {
                         f.name = a.name + "[count]";
                         f.type = ColType::U64;
                         n->schema.push_back(f);
@@ -702,7 +733,7 @@ struct Builder {
                         f.type = ColType::F64;
                         n->schema.push_back(f);
                     } else {
-                        f.name = a.name + "[" + a.fn + "]";
+                        f.name = a.name + "[" + fn + "]";
                         f.type = a.type;
                         n->schema.push_back(f);
                     }
@@ -715,7 +746,7 @@ struct Builder {
                     accs += agg_state_cols(a.fn);
                     if (a.arg < 0) continue;
                     const ColType at = in->schema[(size_t)a.arg].type;
-                    if (at == ColType::UTF8 || (at == ColType::F64 && (a.fn == "sum" || a.fn == "avg"))) { fail(a.fn + " needs an integer column"); return nullptr; }
+                    if (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(a.fn) && a.fn != AggFn::Count)) { fail(std::string(agg_fn_name(a.fn)) + " needs an integer column"); return nullptr; }
                 }
                 if (accs > kMaxUngroupedAccumulators) { fail("more than " + std::to_string(kMaxUngroupedAccumulators) + " accumulators in one ungrouped aggregate"); return nullptr; }
             }
@@ -747,18 +778,9 @@ struct Builder {
                 }
                 return resolve(k, schema);
             };
-            n->on_l = keycol(on->arr[0]->arr[0].get(), l->schema);
-            n->on_r = keycol(on->arr[0]->arr[1].get(), r->schema);
-            if (n->on_l < 0 || n->on_r < 0) { fail("join key not in the input schemas"); return nullptr; }
-            if (on->arr.size() >= 2) {
-                n->on_l2 = keycol(on->arr[1]->arr[0].get(), l->schema);
-                n->on_r2 = keycol(on->arr[1]->arr[1].get(), r->schema);
-                if (n->on_l2 < 0 || n->on_r2 < 0) { fail("join key not in the input schemas"); return nullptr; }
-            }
-            for (size_t k = 2; k < on->arr.size(); ++k) {
-                n->on_lx.push_back(keycol(on->arr[k]->arr[0].get(), l->schema));
-                n->on_rx.push_back(keycol(on->arr[k]->arr[1].get(), r->schema));
-                if (n->on_lx.back() < 0 || n->on_rx.back() < 0) { fail("join key not in the input schemas"); return nullptr; }
+            for (auto &pair : on->arr) {
+                n->on.push_back(KeyPair{keycol(pair->arr[0].get(), l->schema), keycol(pair->arr[1].get(), r->schema)});
+                if (n->on.back().l < 0 || n->on.back().r < 0) { fail("join key not in the input schemas"); return nullptr; }
             }
             n->schema = l->schema;
             if (!semi) n->schema.insert(n->schema.end(), r->schema.begin(), r->schema.end());
@@ -779,9 +801,8 @@ struct Builder {
                         return nullptr;
                     }
                 }
-                bool ok = join_keys_comparable(l->schema[(size_t)n->on_l].type, r->schema[(size_t)n->on_r].type);
-                if (n->on_l2 >= 0) ok = ok && join_keys_comparable(l->schema[(size_t)n->on_l2].type, r->schema[(size_t)n->on_r2].type);
-                for (size_t k = 0; k < n->on_lx.size(); ++k) ok = ok && join_keys_comparable(l->schema[(size_t)n->on_lx[k]].type, r->schema[(size_t)n->on_rx[k]].type);
+                bool ok = true;
+                for (auto &k : n->on) ok = ok && join_keys_comparable(l->schema[(size_t)k.l].type, r->schema[(size_t)k.r].type);
                 if (!ok) { fail(std::string(kind) + " join: join keys must be integer columns of one signedness, or two Utf8 columns"); return nullptr; }
             }
             n->in.push_back(std::move(l));
@@ -850,10 +871,10 @@ struct Builder {
                 if (w->s("window_expr") == "aggregate_window_expr" || (ag && ag->kind == JValue::Obj)) {
                     if (!ag || ag->kind != JValue::Obj) { fail("aggregate_window_expr without its aggregate"); return nullptr; }
                     x.row_number = false;
-                    x.fn = ag->s("aggregate_expr");
-                    for (auto &ch : x.fn) ch = (char)std::tolower((unsigned char)ch);
-                    if (x.fn != "count" && x.fn != "max" && x.fn != "min" && x.fn != "sum" && x.fn != "avg") {
-                        fail("window function '" + x.fn + "' (supported: ROW_NUMBER, COUNT, SUM, MIN, MAX, AVG)");
+                    std::string fn = ag->s("aggregate_expr");
+                    for (auto &ch : fn) ch = (char)std::tolower((unsigned char)ch);
+                    if (!parse_agg_fn(fn, &x.fn)) {
+                        fail("window function '" + fn + "' (supported: ROW_NUMBER, COUNT, SUM, MIN, MAX, AVG)");
                         return nullptr;
                     }
                     f.name = ag->s("name");
@@ -863,23 +884,23 @@ struct Builder {
                         x.arg = resolve(arg, in->schema);
                         if (x.arg < 0) { fail("window aggregate argument not in the input schema"); return nullptr; }
                     } else if (arg && etag(arg) != "literal") {
-                        fail("window aggregate '" + x.fn + "' over a computed expression");
+                        fail("window aggregate '" + fn + "' over a computed expression");
                         return nullptr;
-                    } else if (x.fn != "count") {
-                        fail("window aggregate '" + x.fn + "' over a literal");
+                    } else if (x.fn != AggFn::Count) {
+                        fail("window aggregate '" + fn + "' over a literal");
                         return nullptr;
                     }
                     // the argument types of the GROUP BY path (plan.hip exec_aggregate), refused in its words
                     const ColType at = x.arg >= 0 ? in->schema[(size_t)x.arg].type : ColType::U64;
-                    if (x.fn != "count" && (at == ColType::UTF8 || (at == ColType::F64 && x.fn != "min" && x.fn != "max"))) {
-                        fail(x.fn + " needs an integer column");
+                    if (x.fn != AggFn::Count && (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(x.fn)))) {
+                        fail(fn + " needs an integer column");
                         return nullptr;
                     }
-                    if (x.fn == "count") x.type = ColType::U64;
-                    if (x.fn == "avg") x.type = ColType::F64;
-                    x.is_ts = x.is_ts && (x.fn == "min" || x.fn == "max");
-                    if ((x.fn == "min" || x.fn == "max") && (x.type == ColType::F64) != (at == ColType::F64)) {
-                        fail(x.fn + " of a column into a column of another kind");
+                    if (x.fn == AggFn::Count) x.type = ColType::U64;
+                    if (x.fn == AggFn::Avg) x.type = ColType::F64;
+                    x.is_ts = x.is_ts && agg_is_minmax(x.fn);
+                    if (agg_is_minmax(x.fn) && (x.type == ColType::F64) != (at == ColType::F64)) {
+                        fail(fn + " of a column into a column of another kind");
                         return nullptr;
                     }
                     if (x.type == ColType::UTF8) { fail("window aggregate '" + f.name + "' of an unsupported type"); return nullptr; }
@@ -1027,12 +1048,7 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
             std::vector<char> l(req.begin(), req.begin() + nl), r;
             if (semi) r.assign(n->in[1]->schema.size(), 0);
             else r.assign(req.begin() + nl, req.end());
-            need(l, n->on_l);
-            need(r, n->on_r);
-            need(l, n->on_l2);
-            need(r, n->on_r2);
-            for (int c : n->on_lx) need(l, c);
-            for (int c : n->on_rx) need(r, c);
+            for (auto &k : n->on) { need(l, k.l); need(r, k.r); }
             mark_required(p, n->in[0].get(), l);
             mark_required(p, n->in[1].get(), r);
             break;
@@ -1135,27 +1151,16 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
         }
         case NKind::Join: {
             const size_t nl = n->in[0]->schema.size();
-            if (n->join_type != JoinType::Inner) {
-                // Semi / Anti: `droppable` speaks of the left columns alone.  A NULL key never matches: the right rows it sits in can go, and so can
-                // Semi's left rows -- but an ANTI join KEEPS its NULL-keyed left rows (relops.hpp A-S4): their key columns arrive with validity bytes
-                // and the probe reads them
-                std::vector<char> l = droppable, r(n->in[1]->schema.size(), 0);
-                const bool semi = n->join_type == JoinType::Semi;
-                if (semi) l[(size_t)n->on_l] = 1;
-                r[(size_t)n->on_r] = 1;
-                if (n->on_l2 >= 0) { if (semi) l[(size_t)n->on_l2] = 1; r[(size_t)n->on_r2] = 1; }
-                for (int c : n->on_lx) if (semi) l[(size_t)c] = 1;
-                for (int c : n->on_rx) r[(size_t)c] = 1;
-                mark_null_droppable(p, n->in[0].get(), l);
-                mark_null_droppable(p, n->in[1].get(), r);
-                break;
+            // Inner: NULL keys never match.  Semi / Anti: `droppable` speaks of the left columns alone.  A NULL key never matches: the right rows it
+            // sits in can go, and so can Semi's left rows -- but an ANTI join KEEPS its NULL-keyed left rows (relops.hpp A-S4): their key columns
+            // arrive with validity bytes and the probe reads them
+            const bool inner = n->join_type == JoinType::Inner;
+            std::vector<char> l(droppable.begin(), droppable.begin() + nl), r(n->in[1]->schema.size(), 0);
+            if (inner) r.assign(droppable.begin() + nl, droppable.end());
+            for (auto &k : n->on) {
+                if (n->join_type != JoinType::Anti) l[(size_t)k.l] = 1;
+                r[(size_t)k.r] = 1;
             }
-            std::vector<char> l(droppable.begin(), droppable.begin() + nl), r(droppable.begin() + nl, droppable.end());
-            l[(size_t)n->on_l] = 1;  // NULL keys never match in an inner join
-            r[(size_t)n->on_r] = 1;
-            if (n->on_l2 >= 0) { l[(size_t)n->on_l2] = 1; r[(size_t)n->on_r2] = 1; }
-            for (int c : n->on_lx) l[(size_t)c] = 1;
-            for (int c : n->on_rx) r[(size_t)c] = 1;
             mark_null_droppable(p, n->in[0].get(), l);
             mark_null_droppable(p, n->in[1].get(), r);
             break;
@@ -1183,7 +1188,7 @@ inline void mark_co_partitioned(Plan *p, const Node *n, bool under) {
             if (n->join_partitioned) under = true;
             break;
         case NKind::Aggregate:
-            if (n->mode == "FinalPartitioned") under = true;
+            if (n->mode == AggMode::FinalPartitioned) under = true;
             break;
         default:
             break;

@@ -379,6 +379,38 @@ def test_join_on_composite_keys(gpu, shape, nl, nr, null_p):
         assert len(want) > 0
 
 
+_FILTERED_JOINS = dict(JOINS, i32_pair=[("i", "i"), ("i2", "i2")], one=[("i", "i")])   # + the packed Int32 pair, + one pair
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", sorted(_FILTERED_JOINS))
+@pytest.mark.parametrize("nl,nr,null_p", [(700, 500, 0.1), (20_000, 12_000, 0.1)])
+def test_join_on_composite_keys_under_filters(gpu, shape, nl, nr, null_p):
+    """An inner join whose two inputs are filters: both sides arrive as row lists, and every key column -- the second and later pairs too -- is read
+    through them.  (700, 500) stays inside the one-workgroup join; at (20000, 12000) the smaller side has more than 4096 rows and leaves it."""
+    from flock_amd.runtime import ExecutionContext, collect
+    on = [(a, b + "_r") for a, b in _FILTERED_JOINS[shape]]
+    left, right = _join_tables(nl, nr, nl * 7 + nr, null_p)
+    if shape == "mixed":      # (as in test_join_on_composite_keys: Int32 i meets Int64 l by value)
+        left["i"] = [None if x is None else x % 1000 for x in left["i"]]
+        right["l"] = [None if x is None else x % 1000 for x in right["i"]]
+    right = {c + "_r": v for c, v in right.items()}
+    lit = lambda v: {"physical_expr": "literal", "value": {"Int64": v}}
+    plan = _join_plan(COLS, RCOLS, on)
+    plan["left"] = {"execution_plan": "filter_exec", "input": plan["left"],
+                    "predicate": {"physical_expr": "binary_expr", "left": _c("v"), "op": "Gt", "right": lit(-500_000)}}
+    plan["right"] = {"execution_plan": "filter_exec", "input": plan["right"],
+                     "predicate": {"physical_expr": "binary_expr", "left": _c("v_r", RCOLS), "op": "GtEq", "right": lit(3)}}
+    ctx = ExecutionContext([plan], gpu=gpu)
+    out = collect(ctx, [[_batches(left, 5_000)], [_batches(right, 5_000, RCOLS)]])[0][0]
+    ctx.close()
+    want = g.rows(g.hash_join_inner(g.filter_exec(left, lambda r: r["v"] > -500_000), g.filter_exec(right, lambda r: r["v_r"] >= 3), on))
+    got = _pyrows(out)
+    assert len(want) > 0
+    assert len(got) == len(want), (shape, nl, nr, null_p)
+    assert _multiset(got) == _multiset(want)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("nr", [50, 2_000])
 def test_join_on_a_computed_key_that_holds_nulls(gpu, nr):
