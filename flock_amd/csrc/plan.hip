@@ -21,6 +21,7 @@
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
 #include "pred.hpp"
+#include "distinct.hpp"
 #include "reduce.hpp"
 #include "strmatch.hpp"
 #include "valprog.hpp"
@@ -273,7 +274,7 @@ struct LogicalAgg {
     std::vector<int> args;
 };
 bool logical_agg(const Node *n, LogicalAgg *out) {
-    if (n->kind != NKind::Aggregate) return false;
+    if (n->kind != NKind::Aggregate || n->single_pass) return false;   // (a single pass -- a node with a distinct count -- is no fused pipeline's)
     const Node *low = n;
     if (n->mode != AggMode::Partial) {
         Peeled p = peel(n->in[0].get());
@@ -768,7 +769,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Join && n->join_type == JoinType::Semi) kind = "SemiJoin";
     if (n->kind == NKind::Join && n->join_type == JoinType::Anti) kind = "AntiJoin";
     os << std::string((size_t)depth * 2, ' ') << kind;
-    if (n->kind == NKind::Aggregate) os << "(" << agg_mode_name(n->mode) << ")";
+    if (n->kind == NKind::Aggregate) os << "(" << agg_mode_name(n->mode) << (n->single_pass ? ", single pass" : "") << ")";
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
@@ -870,7 +871,7 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     for (size_t i = 0; i < n->schema.size(); ++i)
         *o += n->schema[i].name + "/" + std::to_string((int)n->schema[i].type) + (n->schema[i].is_ts ? "t" : "") + (n->schema[i].nullable ? "?" : "") +
               (!top && i < n->required.size() && n->required[i] ? "!" : "") + ",";   // (an Aggregate computes every output column: its own `required` does not matter)
-    *o += "|" + std::to_string((int)n->mode) + "|";
+    *o += "|" + std::to_string((int)n->mode) + (n->single_pass ? "s" : "") + "|";
     for (int c : n->group) *o += std::to_string(c) + ",";
     for (auto &a : n->aggs) *o += std::to_string((int)a.fn) + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
     *o += "|";
@@ -2653,7 +2654,7 @@ struct Exec {
     // (COUNT / SUM / MAX / MIN states have the result's type; AVG's (count, sum) state does not).  The stage plans stage.rs cuts keep
     // Partial -> Hash repartition -> FinalPartitioned in one plan (q5.dag, q8.dag): a second hash pass over the groups for nothing.
     bool final_is_identity(const Node *n, const Node **partial) const {
-        if (n->mode == AggMode::Partial || n->group.empty()) return false;
+        if (n->mode == AggMode::Partial || n->group.empty() || n->single_pass) return false;
         const Node *c = n->in[0].get();
         while (c->kind == NKind::Repartition) c = c->in[0].get();
         if (c->kind != NKind::Aggregate || c->mode != AggMode::Partial || c->group.size() != n->group.size() || c->aggs.size() != n->aggs.size() ||
@@ -2677,7 +2678,7 @@ struct Exec {
     }
     // GROUP BY on composite-key ids: gid in [0, G) in order of first appearance, then the dense GROUP BY over the ids (groups come out in id
     // order) where its accumulators allow, else the hashed one with its groups put back in id order.  g->first_row: the groups' first rows.
-    int group_composite(const Node *n, const Table &in, const AggSpec *specs, int n_specs, GroupResultN *g) {
+    int group_composite(const Node *n, const Table &in, const AggSpec *specs, int n_specs, GroupResultN *g, const int32_t **gid_out = nullptr) {
         const int nk = (int)n->group.size();
         DevColumn kc[kMaxKeyCols];
         for (int c = 0; c < nk; ++c) {
@@ -2712,6 +2713,7 @@ struct Exec {
         }
         g->n_groups = groups;
         g->first_row = first;
+        if (gid_out) *gid_out = gid;
         return FLOCKGPU_OK;
     }
 
@@ -2753,7 +2755,10 @@ struct Exec {
         const uint32_t *flags = nullptr, *wave_counts = nullptr;
         int32_t flag_tiles = 0;
         std::vector<int> map;
-        if (const Node *f = filter_below(n->in[0].get(), &map)) {
+        // (a distinct count reads its argument column as a whole: under it the filter is materialised as ever)
+        const bool distinct = ir::has_distinct_count(n);
+        const Node *f = distinct ? nullptr : filter_below(n->in[0].get(), &map);
+        if (f) {
             Table fin;
             FG_TRY(filter_flags(f, &fin, &flags, &wave_counts, &flag_tiles));
             in.rows = fin.rows;
@@ -2762,7 +2767,7 @@ struct Exec {
         } else {
             FG_TRY(exec(n->in[0].get(), &in));
         }
-        const bool is_final = n->mode != AggMode::Partial;
+        const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
         ReduceProgram P;
         // the program's column for input column c (*out = -1: the column holds nothing but NULLs)
         auto col_of = [&](int c, const char *what, bool allow_f64, int *out) -> int {
@@ -2810,7 +2815,12 @@ struct Exec {
         for (auto &a : n->aggs) {
             const size_t oc = (size_t)P.n_outs;
             int c = -1, s = -1, s2 = -1;
-            if (a.fn == AggFn::Count) {
+            if (a.fn == AggFn::CountDistinct) {   // its place in the row: distinct_count_by_group writes the value below, behind the fold on the stream
+                if (a.arg < 0 || (size_t)a.arg >= in.cols.size() || in.cols[(size_t)a.arg].c.type == ColType::F64 ||
+                    (!in.cols[(size_t)a.arg].present && !in.cols[(size_t)a.arg].c.all_null))
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: distinct_count needs an integer or Utf8 column");
+                emit(ReduceOutKind::Rows, -1, -1, -1);
+            } else if (a.fn == AggFn::Count) {
                 if (is_final) {   // the sum of the count states; over no state row it is 0, not NULL
                     FG_TRY(col_of(a.arg, "the COUNT state", false, &c));
                     FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
@@ -2849,6 +2859,10 @@ struct Exec {
                 FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
                 FG_TRY(slot_of(ReduceKind::SumF64, c2, 0, true, false, &s2));
                 emit(ReduceOutKind::AvgFinal, c, s, s2);
+            } else if (n->single_pass) {   // avg in one pass: what Final makes of the one state row -- (double) integer sum / (double) count
+                FG_TRY(col_of(a.arg, "AVG", false, &c));
+                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
+                emit(ReduceOutKind::AvgOnePass, c, s, in.cols[(size_t)a.arg].c.type == ColType::U64 ? 1 : 0);
             } else {   // avg -> its state: [count UInt64, sum Float64]
                 FG_TRY(col_of(a.arg, "AVG", false, &c));
                 FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
@@ -2861,6 +2875,10 @@ struct Exec {
         FG_TRY(arena_get_t(ctx, node_key(pl, n, "gagg").c_str(), (size_t)kReduceMaxOuts + kReduceMaxOuts / 8 + 2, &out));
         uint8_t *ov = reinterpret_cast<uint8_t *>(out + kReduceMaxOuts);
         FG_TRY(reduce_global(ctx, node_key(pl, n, "gred").c_str(), P, in.rows, flags, wave_counts, flag_tiles, out, ov));
+        // the distinct counts: every row in one group, the count straight into the row (never NULL: the fold marked the place valid)
+        for (size_t i = 0; i < n->aggs.size() && distinct; ++i)
+            if (n->aggs[i].fn == AggFn::CountDistinct)
+                FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", (int)i).c_str(), nullptr, 1, in.cols[(size_t)n->aggs[i].arg].c, in.rows, out + i));
         t->rows = 1;
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->schema.size(); ++i) {
@@ -2884,7 +2902,8 @@ struct Exec {
         if (n->group.empty() && !ir::lone_integer_max(n)) return exec_global_aggregate(n, t);
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
-        const bool is_final = n->mode != AggMode::Partial;
+        const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
+        const bool distinct = ir::has_distinct_count(n);
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->schema.size(); ++i) {
             t->cols[i].c.type = n->schema[i].type;
@@ -2912,8 +2931,9 @@ struct Exec {
         }
         // ---- key shapes the paths below do not take -- three or more columns, two other than (Int32, Int32) / DISTINCT (Int32, Utf8), NULLs in
         // a two-column key -- group on composite-key ids (relops.hpp key_codes): groups in order of first appearance
-        bool composite = n->group.size() > 2;
-        if (n->group.size() == 2) {
+        // ... and so does every node with a distinct count, whatever its key: the ids index the ordinary accumulators and the distinct counts alike
+        bool composite = n->group.size() > 2 || distinct;
+        if (n->group.size() == 2 && !distinct) {
             const TCol &a = in.cols[(size_t)n->group[0]], &b = in.cols[(size_t)n->group[1]];
             composite = a.c.type != ColType::I32 || a.c.valid || b.c.valid || b.c.type != (n->aggs.empty() ? ColType::UTF8 : ColType::I32);
             if (a.c.type == ColType::F64 || b.c.type == ColType::F64) composite = false;   // (refused below with today's message)
@@ -2989,10 +3009,14 @@ struct Exec {
         for (auto &a : n->aggs) {
             Out o;
             o.first = n_specs;
-            o.count = agg_state_cols(a.fn);
+            o.count = ir::agg_accumulators(a.fn);
             if (n_specs + o.count > kMaxGroupAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxGroupAggs);
             // (every accumulator carries its argument's validity: NULLs are skipped, a group without a valid value comes out NULL)
-            if (a.fn == AggFn::Count) {
+            if (a.fn == AggFn::CountDistinct) {   // no accumulator: a table of its own over the group ids, below
+                const TCol *v = a.arg >= 0 && (size_t)a.arg < in.cols.size() ? &in.cols[(size_t)a.arg] : nullptr;
+                if (!v || v->c.type == ColType::F64 || (!v->present && !v->c.all_null))
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: distinct_count needs an integer or Utf8 column");
+            } else if (a.fn == AggFn::Count) {
                 if (is_final) {
                     const TCol *st = int_col(a.arg, "the COUNT state");
                     if (!st) return FLOCKGPU_ERR_UNSUPPORTED;
@@ -3023,7 +3047,8 @@ struct Exec {
             outs.push_back(o);
         }
         GroupResultN g;
-        if (composite) FG_TRY(group_composite(n, in, specs, n_specs, &g));
+        const int32_t *gid = nullptr;
+        if (composite) FG_TRY(group_composite(n, in, specs, n_specs, &g, &gid));
         // A dense integer key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer
         // keys") -- slot = key - min over the column's exact range, no hashing, no int64 copy of the key column.  Everything else (Utf8 /
         // two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
@@ -3107,7 +3132,27 @@ struct Exec {
                 t->cols[col].c.nullable = true;
                 return FLOCKGPU_OK;
             };
-            if (a.fn == AggFn::Avg) {
+            if (a.fn == AggFn::CountDistinct) {
+                uint64_t *dc = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc).c_str(), (size_t)g.n_groups + 2, &dc));
+                if (g.n_groups > 0) FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", (int)ai).c_str(), gid, g.n_groups, in.cols[(size_t)a.arg].c, in.rows, dc));
+                t->cols[oc] = dev_col(ColType::U64, dc);
+                t->cols[oc].c.nullable = true;
+                oc += 1;
+            } else if (a.fn == AggFn::Avg && n->single_pass) {   // what Final makes of a group's one state row: (double) integer sum / (double) count
+                double *sum = nullptr, *avg = nullptr;
+                uint8_t *av = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "avs", (int)oc).c_str(), (size_t)g.n_groups + 2, &sum));
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc).c_str(), (size_t)g.n_groups + 2, &avg));
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "avv", (int)oc).c_str(), (size_t)g.n_groups + 16, &av));
+                FG_TRY(i64_to_f64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first + 1]), g.n_groups, sum));
+                FG_TRY(avg_finish(ctx, sum, g.agg[o.first], g.n_groups, avg));
+                FG_TRY(valid_from_i64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first]), g.n_groups, 0, av));   // AVG over no valid value is NULL
+                t->cols[oc] = dev_col(ColType::F64, avg);
+                t->cols[oc].c.nullable = true;
+                t->cols[oc].c.valid = av;
+                oc += 1;
+            } else if (a.fn == AggFn::Avg) {
                 if (is_final) {
                     double *avg = nullptr;
                     uint8_t *av = nullptr;

@@ -10,6 +10,10 @@
 // COUNT / SUM / MIN / MAX / AVG over the default frame.  hash_join_exec takes join_type Inner, Semi and Anti (Semi / Anti: the left input's rows
 // that have / lack a partner on the right, the left input's schema -- relops.hpp A-S1..6).  Anything else (other window functions and frames,
 // Left / Right / Full joins, unknown expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
+// hash_aggregate_exec takes COUNT / SUM / MIN / MAX / AVG and COUNT(DISTINCT x) -- an aggr_expr entry tagged "distinct_count" (alias "count_distinct") with
+// its one argument under `exprs` or `expr` (distinct.hpp A-D1..A-D7).  That aggregate's Partial state is a List column, which this boundary does not
+// carry: Final / FinalPartitioned over the Partial of the same plan becomes ONE single-pass node over the Partial's input (Node::single_pass); a Partial
+// with a distinct count that anything else consumes is refused.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -100,16 +104,17 @@ struct SortCol {
     bool nulls_first = false;  // parsed and carried; device columns hold no NULLs (a NULL that could reach a sort is refused at feed)
 };
 // Aggregate functions and stage modes: a name becomes its enum once, where the parser validates it (parse_agg_fn / parse_agg_mode)
-enum class AggFn { Count, Sum, Min, Max, Avg };
+enum class AggFn { Count, Sum, Min, Max, Avg, CountDistinct };
 enum class AggMode { Partial, Final, FinalPartitioned };
 inline const char *agg_fn_name(AggFn f) {   // the lower-case name, as the messages print it
-    static const char *names[] = {"count", "sum", "min", "max", "avg"};
+    static const char *names[] = {"count", "sum", "min", "max", "avg", "distinct_count"};
     return names[(int)f];
 }
 inline const char *agg_mode_name(AggMode m) {
     static const char *names[] = {"Partial", "Final", "FinalPartitioned"};
     return names[(int)m];
 }
+// (the five ordinary functions, GROUP BY's and the window aggregates'; a distinct count is recognised by is_distinct_count_tag, in hash_aggregate_exec alone)
 inline bool parse_agg_fn(const std::string &name, AggFn *out) {
     for (AggFn f : {AggFn::Count, AggFn::Sum, AggFn::Min, AggFn::Max, AggFn::Avg})
         if (name == agg_fn_name(f)) { *out = f; return true; }
@@ -120,6 +125,7 @@ inline bool parse_agg_mode(const std::string &name, AggMode *out) {
         if (name == agg_mode_name(m)) { *out = m; return true; }
     return false;
 }
+inline bool is_distinct_count_tag(const std::string &name) { return name == "distinct_count" || name == "count_distinct"; }
 inline bool agg_is_minmax(AggFn f) { return f == AggFn::Min || f == AggFn::Max; }
 // The 64-bit accumulator of COUNT / SUM / MIN / MAX over a column of type `t` (GROUP BY's and the window aggregates'; AVG: its sum -- the count
 // beside it is the caller's)
@@ -141,7 +147,11 @@ struct Agg {
 };
 // State columns a Partial stage emits per aggregate, as DataFusion ~6 lays them out (Accumulator::state / state_fields,
 // SURVEY.md appendix D): COUNT -> [count UInt64]; MAX / MIN / SUM -> [value]; AVG -> [count UInt64, sum Float64].
+// (COUNT(DISTINCT) never emits its state: one result column in the single-pass node, Node::single_pass)
 inline int agg_state_cols(AggFn fn) { return fn == AggFn::Avg ? 2 : 1; }
+// 64-bit accumulators the aggregate takes in GROUP BY's table / the ungrouped reduce: a distinct count takes none, it owns a table of its own
+inline int agg_accumulators(AggFn fn) { return fn == AggFn::CountDistinct ? 0 : agg_state_cols(fn); }
+constexpr int kMaxDistinctCounts = 4;          // of one aggregate node
 constexpr int kMaxUngroupedAccumulators = 8;   // of one aggregate without GROUP BY (AVG takes two)
 // key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
 constexpr int kMaxJoinPairs = 8;
@@ -174,6 +184,9 @@ struct Node {
     AggMode mode = AggMode::Partial;   // Aggregate
     std::vector<int> group;         // Aggregate: input columns of the group keys
     std::vector<Agg> aggs;
+    // Aggregate with a distinct count: Final / FinalPartitioned and the Partial below it as ONE aggregation over the Partial's input -- `mode` is the
+    // upper node's, arguments are input columns as a Partial's, the schema is the finished results' (AVG one Float64 column)
+    bool single_pass = false;
     std::vector<KeyPair> on;        // Join: the key pairs, 1 to kMaxJoinPairs (q9 has two: auction = id AND price = final)
     bool join_partitioned = false;  // Join: mode=Partitioned (both inputs arrive hash-partitioned on the keys)
     JoinType join_type = JoinType::Inner;   // Join: Semi / Anti return rows of the LEFT input only (schema = the left input's)
@@ -195,9 +208,14 @@ inline bool lone_integer_max(const Node *n) {
     const ColType at = sch[(size_t)n->aggs[0].arg].type;
     return at != ColType::UTF8 && at != ColType::F64;
 }
+inline bool has_distinct_count(const Node *n) {
+    for (auto &a : n->aggs)
+        if (a.fn == AggFn::CountDistinct) return true;
+    return false;
+}
 inline int ungrouped_accumulators(const Node *n) {
     int accs = 0;
-    for (auto &a : n->aggs) accs += agg_state_cols(a.fn);
+    for (auto &a : n->aggs) accs += agg_accumulators(a.fn);
     return accs;
 }
 
@@ -272,6 +290,36 @@ struct Builder {
     bool fail(const std::string &m) {
         if (err.empty()) err = m;
         return false;
+    }
+
+    // hash_aggregate_exec `j` lists a distinct count
+    static bool json_has_distinct_count(const JValue *j) {
+        const JValue *ae = j->get("aggr_expr");
+        if (ae && ae->kind == JValue::Arr)
+            for (auto &x : ae->arr)
+                if (x->kind == JValue::Obj && is_distinct_count_tag(x->s("aggregate_expr"))) return true;
+        return false;
+    }
+    // The Partial hash_aggregate_exec that Final / FinalPartitioned `j` merges: below nothing but repartition_exec / coalesce_* / merge_exec nodes, with
+    // as many group keys and the same aggregates by tag and name.  Null: there is none.
+    static const JValue *partial_below(const JValue *j) {
+        const JValue *c = j->get("input");
+        for (int depth = 0; c && c->kind == JValue::Obj && depth < 64; ++depth) {
+            const std::string &t = tag(c);
+            if (t != "repartition_exec" && t != "coalesce_batches_exec" && t != "coalesce_partitions_exec" && t != "merge_exec") break;
+            c = c->get("input");
+        }
+        if (!c || c->kind != JValue::Obj || tag(c) != "hash_aggregate_exec" || c->s("mode") != "Partial") return nullptr;
+        auto count = [](const JValue *l) { return l && l->kind == JValue::Arr ? l->arr.size() : (size_t)0; };
+        const JValue *ga = j->get("group_expr"), *gb = c->get("group_expr"), *aa = j->get("aggr_expr"), *ab = c->get("aggr_expr");
+        if (count(ga) != count(gb) || count(aa) != count(ab)) return nullptr;
+        for (size_t i = 0; i < count(aa); ++i) {
+            const JValue *x = aa->arr[i].get(), *y = ab->arr[i].get();
+            if (x->kind != JValue::Obj || y->kind != JValue::Obj || x->s("name") != y->s("name")) return nullptr;
+            const std::string fx = x->s("aggregate_expr"), fy = y->s("aggregate_expr");
+            if (fx != fy && !(is_distinct_count_tag(fx) && is_distinct_count_tag(fy))) return nullptr;
+        }
+        return c;
     }
 
     bool fields_of(const JValue *schema, std::vector<Field> *out) {
@@ -659,15 +707,34 @@ struct Builder {
         } else if (t == "hash_aggregate_exec") {
             n->kind = NKind::Aggregate;
             if (!parse_agg_mode(j->s("mode"), &n->mode)) { fail("aggregate mode '" + j->s("mode") + "'"); return nullptr; }
-            auto in = node(j->get("input"), depth + 1);
+            // COUNT(DISTINCT) (distinct.hpp A-D5): its Partial state is a List column.  Final / FinalPartitioned over the Partial of the same plan --
+            // identical group and aggregate lists, only repartitions / coalesces between -- is read as ONE aggregation over the Partial's input:
+            // `src` = the Partial, whose entries carry the argument expressions.  Any other Partial with a distinct count is refused.
+            const bool distinct = json_has_distinct_count(j);
+            const JValue *src = j;
+            if (distinct && n->mode == AggMode::Partial) {
+                fail("distinct_count in a Partial aggregate that is not read by the Final of the same plan: its partial state is a List column, and there is no list state at this boundary");
+                return nullptr;
+            }
+            if (distinct) {
+                src = partial_below(j);
+                n->single_pass = src != nullptr;
+                if (!src) src = j;
+            }
+            auto in = node(src->get("input"), depth + 1);
             if (!in) return nullptr;
-            const bool is_final = n->mode != AggMode::Partial;
+            if (distinct && !n->single_pass) {
+                fail("distinct_count in a " + std::string(agg_mode_name(n->mode)) + " aggregate that is not over the Partial of the same plan: there is no list state at this boundary");
+                return nullptr;
+            }
+            const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
+            const JValue *names = j->get("group_expr");   // (single pass: the upper node names the key columns)
             // A group key or an aggregate argument that is an EXPRESSION (GROUP BY a % 10, SUM(price * 2)): the stage that evaluates it
             // (Partial) gets a projection underneath that carries every input column through and the expression's value beside them
             // (the general evaluator, valprog.hpp); the aggregate then reads a column, as ever.  -1: refused (plan->why says why).
             bool wrapped = false;
             auto computed = [&](const JValue *e, const char *what) -> int { return computed_column(in, wrapped, e, what); };
-            const JValue *ge = j->get("group_expr");
+            const JValue *ge = src->get("group_expr");
             size_t gi = 0;
             if (ge && ge->kind == JValue::Arr)
                 for (auto &pair : ge->arr) {
@@ -682,19 +749,26 @@ struct Builder {
                     n->group.push_back(c);
                     Field f = in->schema[(size_t)c];
                     f.name = pair->arr[1]->kind == JValue::Str ? pair->arr[1]->str : f.name;
+                    if (n->single_pass && names->arr[gi]->kind == JValue::Arr && names->arr[gi]->arr.size() >= 2 && names->arr[gi]->arr[1]->kind == JValue::Str)
+                        f.name = names->arr[gi]->arr[1]->str;
                     n->schema.push_back(f);
                     ++gi;
                 }
-            const JValue *ae = j->get("aggr_expr");
+            const JValue *ae = src->get("aggr_expr");
             int state_at = (int)n->group.size();  // Final: position of the next aggregate's first state column
+            int n_distinct = 0;
             if (ae && ae->kind == JValue::Arr)
                 for (auto &x : ae->arr) {
                     Agg a;
                     a.name = x->s("name");
                     bool ts = false;
-                    if (!parse_type(x->get("data_type"), &a.type, &ts)) { fail("aggregate '" + a.name + "' of an unsupported type"); return nullptr; }
-                    if (!parse_agg_fn(x->s("aggregate_expr"), &a.fn)) {
-                        fail("aggregate function '" + x->s("aggregate_expr") + "' (supported: count, max, min, sum, avg)");
+                    const bool dc = is_distinct_count_tag(x->s("aggregate_expr"));
+                    if (!parse_type(x->get("data_type"), &a.type, &ts) && !(dc && !x->get("data_type"))) { fail("aggregate '" + a.name + "' of an unsupported type"); return nullptr; }
+                    if (dc) {
+                        a.fn = AggFn::CountDistinct;
+                        if (++n_distinct > kMaxDistinctCounts) { fail("more than " + std::to_string(kMaxDistinctCounts) + " distinct counts in one aggregate (each owns a table)"); return nullptr; }
+                    } else if (!parse_agg_fn(x->s("aggregate_expr"), &a.fn)) {
+                        fail("aggregate function '" + x->s("aggregate_expr") + "' (supported: count, max, min, sum, avg, distinct_count)");
                         return nullptr;
                     }
                     const std::string fn = agg_fn_name(a.fn);
@@ -705,6 +779,11 @@ struct Builder {
                         if ((size_t)state_at > in->schema.size()) { fail("final aggregate without its state column"); return nullptr; }
                     } else {
                         const JValue *arg = x->get("expr");
+                        const JValue *args = dc ? x->get("exprs") : nullptr;   // (the fork's tag cannot be checked: the argument under `exprs`, a list of one, or `expr`)
+                        if (args && args->kind == JValue::Arr) {
+                            if (args->arr.size() != 1) { fail("distinct_count over " + std::to_string(args->arr.size()) + " argument expressions: it takes one"); return nullptr; }
+                            arg = args->arr[0].get();
+                        }
                         if (arg && etag(arg) == "column") {
                             a.arg = resolve(arg, in->schema);
                             if (a.arg < 0) { fail("aggregate argument not in the input schema"); return nullptr; }
@@ -716,12 +795,13 @@ struct Builder {
                             return nullptr;
                         }
                     }
-                    if (a.fn == AggFn::Count) a.type = ColType::U64;
+                    if (dc && in->schema[(size_t)a.arg].type == ColType::F64) { fail("distinct_count needs an integer or Utf8 column"); return nullptr; }
+                    if (a.fn == AggFn::Count || dc) a.type = ColType::U64;
                     if (a.fn == AggFn::Avg) a.type = ColType::F64;
                     Field f;
                     f.nullable = true;
                     f.is_ts = ts && agg_is_minmax(a.fn);   // MIN / MAX of a Timestamp column is a Timestamp (q11's start_time / end_time)
-                    if (is_final) {
+                    if (is_final || n->single_pass) {
                         f.name = a.name;
                         f.type = a.type;
                         n->schema.push_back(f);
@@ -743,8 +823,8 @@ struct Builder {
             if (n->group.empty()) {
                 int accs = 0;
                 for (auto &a : n->aggs) {
-                    accs += agg_state_cols(a.fn);
-                    if (a.arg < 0) continue;
+                    accs += agg_accumulators(a.fn);
+                    if (a.arg < 0 || a.fn == AggFn::CountDistinct) continue;
                     const ColType at = in->schema[(size_t)a.arg].type;
                     if (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(a.fn) && a.fn != AggFn::Count)) { fail(std::string(agg_fn_name(a.fn)) + " needs an integer column"); return nullptr; }
                 }
@@ -1188,7 +1268,7 @@ inline void mark_co_partitioned(Plan *p, const Node *n, bool under) {
             if (n->join_partitioned) under = true;
             break;
         case NKind::Aggregate:
-            if (n->mode == AggMode::FinalPartitioned) under = true;
+            if (n->mode == AggMode::FinalPartitioned && !n->single_pass) under = true;   // (a single pass groups the rows itself, wherever they were placed)
             break;
         default:
             break;

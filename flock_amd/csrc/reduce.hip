@@ -381,6 +381,10 @@ __global__ __launch_bounds__(kFoldBlock) void global_fold_kernel(const ReducePro
             case (int32_t)ReduceOutKind::SumAsF64:
                 val = (uint64_t)__double_as_longlong(d.b ? (double)va : (double)(int64_t)va);
                 break;
+            case (int32_t)ReduceOutKind::AvgOnePass:
+                ok = n != 0;
+                val = ok ? (uint64_t)__double_as_longlong((d.b ? (double)va : (double)(int64_t)va) / (double)n) : 0;
+                break;
             default:   // AvgFinal
                 ok = va != 0;
                 val = ok ? (uint64_t)__double_as_longlong(__longlong_as_double((int64_t)vb) / (double)va) : 0;

@@ -43,6 +43,8 @@ enum class ReduceOutKind : int32_t {
     ValueAlways = 3, // Final COUNT: slot a, never NULL
     SumAsF64 = 4,    // AVG's sum state: (double) of the integer sum in slot a (b: the column is unsigned)
     AvgFinal = 5,    // Final AVG: Float64 sum of slot b / (double) integer sum of slot a; NULL while that is 0
+    AvgOnePass = 6,  // AVG finished in one pass (a node with a distinct count): (double) of the integer sum in slot a (b: unsigned) / (double) count of `col`;
+                     // NULL while the count is 0 -- the division Final makes of the one (count, sum) state row
 };
 struct ReduceOut {
     int32_t kind = 0;
