@@ -2,6 +2,7 @@
 // take() for fixed-width and Utf8 columns, in-place prefix sums.  Every multi-tile operation is
 // count -> scan -> emit (scan.hpp): no workgroup ever waits on another one inside a launch.
 #include "gather.hpp"
+#include "utf8_chunks.hpp"
 
 #include <algorithm>
 
@@ -613,7 +614,6 @@ __device__ __forceinline__ void utf8_emit_tile_at(const int32_t *__restrict__ sr
 // chunk one unaligned 16-byte load, four funnel shifts, one store) 3.8 ms with non-temporal stores, 1.48 with plain ones -- 64 lanes storing 16
 // bytes each 75 bytes apart cost the texture path a line per lane.  A kernel of its own: the short values' kernel -- q3's and q8's names --
 // runs eight workgroups per CU on 59 VGPRs.
-constexpr int kLongMapChunks = 8192;   // 16 KB of LDS: the chunk -> value map of a 128 KB output window
 __global__ __launch_bounds__(kBlock) void utf8_emit_long_kernel(const int32_t *__restrict__ src_off, const uint8_t *__restrict__ src, const int32_t *__restrict__ rows,
                                                                 int64_t n, const uint32_t *__restrict__ counts, const uint64_t *__restrict__ tile_base,
                                                                 const uint64_t *__restrict__ col_base, int32_t *__restrict__ out_off, uint8_t *__restrict__ out) {
@@ -665,88 +665,15 @@ __global__ __launch_bounds__(kBlock) void utf8_emit_long_kernel(const int32_t *_
         s_end[k * kBlock + threadIdx.x] = phase + excl[k] + len[k];
         s_b[k * kBlock + threadIdx.x] = b[k];
     }
-    const uint32_t end = phase + tile_bytes;
-    uint8_t *gout = out + (base - phase);  // 16-byte aligned
-    const uintptr_t sbase = reinterpret_cast<uintptr_t>(src);
-    // bytes 0 .. x - 1 of a dword, x clamped to 0 .. 4 (no branches: a clamp, a 64-bit shift whose low word runs empty at x = 4, a complement)
-    auto low_mask = [](int32_t x) -> uint32_t {
-        const uint32_t c = (uint32_t)min(max(x, 0), 4);
-        return ~(uint32_t)(0xffffffffull << (8u * c));
-    };
-    // sixteen chunk bytes from address A on (the byte at A lands on chunk byte 0; only chunk bytes a .. bnd - 1 are the value's -- the rest comes
-    // back as whatever the two aligned chunks around them hold, or zero).  An aligned 16-byte chunk that holds at least one byte of the value
-    // never crosses a page: only such chunks are read.
-    auto realigned = [&](uintptr_t A, uint32_t a, uint32_t bnd, uint32_t (&V4)[4]) {
-        const uint32_t sh = (uint32_t)(A & 15), qd = sh >> 2, bs = (sh & 3) * 8;
-        const uint4 *q = reinterpret_cast<const uint4 *>(A & ~uintptr_t(15));
-        uint4 c0 = make_uint4(0, 0, 0, 0), c1 = make_uint4(0, 0, 0, 0);
-        if (bnd > a && sh + a < 16u) c0 = q[0];
-        if (bnd > a && sh + bnd > 16u) c1 = q[1];
-        // the window of five dwords that starts `qd` dwords into the eight: two rounds of bit-selects (by one dword, by two) -- a lane's qd is
-        // its own, and the four-way choice written with ?: came back from the compiler as four divergent copies of everything behind it
-        const uint32_t W[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-        const uint32_t by1 = 0u - (qd & 1u), by2 = 0u - (qd >> 1);
-        uint32_t X[7], V[5];
+    uint32_t start[kLenItems], index[kLenItems];
 #pragma unroll
-        for (int j = 0; j < 7; ++j) X[j] = (W[j + 1] & by1) | (W[j] & ~by1);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) V[j] = (X[j + 2] & by2) | (X[j] & ~by2);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) V4[i] = __funnelshift_r(V[i], V[i + 1], bs);
-    };
-    const uint32_t n_chunks = (end + 15u) >> 4;
-    for (uint32_t cbase = 0; cbase < n_chunks; cbase += (uint32_t)kLongMapChunks) {   // (one round for tiles up to 128 KB: 128 bytes a value)
-        const uint32_t cend = cbase + (uint32_t)kLongMapChunks < n_chunks ? cbase + (uint32_t)kLongMapChunks : n_chunks;
-        // ---- every value names itself in the chunks whose first in-tile byte it holds: from the first 16-byte boundary at or behind its start
-        // (the tile's very first chunk for the value that starts the tile) to the chunk of its last byte
-        __syncthreads();   // (the lists above are complete; the previous round's map has been read)
-#pragma unroll
-        for (int k = 0; k < kLenItems; ++k) {
-            if (len[k] == 0) continue;
-            const uint32_t p0 = phase + excl[k], p1 = p0 + len[k];
-            uint32_t c = p0 == phase ? 0u : (p0 + 15u) >> 4;
-            const uint32_t c_last = (p1 - 1u) >> 4;
-            if (c < cbase) c = cbase;
-            for (; c <= c_last && c < cend; ++c) s_first[c - cbase] = (uint16_t)(k * kBlock + threadIdx.x);
-        }
-        __syncthreads();
-        // ---- every lane makes whole chunks of the output
-        for (uint32_t ci = cbase + threadIdx.x; ci < cend; ci += kBlock) {
-            const uint32_t o = ci << 4, c_lo = o < phase ? phase : o, chi = o + 16 < end ? o + 16 : end;
-            uint32_t v = s_first[ci - cbase];
-            // the value the chunk starts in, and the one behind it: two pieces with ONE split between them is what a chunk of long values holds
-            const uint32_t p0 = v ? s_end[v - 1] : phase, p1 = s_end[v], hi1 = p1 < chi ? p1 : chi;
-            const uint32_t w = v + 1 < (uint32_t)kLenTile ? v + 1 : v;
-            const uint32_t q1 = s_end[w], hi2 = hi1 < chi ? (q1 < chi ? q1 : chi) : hi1;
-            uint32_t P1[4], P2[4], acc[4];
-            realigned(sbase + (uint32_t)s_b[v] + o - p0, c_lo - o, hi1 - o, P1);
-            realigned(sbase + (uint32_t)s_b[w] + o - p1, hi1 - o, hi2 - o, P2);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const uint32_t m = low_mask((int32_t)(hi1 - o) - 4 * i);   // chunk bytes below the split are the first value's
-                acc[i] = (P1[i] & m) | (P2[i] & ~m);
-            }
-            uint32_t pos = hi2;
-            if (pos < chi) {   // (short values in a long column: a third piece and more, one by one under range masks)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] &= low_mask((int32_t)(pos - o) - 4 * i);
-                for (v = w + 1; pos < chi; ++v) {
-                    const uint32_t e = s_end[v], hi = e < chi ? e : chi;
-                    if (hi <= pos) continue;   // (an empty value)
-                    uint32_t P[4];
-                    realigned(sbase + (uint32_t)s_b[v] + o - s_end[v - 1], pos - o, hi - o, P);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i] |= P[i] & low_mask((int32_t)(hi - o) - 4 * i) & ~low_mask((int32_t)(pos - o) - 4 * i);
-                    pos = hi;
-                }
-            }
-            if (o >= phase && o + 16 <= end) {
-                stream_store4(gout + o, make_uint4(acc[0], acc[1], acc[2], acc[3]));
-            } else {  // the tile's first / last chunk is shared with the neighbouring tile: only this tile's bytes
-                for (uint32_t c = c_lo; c < chi; ++c) gout[c] = (uint8_t)(acc[(c - o) >> 2] >> (8 * ((c - o) & 3)));
-            }
-        }
+    for (int k = 0; k < kLenItems; ++k) {
+        start[k] = phase + excl[k];
+        index[k] = (uint32_t)(k * kBlock + threadIdx.x);
     }
+    const uintptr_t sbase = reinterpret_cast<uintptr_t>(src);
+    utf8_emit_chunks<kLenTile, kLenItems>(s_end, [&](uint32_t v) { return sbase + (uint32_t)s_b[v]; }, s_first, start, len, index, phase, phase + tile_bytes,
+                                          out + (base - phase));   // (utf8_chunks.hpp)
 }
 
 __device__ __forceinline__ void utf8_emit_tile(const int32_t *__restrict__ src_off, const uint8_t *__restrict__ src,

@@ -24,6 +24,7 @@
 #include "distinct.hpp"
 #include "reduce.hpp"
 #include "strmatch.hpp"
+#include "textsel.hpp"
 #include "valprog.hpp"
 
 using namespace flockgpu;
@@ -778,10 +779,11 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
         pred_text(n->pred.get(), n->schema, os);
         os << ")";
     }
-    if (n->kind == NKind::Project) {   // the columns computed with a scalar function, as `name = expression`
+    if (n->kind == NKind::Project) {   // the columns computed with a scalar function, and the text-valued ones, as `name = expression`
         bool any = false;
         for (size_t i = 0; i < n->proj.size(); ++i) {
-            if (!holds_func(n->proj[i].first.get())) continue;
+            const bool text = n->proj[i].first->kind != EKind::Col && i < n->schema.size() && n->schema[i].type == ColType::UTF8;   // 'bid', CASE ... (textsel.hpp)
+            if (!holds_func(n->proj[i].first.get()) && !text) continue;
             os << (any ? ", " : "(") << n->proj[i].second << " = ";
             pred_text(n->proj[i].first.get(), n->in[0]->schema, os);
             any = true;
@@ -2031,6 +2033,89 @@ struct Exec {
         return val_unsupported("an expression of an unknown kind");
     }
 
+    // ---- text-valued expressions (textsel.hpp): `e` -> its sources in `tt` and its SELECTOR pushed onto `b` -- an Int32 value, the index of the source
+    // the row takes; a NULL where the row has no value.  CASE is val_compile's CASE with the branches compiled here (nested CASE: nested Select).
+    int text_full() { return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d distinct sources or %d bytes of literals in one Utf8-valued expression", kTextMaxSources, kTextMaxLiteralBytes); }
+    int text_compile(const Expr *e, const Table &in, ValBuilder &b, TextTable &tt, bool *may_null) {
+        auto source = [&](int idx) { return idx < 0 ? text_full() : b.push(ValOpKind::Const, ValType::I32, 0, b.add_const((uint64_t)idx)) ? FLOCKGPU_OK : val_full(); };
+        auto null = [&]() {
+            *may_null = true;
+            return b.push(ValOpKind::Null, ValType::I32, 0) ? FLOCKGPU_OK : val_full();
+        };
+        switch (e->kind) {
+            case EKind::LitS: return source(tt.add_literal(e->s));
+            case EKind::LitNull: return null();
+            case EKind::Cast:
+                if (e->cast_to != ColType::UTF8) return val_unsupported("CASE branches of different types");
+                return text_compile(e->l.get(), in, b, tt, may_null);
+            case EKind::Col: {
+                const TCol &c = in.cols[(size_t)e->col];
+                if (c.c.type != ColType::UTF8) return val_unsupported("CASE branches of different types");
+                if (c.c.all_null) return null();
+                if (!c.present || !c.c.offsets) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
+                return source(tt.add_column(c.c));   // (its NULLs: the kernels read the column's validity bytes)
+            }
+            case EKind::Case: {
+                if (e->r) FG_TRY(text_compile(e->r.get(), in, b, tt, may_null));
+                else FG_TRY(null());
+                for (size_t i = e->list.size(); i >= 2; i -= 2) {
+                    const Expr *w = e->list[i - 2].get(), *th = e->list[i - 1].get();
+                    if (e->l) {   // CASE x WHEN v: x = v
+                        const int tc = val_common_type(e->l.get(), w, in, -1);
+                        if (tc < 0 || tc > 3) return val_unsupported("CASE operand and WHEN value without one numeric type");
+                        int t1 = -1, t2 = -1;
+                        FG_TRY(val_compile(e->l.get(), in, b, tc, &t1, may_null));
+                        FG_TRY(val_compile(w, in, b, tc, &t2, may_null));
+                        if (t1 != tc || t2 != tc) return val_unsupported("CASE operand and WHEN value of different types");
+                        if (!b.push(ValOpKind::Eq, (ValType)tc, 2)) return val_full();
+                    } else {
+                        int tw = -1;
+                        FG_TRY(val_compile(w, in, b, 5, &tw, may_null));
+                        if (tw != 5) return val_unsupported("a WHEN that is not Boolean");
+                    }
+                    FG_TRY(text_compile(th, in, b, tt, may_null));
+                    if (!b.push(ValOpKind::Select, ValType::I32, 3)) return val_full();
+                }
+                return FLOCKGPU_OK;
+            }
+            default: return val_unsupported("CASE branches of different types");
+        }
+    }
+    // Column i of projection `n` as text: the selector through the evaluator (none for a bare literal or column), then the length and emit passes
+    int project_text(const Node *n, size_t i, const Table &in, TCol *o) {
+        const Expr *e = n->proj[i].first.get();
+        ValBuilder vb;
+        TextTable tt;
+        bool may_null = false;
+        FG_TRY(text_compile(e, in, vb, tt, &may_null));
+        const int64_t rows = std::max<int64_t>(in.rows, 0);
+        const int32_t *sel = nullptr;
+        const uint8_t *sel_valid = nullptr;
+        const bool bare = vb.p.n_ops == 1;   // one push: a literal, a column, a NULL
+        if (bare && tt.s.k == 1 && tt.s.src[0].offsets) {   // CAST(column AS Utf8): the column itself
+            const Expr *c = e;
+            while (c->kind == EKind::Cast) c = c->l.get();
+            *o = in.cols[(size_t)c->col];
+            o->c.nullable = true;
+            return FLOCKGPU_OK;
+        }
+        if (!bare) {
+            void *vals = nullptr;
+            uint8_t *vv = nullptr;
+            FG_TRY(arena_get(ctx, node_key(pl, n, "val", (int)i).c_str(), ((size_t)rows + 2) * 8, &vals));
+            if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, "valv", (int)i).c_str(), (size_t)rows + 16, &vv));
+            FG_TRY(valprog_to_column(ctx, node_key(pl, n, "vprog", (int)i).c_str(), vb.p, in.rows, ColType::I32, vals, vv));
+            sel = static_cast<const int32_t *>(vals);
+            sel_valid = vv;
+        }
+        DevColumn out;
+        FG_TRY(text_select(ctx, node_key(pl, n, "text", (int)i).c_str(), tt.s, sel, sel_valid, in.rows, &out));
+        *o = dev_col(ColType::UTF8, out.values, out.offsets, out.bytes);
+        o->c.valid = out.valid;
+        o->c.nullable = true;
+        return FLOCKGPU_OK;
+    }
+
     // A filter's input table and its predicate compiled for it: the one-pass program of pred.hpp (*general = false, `b`), or -- a predicate that
     // program has no leaf for (arithmetic inside a comparison, CASE, casts of computed values) -- the general evaluator's (*general = true, `vb`),
     // which writes the same flag words + wave counts
@@ -2258,6 +2343,10 @@ struct Exec {
             if (!n->required[i]) continue;
             if (e->kind == EKind::Col) {
                 o = in.cols[(size_t)e->col];
+                continue;
+            }
+            if (n->schema[i].type == ColType::UTF8) {   // a text literal, CAST(column AS Utf8), CASE with text branches (textsel.hpp)
+                FG_TRY(project_text(n, i, in, &o));
                 continue;
             }
             // literal * CAST(Int32 column AS Float64): q1's currency conversion (planner.rs:90), one IEEE multiply

@@ -14,6 +14,8 @@
 // its one argument under `exprs` or `expr` (distinct.hpp A-D1..A-D7).  That aggregate's Partial state is a List column, which this boundary does not
 // carry: Final / FinalPartitioned over the Partial of the same plan becomes ONE single-pass node over the Partial's input (Node::single_pass); a Partial
 // with a distinct count that anything else consumes is refused.
+// A computed expression ends in a number (the general evaluator, valprog.hpp) or in TEXT: a Utf8 literal, a Utf8 column or a CASE whose branches are such
+// (textsel.hpp A-T1..A-T5) -- as a projected column and, through computed_column, as a GROUP BY / ORDER BY key or a COUNT / COUNT(DISTINCT) argument.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -23,6 +25,7 @@
 #include "plan_json.hpp"
 #include "relops.hpp"
 #include "strmatch.hpp"
+#include "textsel.hpp"
 
 namespace flockgpu {
 namespace ir {
@@ -72,7 +75,7 @@ inline int expr_static_type(const Expr *e, const std::vector<Field> &schema) {
         case EKind::LitF: return 3;
         case EKind::LitS: return 4;
         case EKind::LitB: return 5;
-        case EKind::LitNull: return -1;
+        case EKind::LitNull: return e->lit_kind == "Utf8" ? 4 : -1;   // ({"Utf8": null} is a NULL of type Utf8, textsel.hpp A-T1; every other NULL takes the type it meets)
         case EKind::Cast: return (int)e->cast_to;
         case EKind::Neg: return expr_static_type(e->l.get(), schema);
         case EKind::Not: case EKind::IsNull: case EKind::IsNotNull: case EKind::InList: return 5;
@@ -570,6 +573,61 @@ struct Builder {
         return true;
     }
 
+    // A text-valued expression (textsel.hpp A-T1) in a value position: its sources -- distinct literals and columns -- are collected for the A-T5
+    // limits; a branch of another type is refused.
+    bool text_sources(const Expr *e, const std::vector<Field> &schema, std::set<std::string> *lits, std::set<int> *cols) {
+        switch (e->kind) {
+            case EKind::LitS: lits->insert(e->s); return true;
+            case EKind::LitNull: return true;
+            case EKind::Col:
+                if (schema[(size_t)e->col].type != ColType::UTF8) return fail("CASE branches of different types");
+                cols->insert(e->col);
+                return true;
+            case EKind::Cast: {
+                if (e->cast_to != ColType::UTF8) return fail("CASE branches of different types");
+                const int from = expr_static_type(e->l.get(), schema);
+                if (from != 4 && from != -1) return fail("CAST between other than numeric types inside a computed expression");
+                return text_sources(e->l.get(), schema, lits, cols);
+            }
+            case EKind::Case:
+                for (size_t i = 1; i < e->list.size(); i += 2)
+                    if (!text_sources(e->list[i].get(), schema, lits, cols)) return false;
+                return !e->r || text_sources(e->r.get(), schema, lits, cols);
+            default: return fail("CASE branches of different types");
+        }
+    }
+    // `e` of static type Utf8 is a text-valued expression within the limits of one source table
+    bool check_text(const Expr *e, const std::vector<Field> &schema) {
+        std::set<std::string> lits;
+        std::set<int> cols;
+        if (!text_sources(e, schema, &lits, &cols)) return false;
+        if (lits.size() + cols.size() > (size_t)kTextMaxSources)
+            return fail("more than " + std::to_string(kTextMaxSources) + " distinct sources (literals plus columns) in one Utf8-valued expression");
+        size_t bytes = 0;
+        for (auto &l : lits) bytes += l.size();
+        if (bytes > (size_t)kTextMaxLiteralBytes) return fail("more than " + std::to_string(kTextMaxLiteralBytes) + " bytes of literals in one Utf8-valued expression");
+        return true;
+    }
+    // a CASE anywhere in a numeric expression whose branches hold text beside numbers (the static type is the first typed branch's)
+    bool check_case_types(const Expr *e, const std::vector<Field> &schema) {
+        if (!e) return true;
+        if (e->kind == EKind::Case) {
+            bool text = false, other = false;
+            auto see = [&](const Expr *b) {
+                const int t = expr_static_type(b, schema);
+                text = text || t == 4;
+                other = other || (t >= 0 && t != 4);
+            };
+            for (size_t i = 1; i < e->list.size(); i += 2) see(e->list[i].get());
+            if (e->r) see(e->r.get());
+            if (text && other) return fail("CASE branches of different types");
+        }
+        if (!check_case_types(e->l.get(), schema) || !check_case_types(e->r.get(), schema)) return false;
+        for (auto &x : e->list)
+            if (!check_case_types(x.get(), schema)) return false;
+        return true;
+    }
+
     // An EXPRESSION where an operator reads a column (GROUP BY a % 10, SUM(price * 2), ORDER BY a + b): `in` gets a projection on top (once:
     // `wrapped`) that carries every column through and the expression's value beside them (the general evaluator, valprog.hpp); returns the
     // new column's index in the wrapped schema, -1 when refused (`err` says why).
@@ -593,7 +651,9 @@ struct Builder {
         auto x = expr(e, below);
         if (!x) return -1;
         const int ty = expr_static_type(x.get(), below);
-        if (ty < 0 || ty > 3) { fail(std::string(what) + " over an expression without a numeric type"); return -1; }
+        if (!check_case_types(x.get(), below)) return -1;
+        if (ty == 4 && !check_text(x.get(), below)) return -1;   // a text-valued key / argument (textsel.hpp)
+        if (ty < 0 || ty > 4) { fail(std::string(what) + " over an expression without a numeric type"); return -1; }
         Field f;
         f.name = "#" + std::to_string(in->schema.size());
         f.type = (ColType)ty;
@@ -692,9 +752,11 @@ struct Builder {
                 if (e->kind == EKind::Col) {
                     const Field &src = in->schema[(size_t)e->col];
                     f.type = src.type; f.is_ts = src.is_ts; f.nullable = src.nullable;
-                } else {   // computed: q1's `literal * column` kernel, or the general evaluator (valprog.hpp) -- a numeric result either way
+                } else {   // computed: q1's `literal * column` kernel or the general evaluator (valprog.hpp) for a numeric result, textsel.hpp for text
                     const int ty = expr_static_type(e.get(), in->schema);
-                    if (ty < 0 || ty > 3) { fail(ty == 5 ? "projection of a Boolean expression (no Boolean columns at this boundary)" : "projection expression without a numeric type"); return nullptr; }
+                    if (!check_case_types(e.get(), in->schema)) return nullptr;
+                    if (ty == 4 && !check_text(e.get(), in->schema)) return nullptr;
+                    if (ty < 0 || ty > 4) { fail(ty == 5 ? "projection of a Boolean expression (no Boolean columns at this boundary)" : "projection expression without a numeric type"); return nullptr; }
                     if (!check_like(e.get(), in->schema, false)) return nullptr;
                     f.type = (ColType)ty;
                     f.nullable = true;

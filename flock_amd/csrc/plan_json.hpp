@@ -55,6 +55,16 @@ struct JParser {
                     case 'u': {
                         if (end - p < 5) return fail("bad \\u escape");
                         unsigned v = (unsigned)strtoul(std::string(p + 1, p + 5).c_str(), nullptr, 16);
+                        // a surrogate pair (how JSON writes a code point above U+FFFF) is ONE code point of four UTF-8 bytes
+                        if (v >= 0xD800 && v < 0xDC00 && end - p >= 11 && p[5] == '\\' && p[6] == 'u') {
+                            const unsigned lo = (unsigned)strtoul(std::string(p + 7, p + 11).c_str(), nullptr, 16);
+                            if (lo >= 0xDC00 && lo < 0xE000) {
+                                const unsigned cp = 0x10000 + ((v - 0xD800) << 10) + (lo - 0xDC00);
+                                out += (char)(0xF0 | (cp >> 18)); out += (char)(0x80 | ((cp >> 12) & 0x3F)); out += (char)(0x80 | ((cp >> 6) & 0x3F)); out += (char)(0x80 | (cp & 0x3F));
+                                p += 10;
+                                break;
+                            }
+                        }
                         if (v < 0x80) out += (char)v;
                         else if (v < 0x800) { out += (char)(0xC0 | (v >> 6)); out += (char)(0x80 | (v & 0x3F)); }
                         else { out += (char)(0xE0 | (v >> 12)); out += (char)(0x80 | ((v >> 6) & 0x3F)); out += (char)(0x80 | (v & 0x3F)); }

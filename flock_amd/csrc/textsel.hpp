@@ -1,0 +1,95 @@
+// Utf8-VALUED expressions of ProjectionExec (textsel.hip): text literals, Utf8 columns and CASE whose branches are text.  The numeric evaluator
+// (valprog.hpp) stays what it was: the expression is lowered on the host (plan.hip text_compile) into
+//   a SELECTOR  the same CASE with every text branch replaced by the index of its SOURCE (0 .. K - 1) and NULL kept NULL: an Int32 program of
+//               the existing interpreter, nested CASE as nested Select.  A bare literal or column has no selector;
+//   a SOURCE TABLE (TextSources, passed by value): K entries, each a literal (offset and length in a pool of at most kTextMaxLiteralBytes) or a
+//               Utf8 column of the input (offsets, bytes, validity bytes);
+// and two kernels turn (selector, table) into an ordinary Utf8 column -- int32 offsets, bytes, validity bytes:
+//   length pass  per row the selected source's length (a literal's from the table in LDS, a column's from its two offsets) -> one byte count per
+//                wave for the tile scan (scan.hpp), and the result's validity bytes where a NULL can occur;
+//   -- tile scan; the total goes to pinned memory; the host waits once, checks it against 2^31 and sizes the byte buffer --
+//   emit pass    offsets (one aligned 16-byte store per lane: a lane owns four consecutive rows) and bytes.  A tile whose bytes fit kTextStageBytes
+//                (literals, short values) is assembled in LDS and streamed out as aligned 16-byte chunks, the two chunks it shares with its
+//                neighbour tiles byte by byte (textsel_emit_kernel); every larger tile -- long column values, up to single values of any length --
+//                goes through the take's chunk-wise copy for long values (utf8_chunks.hpp, shared with gather.hip utf8_emit_long_kernel) over
+//                the tile's (address, length) list in LDS (textsel_emit_long_kernel): every lane builds whole 16-byte output chunks.
+// A projection of literals alone (NEXMark q14's bid_time_type) reads nothing but the selector; a bare literal is one fill.
+//
+// Dialect and semantics (DataFusion ~6 CaseExpr / Literal; like valprog.hpp's A-V / A-F lists ASSUMPTIONS, not reference-held vectors -- checked
+// against tests/text_expr_ref.py and, there, against pyarrow.compute.case_when):
+//   A-T1 a text-valued expression is a Utf8 literal ({"Utf8": null}: a NULL of type Utf8), a Utf8 column (a cast_expr to Utf8 may sit in front),
+//        or a case_expr whose THEN / ELSE branches are text-valued or untyped NULL literals (nested CASE counts).  Its static type is Utf8; leading
+//        NULL branches do not hide it.  A CASE that mixes text and numeric branches is refused ("CASE branches of different types");
+//   A-T2 CASE picks the first WHEN that is TRUE (NULL and FALSE are not), else ELSE, else NULL; `CASE WHEN cond` and `CASE base WHEN value` are
+//        both taken; conditions, base and value are what the general evaluator takes (numeric, Timestamp, scalar functions, IS NULL, IN, Kleene
+//        AND / OR / NOT) and every one of them is evaluated for every row (A-V7: a zero divisor in a branch that is never chosen fails the call);
+//   A-T3 '' is a value, not NULL; a chosen column whose row is NULL gives NULL; bytes are copied verbatim (no validation, no normalisation);
+//        the result is nullable;
+//   A-T4 taken as a projection_exec output column and, through the projection computed_column puts underneath, as a GROUP BY key, an ORDER BY
+//        key, the argument of COUNT / COUNT(DISTINCT) and a DISTINCT column -- hence under and over filters, joins, sorts, limits and in stage
+//        plans.  The result is an ordinary Utf8 column every consumer reads unchanged; its bytes do not depend on batching or grid shape;
+//   A-T5 refused by name at create / explain: more than kTextMaxSources distinct sources (literals plus columns) in one expression, more than
+//        kTextMaxLiteralBytes bytes of (distinct) literals in one expression.  Refused at execute: a result of 2^31 bytes or more, checked on
+//        the published total before any byte is written.
+//   Still refused, as before: a Utf8 column or literal inside a condition or under an operator, LIKE inside a computed expression, text-producing
+//   scalar functions, Boolean projections, hash partitioning on a computed expression, MIN / MAX of text.
+#pragma once
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "relops.hpp"
+
+namespace flockgpu {
+
+constexpr int kTextMaxSources = 16;
+constexpr int kTextMaxLiteralBytes = 1024;
+constexpr int kTextTile = 1024;          // rows of a workgroup: four consecutive rows per lane
+constexpr int kTextStageBytes = 16384;   // the LDS stage of the emit pass: a tile of more bytes takes the chunk-wise kernel
+
+struct TextSource {
+    const int32_t *offsets;   // column source; null: a literal
+    const uint8_t *bytes;
+    const uint8_t *valid;     // column source with NULLs: one byte per row
+    uint32_t lit_off, lit_len;   // literal: where it lies in the pool (a multiple of four), its length
+};
+struct TextSources {
+    TextSource src[kTextMaxSources];
+    uint32_t pool[(kTextMaxLiteralBytes + 4 * kTextMaxSources) / 4];   // the literals, each from a 4-byte boundary on
+    int32_t k = 0;
+    int32_t n_cols = 0;   // column sources among the k
+};
+
+// Host-side assembly: every add returns the source's index (a literal or column that is already there: its index), -1 when the table is full.
+struct TextTable {
+    TextSources s{};
+    uint32_t pool_used = 0;
+    std::vector<std::string> lits;   // by source index ("" for a column)
+    int add_literal(const std::string &v) {
+        for (int i = 0; i < s.k; ++i)
+            if (!s.src[i].offsets && lits[(size_t)i] == v) return i;
+        if (s.k >= kTextMaxSources || pool_used + v.size() > sizeof(s.pool)) return -1;
+        TextSource &t = s.src[s.k];
+        t = TextSource{nullptr, nullptr, nullptr, pool_used, (uint32_t)v.size()};
+        std::memcpy(reinterpret_cast<uint8_t *>(s.pool) + pool_used, v.data(), v.size());
+        pool_used = (pool_used + (uint32_t)v.size() + 3u) & ~3u;
+        lits.push_back(v);
+        return s.k++;
+    }
+    int add_column(const DevColumn &c) {
+        for (int i = 0; i < s.k; ++i)
+            if (s.src[i].offsets == c.offsets && s.src[i].bytes == c.values && s.src[i].valid == c.valid) return i;
+        if (s.k >= kTextMaxSources) return -1;
+        s.src[s.k] = TextSource{c.offsets, static_cast<const uint8_t *>(c.values), c.valid, 0, 0};
+        lits.emplace_back();
+        ++s.n_cols;
+        return s.k++;
+    }
+};
+
+// out = for every row i the value of source sel[i] (sel null: source 0 for every row); a row whose sel_valid byte is 0 (sel_valid may be null) or
+// whose chosen column holds a NULL there is NULL.  No source at all: every row NULL.  Offsets, bytes and validity live in the ctx arena under
+// `name`.  One host wait (the byte total); none for a bare literal or an empty result.
+int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &srcs, const int32_t *sel, const uint8_t *sel_valid, int64_t rows, DevColumn *out);
+
+}  // namespace flockgpu

@@ -89,7 +89,10 @@ typedef struct flockgpu_plan flockgpu_plan;
  * global_limit_exec / local_limit_exec, window_agg_exec (ROW_NUMBER()).
  * Expressions (`physical_expr` tags): column, literal, cast_expr, try_cast_expr, binary_expr (Eq NotEq Lt LtEq Gt GtEq And Or Plus Minus
  * Multiply Divide Modulo), not_expr, is_null_expr, is_not_null_expr, negative_expr, in_list_expr, case_expr -- over Int32 / Int64 / UInt64 /
- * Float64 / Timestamp(Millisecond) values (Utf8: =, <>, IN, IS NULL against literals).  Both operands of a binary operator have one type,
+ * Float64 / Timestamp(Millisecond) values (Utf8: =, <>, IN, IS NULL against literals).  A computed value may also be TEXT: a Utf8 literal, a Utf8
+ * column (under a cast to Utf8) or a case_expr whose THEN / ELSE branches are such or NULL -- as a projected column, a GROUP BY / ORDER BY key, the
+ * argument of COUNT / COUNT(DISTINCT); at most 16 distinct sources and 1024 bytes of literals per expression, a result below 2^31 bytes; text inside a
+ * condition or under an operator stays refused.  Both operands of a binary operator have one type,
  * as the reference's planner leaves them.  At execute, integer division / modulo by zero in a row whose operands are not NULL and a
  * CAST whose value does not fit its target are FLOCKGPU_ERR_INVALID for the call (the reference's execute fails with an ArrowError);
  * TRY_CAST yields NULL instead. */
