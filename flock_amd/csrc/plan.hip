@@ -20,6 +20,7 @@
 
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
+#include "cross.hpp"
 #include "pred.hpp"
 #include "distinct.hpp"
 #include "reduce.hpp"
@@ -769,6 +770,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     const char *kind = kinds[(int)n->kind];
     if (n->kind == NKind::Join && n->join_type == JoinType::Semi) kind = "SemiJoin";
     if (n->kind == NKind::Join && n->join_type == JoinType::Anti) kind = "AntiJoin";
+    if (n->kind == NKind::Join && n->join_type == JoinType::Cross) kind = "CrossJoin";
     os << std::string((size_t)depth * 2, ' ') << kind;
     if (n->kind == NKind::Aggregate) os << "(" << agg_mode_name(n->mode) << (n->single_pass ? ", single pass" : "") << ")";
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
@@ -829,7 +831,8 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     os << "\n";
     if (f != kNone) return;  // the fused pipeline swallows the sub-tree
     for (size_t i = 0; i < n->in.size(); ++i)
-        describe(pl, n->in[i].get(), depth + 1, os, keys_only || (i == 1 && n->kind == NKind::Join && n->join_type != JoinType::Inner));
+        describe(pl, n->in[i].get(), depth + 1, os,   // (a cross join prunes both sides to what is read above it: its scans say what they upload, too)
+                 keys_only || (n->kind == NKind::Join && (n->join_type == JoinType::Cross || (i == 1 && n->join_type != JoinType::Inner))));
 }
 
 // The whole plan is one NEXMark pipeline when, below pure projections, its root is a fused node (or q1's projection).
@@ -878,7 +881,7 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     for (auto &a : n->aggs) *o += std::to_string((int)a.fn) + "." + std::to_string(a.arg) + "." + std::to_string(a.arg2) + "." + std::to_string((int)a.type) + ",";
     *o += "|";
     for (auto &k : n->on) *o += std::to_string(k.l) + "=" + std::to_string(k.r) + ",";   // (every key pair)
-    *o += std::string(n->join_partitioned ? "p" : "") + (n->join_type == JoinType::Semi ? "s" : n->join_type == JoinType::Anti ? "a" : "") + "|";
+    *o += std::string(n->join_partitioned ? "p" : "") + (n->join_type == JoinType::Semi ? "s" : n->join_type == JoinType::Anti ? "a" : n->join_type == JoinType::Cross ? "x" : "") + "|";
     for (int c : n->hash_cols) *o += std::to_string(c) + ",";
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
     for (auto &k : n->sort_cols) *o += std::to_string(k.col) + (k.descending ? "d" : "a") + (k.nulls_first ? "f" : "l") + ",";
@@ -2167,7 +2170,7 @@ struct Exec {
         if (pl->fused[(size_t)n->id].kind == kNone) {
             if (n->kind == NKind::Repartition) return exec_lazy(n->in[0].get(), z);
             // a Semi / Anti join is a choice of rows of its left input, like a filter: nothing is taken until the consumer's output
-            if (n->kind == NKind::Join && n->join_type != JoinType::Inner) return exec_semi_lazy(n, z);
+            if (n->kind == NKind::Join && (n->join_type == JoinType::Semi || n->join_type == JoinType::Anti)) return exec_semi_lazy(n, z);
             if (n->kind == NKind::Filter) {
                 int32_t *rows = nullptr;
                 int64_t n_out = 0;
@@ -2299,7 +2302,7 @@ struct Exec {
             case NKind::Sort: return exec_sort(n, -1, t);
             case NKind::Window: return exec_window(n, t);
             case NKind::Limit: return exec_limit(n, t);
-            case NKind::Join: return exec_join(n, t);
+            case NKind::Join: return n->join_type == JoinType::Cross ? exec_cross(n, t) : exec_join(n, t);
             case NKind::Aggregate: {
                 const std::string &sig = pl->twin_sig[(size_t)n->id];
                 if (sig.empty()) return exec_aggregate(n, t);
@@ -2644,6 +2647,65 @@ struct Exec {
         }
         FG_TRY(join_key64(ctx, node_key(pl, n, "join").c_str(), kl, nl, kr, nr, &lrows, &rrows, &pairs));
         return emit_pairs(n, ZL, ZR, lrows, rrows, pairs, t);
+    }
+
+    // CrossJoinExec (cross.hpp A-X1..6): L x R rows, pair (i, j) at row i * R + j, no pair lists -- left columns are repeats, right columns tiles,
+    // produced for the columns somebody reads.  A side with a row list is taken once (L or R rows) and the result replicated.  A side of exactly one
+    // row -- a global aggregate's -- leaves the other side's columns what they are (no kernel, no copy) and becomes fills.
+    int exec_cross(const Node *n, Table *t) {
+        Lazy Z[2];
+        FG_TRY(exec_lazy(n->in[0].get(), &Z[0]));
+        FG_TRY(exec_lazy(n->in[1].get(), &Z[1]));
+        const int64_t L = std::max<int64_t>(Z[0].rows, 0), R = std::max<int64_t>(Z[1].rows, 0);
+        const size_t nl = Z[0].base.cols.size();
+        // (A-X6) the row count, before anything of the result exists
+        int64_t rows = 0;
+        if (!cross_rows_ok(L, R, &rows))
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: cross join (node %d) of %lld x %lld rows: more than 2^31 rows", n->id, (long long)L, (long long)R);
+        t->rows = rows;
+        t->cols.assign(n->schema.size(), TCol{});
+        if (nl + Z[1].base.cols.size() != n->schema.size()) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a cross join whose inputs are not its schema");
+        // each side as a plain table of the columns somebody reads: its base, or ONE take through its row list (no rows at all: the empty take, A-X4)
+        Table side;
+        side.cols.assign(n->schema.size(), TCol{});
+        for (int s = 0; s < 2; ++s) {
+            const size_t first = s ? nl : 0;
+            if (Z[s].via || rows == 0) {
+                FG_TRY(take_table(n, Z[s].base, n->required, Z[s].via, rows == 0 ? 0 : Z[s].rows, (int)first, &side));
+            } else {
+                for (size_t i = 0; i < Z[s].base.cols.size(); ++i) {
+                    side.cols[first + i] = Z[s].base.cols[i];
+                    if (!n->required[first + i]) side.cols[first + i].present = false;
+                }
+            }
+        }
+        if (rows == 0) {
+            *t = side;
+            t->rows = 0;
+            return FLOCKGPU_OK;
+        }
+        // (A-X6) every Utf8 column's bytes, before anything of the result exists
+        for (size_t i = 0; i < side.cols.size(); ++i) {
+            const TCol &c = side.cols[i];
+            int64_t bytes = 0;
+            if (c.present && c.c.type == ColType::UTF8 && !cross_bytes_ok(c.c.bytes, i < nl ? R : L, &bytes))
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: cross join (node %d) of %lld x %lld rows: Utf8 column '%s' exceeds 2^31 bytes", n->id, (long long)L,
+                            (long long)R, n->schema[i].name.c_str());
+        }
+        for (size_t i = 0; i < side.cols.size(); ++i) {
+            const TCol &c = side.cols[i];
+            TCol &o = t->cols[i];
+            o = c;
+            if (!c.present) continue;
+            const bool left = i < nl;
+            // the other side is one row: this side's column IS the result's
+            if ((left ? R : L) == 1) continue;
+            o.subset_of = c.subset_of ? c.subset_of : c.c.values;   // (every value of the result is a value of the source)
+            const std::string name = node_key(pl, n, "cross", (int)i);
+            if (left) FG_TRY(cross_repeat(ctx, name.c_str(), c.c, L, R, &o.c));
+            else FG_TRY(cross_tile(ctx, name.c_str(), c.c, R, L, &o.c));
+        }
+        return FLOCKGPU_OK;
     }
 
     // HashJoinExec join_type Semi / Anti (relops.hpp A-S1..6) as a LAZY table: the left input's base table and the list of its rows that have

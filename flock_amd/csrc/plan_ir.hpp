@@ -10,6 +10,8 @@
 // COUNT / SUM / MIN / MAX / AVG over the default frame.  hash_join_exec takes join_type Inner, Semi and Anti (Semi / Anti: the left input's rows
 // that have / lack a partner on the right, the left input's schema -- relops.hpp A-S1..6).  Anything else (other window functions and frames,
 // Left / Right / Full joins, unknown expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
+// cross_join_exec (cross.hpp A-X1..6) is a Join node of JoinType::Cross without key pairs: left ++ right columns, L x R rows, pair (i, j) at row i * R + j.
+// (The fork's typetag name cannot be checked -- its DataFusion source is not under the reference --: it follows the naming of every tag seen so far.)
 // hash_aggregate_exec takes COUNT / SUM / MIN / MAX / AVG and COUNT(DISTINCT x) -- an aggr_expr entry tagged "distinct_count" (alias "count_distinct") with
 // its one argument under `exprs` or `expr` (distinct.hpp A-D1..A-D7).  That aggregate's Partial state is a List column, which this boundary does not
 // carry: Final / FinalPartitioned over the Partial of the same plan becomes ONE single-pass node over the Partial's input (Node::single_pass); a Partial
@@ -170,7 +172,7 @@ struct WinExpr {
     std::vector<SortCol> order;    // aggregate: input columns of the ORDER BY (they delimit the peer groups; the input arrives sorted)
 };
 constexpr int kMaxWindowKeys = 4;   // PARTITION BY / ORDER BY columns of an aggregate window (each)
-enum class JoinType { Inner, Semi, Anti };
+enum class JoinType { Inner, Semi, Anti, Cross };   // Cross: cross_join_exec -- no key pairs (`on` empty), every pair of rows
 // a join key pair that can compare: two Utf8 columns, or two integer columns of one signedness (Float64 keys are refused)
 inline bool join_keys_comparable(ColType x, ColType y) {
     return x != ColType::F64 && y != ColType::F64 && (x == ColType::UTF8) == (y == ColType::UTF8) && (x == ColType::U64) == (y == ColType::U64);
@@ -190,7 +192,7 @@ struct Node {
     // Aggregate with a distinct count: Final / FinalPartitioned and the Partial below it as ONE aggregation over the Partial's input -- `mode` is the
     // upper node's, arguments are input columns as a Partial's, the schema is the finished results' (AVG one Float64 column)
     bool single_pass = false;
-    std::vector<KeyPair> on;        // Join: the key pairs, 1 to kMaxJoinPairs (q9 has two: auction = id AND price = final)
+    std::vector<KeyPair> on;        // Join: the key pairs, 1 to kMaxJoinPairs (q9 has two: auction = id AND price = final); none for JoinType::Cross
     bool join_partitioned = false;  // Join: mode=Partitioned (both inputs arrive hash-partitioned on the keys)
     JoinType join_type = JoinType::Inner;   // Join: Semi / Anti return rows of the LEFT input only (schema = the left input's)
     std::vector<int> hash_cols;     // Repartition
@@ -949,6 +951,36 @@ struct Builder {
             }
             n->in.push_back(std::move(l));
             n->in.push_back(std::move(r));
+        } else if (t == "cross_join_exec") {
+            // CrossJoinExec (cross.hpp): `left`, `right`, optionally `schema`; `on`, `join_type`, `mode`, `random_state`, where present, are ignored
+            n->kind = NKind::Join;
+            n->join_type = JoinType::Cross;
+            auto l = node(j->get("left"), depth + 1);
+            if (!l) return nullptr;
+            auto r = node(j->get("right"), depth + 1);
+            if (!r) return nullptr;
+            n->schema = l->schema;
+            n->schema.insert(n->schema.end(), r->schema.begin(), r->schema.end());
+            // (A-X1) a serialised schema that is not left ++ right -- a column short, another type -- is another operator's
+            const JValue *sc = j->get("schema");
+            const JValue *sf = sc ? sc->get("fields") : nullptr;
+            if (sf && sf->kind == JValue::Arr) {
+                std::vector<Field> given;
+                if (!fields_of(sc, &given)) return nullptr;
+                if (given.size() != n->schema.size()) {
+                    fail("Cross join: the node's schema (" + std::to_string(given.size()) + " columns) is not the left input's followed by the right input's (" +
+                         std::to_string(l->schema.size()) + " + " + std::to_string(r->schema.size()) + " columns)");
+                    return nullptr;
+                }
+                for (size_t i = 0; i < given.size(); ++i)
+                    if (given[i].type != n->schema[i].type || given[i].is_ts != n->schema[i].is_ts) {
+                        fail("Cross join: the node's schema says " + std::string(type_name(given[i])) + " for column " + std::to_string(i) + " ('" + given[i].name +
+                             "'), the inputs give " + type_name(n->schema[i]) + ": a cross join returns left ++ right columns unchanged");
+                        return nullptr;
+                    }
+            }
+            n->in.push_back(std::move(l));
+            n->in.push_back(std::move(r));
         } else if (t == "sort_exec") {
             n->kind = NKind::Sort;
             auto in = node(j->get("input"), depth + 1);
@@ -1186,7 +1218,8 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
         case NKind::Join: {
             const size_t nl = n->in[0]->schema.size();
             // (Semi / Anti: the output IS the left side; the right child is read for its key columns alone -- a leaf under it uploads nothing else)
-            const bool semi = n->join_type != JoinType::Inner;
+            // (Cross: no keys -- each side gets what the ancestors read of it, COUNT(*) above asks neither side for a column)
+            const bool semi = n->join_type == JoinType::Semi || n->join_type == JoinType::Anti;
             std::vector<char> l(req.begin(), req.begin() + nl), r;
             if (semi) r.assign(n->in[1]->schema.size(), 0);
             else r.assign(req.begin() + nl, req.end());
@@ -1296,7 +1329,10 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
             // Inner: NULL keys never match.  Semi / Anti: `droppable` speaks of the left columns alone.  A NULL key never matches: the right rows it
             // sits in can go, and so can Semi's left rows -- but an ANTI join KEEPS its NULL-keyed left rows (relops.hpp A-S4): their key columns
             // arrive with validity bytes and the probe reads them
-            const bool inner = n->join_type == JoinType::Inner;
+            // Cross: the node itself makes nothing droppable (a NULL row of either side is a row of the result, L x R counts it); what an ancestor may
+            // drop passes through as through an inner join's non-key columns: a row (i, j) whose column c is NULL is dropped above exactly when every pair
+            // of the source row is, and anything below that counts rows (Aggregate, Limit, Window) resets the marks on its own
+            const bool inner = n->join_type == JoinType::Inner || n->join_type == JoinType::Cross;
             std::vector<char> l(droppable.begin(), droppable.begin() + nl), r(n->in[1]->schema.size(), 0);
             if (inner) r.assign(droppable.begin() + nl, droppable.end());
             for (auto &k : n->on) {

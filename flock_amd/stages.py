@@ -9,7 +9,8 @@ from the root;
   * `hash_join_exec`: the current plan (join with two empty `memory_exec` leaves) becomes a stage, its `left` and `right`
     inputs become the two plans of the stage below -- and the walk stops there (stage.rs:335-336);
   * `sort_exec`: like a final aggregate;
-  * everything else: descend.
+  * everything else: descend.  (`cross_join_exec` has no `input`: the walk ends there as it does at a leaf, and the cross join stays in one
+    stage with both of its inputs -- stage.rs knows no such node.)
 A stage plan whose root is `coalesce_batches_exec <- repartition_exec Hash` is a shuffling stage
 (`ExecutionContext::is_shuffling`, flock/src/runtime/context.rs:328-337): the function runs `execute_partitioned` and sends
 partition j to member j of the next function group (flock-function/src/aws/actor.rs:60-66,425-543).
@@ -64,6 +65,10 @@ def node_schema(n: dict) -> dict:
         return {"fields": copy.deepcopy(fields), "metadata": {}}
     if kind in ("projection_exec", "hash_aggregate_exec", "hash_join_exec") and "schema" in n:
         return copy.deepcopy(n["schema"])
+    if kind == "cross_join_exec":   # (no cut here: the walk passes through it; its schema is asked for when something above it is cut off)
+        if "schema" in n:
+            return copy.deepcopy(n["schema"])
+        return {"fields": node_schema(n["left"])["fields"] + node_schema(n["right"])["fields"], "metadata": {}}
     if "input" in n:
         return node_schema(n["input"])
     raise ValueError(f"no schema for plan node {kind!r}")

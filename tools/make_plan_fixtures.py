@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes tests/golden/plans/*.json: the physical plans of the five NEXMark target queries (and q7, q13) in the
-serde_json dialect of the reference's DataFusion fork.
+serde_json dialect of the reference's DataFusion fork, and bids_above_average.json (a cross join against a global aggregate).
 
 The fork's serialiser cannot be run here (no Rust toolchain), so the plans are AUTHORED from
   * the grammar of the checked-in fixtures flock/src/tests/data/plan/{simple_select,aggregate,join}.json
@@ -442,8 +442,36 @@ def arch_sort():
     return sort_by({"execution_plan": "coalesce_partitions_exec", "input": memory(BID, [0, 1, 2, 3], "bid")}, [(col("bidder", 1), False)])
 
 
+def cross_join(left, right, fields):
+    """cross_join_exec (cross.hpp): the tag follows the naming of the fork's other nodes; left ++ right columns, no key pairs."""
+    return {"execution_plan": "cross_join_exec", "left": left, "right": right, "schema": schema(fields)}
+
+
+def bids_above_average():
+    """`SELECT auction, bidder, price, avgp FROM bid CROSS JOIN (SELECT AVG(price) AS avgp FROM bid) a WHERE CAST(price AS Float64) > avgp`:
+    DataFusion of that generation has no scalar sub-queries and plans the statement as
+      ProjectionExec <- CoalesceBatches <- FilterExec: CAST(price@2 AS Float64) > avgp@3 <- CrossJoinExec
+        left   RepartitionExec RoundRobin <- MemoryExec bid [auction, bidder, price]
+        right  ProjectionExec [AVG(bid.price) AS avgp] <- HashAggregate Final <- CoalescePartitions <- HashAggregate Partial <- RoundRobin <- MemoryExec bid [price]"""
+    three = BID[:3]
+    price = [field("price", "Int32")]
+    avg = [{"aggregate_expr": "avg", "name": "AVG(bid.price)", "data_type": "Float64", "nullable": True, "expr": col("price", 0)}]
+    part = [field("AVG(bid.price)[count]", "UInt64", True), field("AVG(bid.price)[sum]", "Float64", True)]
+    fin = [field("AVG(bid.price)", "Float64", True)]
+    avgp = [field("avgp", "Float64", True)]
+    partial = agg(rr(memory(BID, [2], "bid")), "Partial", [], avg, price, part)
+    final = agg({"execution_plan": "coalesce_partitions_exec", "input": partial}, "Final", [], avg, price, fin)
+    right = proj(final, [(col("AVG(bid.price)", 0), "avgp")], avgp)
+    x = cross_join(rr(memory(BID, [0, 1, 2], "bid")), right, three + avgp)
+    keep = coalesce(filt(x, binary(cast(col("price", 2), "Float64"), "Gt", col("avgp", 3))))
+    return proj(keep, [(col(f["name"], i), f["name"]) for i, f in enumerate(three + avgp)], three + avgp)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, "bids_above_average.json"), "w") as f:
+        json.dump(bids_above_average(), f, indent=1, sort_keys=True)
+        f.write("\n")
     for name, fn in (("golden_aggregate", golden_aggregate), ("golden_join", golden_join), ("golden_aggregate_sorted", golden_aggregate_sorted),
                      ("golden_join_sorted", golden_join_sorted), ("q3_sorted", q3_sorted)):
         with open(os.path.join(OUT, name + ".json"), "w") as f:
