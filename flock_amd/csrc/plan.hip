@@ -738,6 +738,12 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
             return;
         case EKind::Case: os << "CASE ..."; return;
         case EKind::Func: {
+            if (fn_is_slice(e->fn)) {   // split_part(url, '/', 4)
+                std::vector<std::string> names;
+                for (auto &f : schema) names.push_back(f.name);
+                os << slice_text(e, names);
+                return;
+            }
             static const char *units[] = {"second", "minute", "hour", "day", "week", "month", "year", "dow", "doy"};
             os << e->s << "(";
             if (e->i >= 0 && e->i < 9) os << "'" << units[e->i] << "', ";
@@ -1123,6 +1129,7 @@ struct Exec {
     // now() (valprog.hpp A-F8): the UTC wall clock in milliseconds, read once -- here, as the execute begins
     int64_t now_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
     int fn_cols = 0;   // length columns written so far by this execute (octet_length / char_length: a buffer each, named by this count)
+    int slice_bufs = 0;   // ... and the (begin, end) pairs of text slice calls (textslice.hpp)
 
     // A relation the SQL scans twice (q5 and q7 read `bid` in both join inputs, q5_plan.fmt:6,13) has two MemoryExec leaves
     // but arrives as ONE source, which feed_data_sources hands to the first matching leaf (context.rs:273-300) -- the
@@ -1989,6 +1996,7 @@ struct Exec {
                     *may_null = *may_null || d.valid != nullptr;
                     return b.push(ValOpKind::Col, ValType::I32, 0, b.add_col(d)) ? FLOCKGPU_OK : val_full();
                 }
+                if (fn_is_slice(e->fn)) return val_unsupported("a Utf8-valued function inside a computed expression");
                 const bool math = fn_is_math(e->fn);
                 int ta = -1;
                 FG_TRY(val_compile(e->list[0].get(), in, b, math ? 3 : 1, &ta, may_null));
@@ -2058,6 +2066,43 @@ struct Exec {
                 if (!c.present || !c.c.offsets) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
                 return source(tt.add_column(c.c));   // (its NULLs: the kernels read the column's validity bytes)
             }
+            case EKind::Func: {   // a slice function (textslice.hpp): the chain of calls down to its column, innermost first, one launch each
+                if (!fn_is_slice(e->fn)) return val_unsupported("CASE branches of different types");
+                std::vector<const Expr *> chain;
+                const Expr *c = e;
+                while (c->kind == EKind::Func || c->kind == EKind::Cast) {
+                    if (c->kind == EKind::Func) {
+                        if (!fn_is_slice(c->fn) || c->list.empty()) return val_unsupported("a text slice of something that is not a Utf8 column");
+                        chain.push_back(c);
+                        c = c->list[0].get();
+                    } else {
+                        c = c->l.get();
+                    }
+                }
+                if (c->kind != EKind::Col || in.cols[(size_t)c->col].c.type != ColType::UTF8) return val_unsupported("a text slice of something that is not a Utf8 column");
+                const TCol &col = in.cols[(size_t)c->col];
+                if (col.c.all_null) return null();
+                if (!col.present || !col.c.offsets) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
+                // (the key names the column by its position in `in`: identical calls of one expression are one source)
+                const std::string key = slice_text(e, std::vector<std::string>());
+                int idx = tt.find_slice(key);
+                if (idx < 0) {
+                    const int32_t *sb = nullptr, *se = nullptr;
+                    for (size_t k = chain.size(); k-- > 0;) {
+                        const Expr *f = chain[k];
+                        SliceSpec spec;
+                        spec.fn = slice_fn_of(f->fn);
+                        spec.n = (int32_t)f->slice_n;
+                        spec.arg = f->slice_arg;
+                        int32_t *ob = nullptr, *oe = nullptr;
+                        FG_TRY(text_slice(ctx, node_key(pl, pl->ir.root.get(), "slice", slice_bufs++).c_str(), col.c, in.rows, spec, sb, se, &ob, &oe));
+                        sb = ob;
+                        se = oe;
+                    }
+                    idx = tt.add_slice(col.c, sb, se, key);
+                }
+                return source(idx);   // (its NULLs: the column's validity bytes, as for a bare column)
+            }
             case EKind::Case: {
                 if (e->r) FG_TRY(text_compile(e->r.get(), in, b, tt, may_null));
                 else FG_TRY(null());
@@ -2095,7 +2140,7 @@ struct Exec {
         const int32_t *sel = nullptr;
         const uint8_t *sel_valid = nullptr;
         const bool bare = vb.p.n_ops == 1;   // one push: a literal, a column, a NULL
-        if (bare && tt.s.k == 1 && tt.s.src[0].offsets) {   // CAST(column AS Utf8): the column itself
+        if (bare && tt.s.k == 1 && tt.s.src[0].offsets && !tt.s.src[0].begin) {   // CAST(column AS Utf8): the column itself (a bare slice is one text_select)
             const Expr *c = e;
             while (c->kind == EKind::Cast) c = c->l.get();
             *o = in.cols[(size_t)c->col];

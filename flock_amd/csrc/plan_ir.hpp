@@ -18,6 +18,8 @@
 // with a distinct count that anything else consumes is refused.
 // A computed expression ends in a number (the general evaluator, valprog.hpp) or in TEXT: a Utf8 literal, a Utf8 column or a CASE whose branches are such
 // (textsel.hpp A-T1..A-T5) -- as a projected column and, through computed_column, as a GROUP BY / ORDER BY key or a COUNT / COUNT(DISTINCT) argument.
+// The text slice functions split_part / left / right / ltrim / rtrim / btrim of a Utf8 column (textslice.hpp A-SL1..A-SL8) are text-valued expressions
+// too: `split_part(url, '/', 4)`, `btrim(split_part(description, ',', 1))`.  Every other text-producing function stays refused.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -28,6 +30,7 @@
 #include "relops.hpp"
 #include "strmatch.hpp"
 #include "textsel.hpp"
+#include "textslice.hpp"
 
 namespace flockgpu {
 namespace ir {
@@ -43,7 +46,8 @@ struct Field {
 // IsNullExpr{arg}, IsNotNullExpr{arg}, NotExpr{arg}, NegativeExpr{arg}, InListExpr{expr, list, negated}).
 enum class EKind { Col, LitI, LitF, LitS, LitB, LitNull, Bin, Cast, Not, IsNull, IsNotNull, Neg, InList, Case, Func };
 // Scalar functions (`scalar_function_expr`; shape and semantics: valprog.hpp A-F1..A-F8)
-enum class Fn { Abs, Signum, Floor, Ceil, Round, Trunc, Sqrt, DateTrunc, DatePart, OctetLength, CharLength, Now };
+// ... and the text slice functions (textslice.hpp A-SL1..A-SL8), SplitPart .. Btrim in SliceFn's order
+enum class Fn { Abs, Signum, Floor, Ceil, Round, Trunc, Sqrt, DateTrunc, DatePart, OctetLength, CharLength, Now, SplitPart, Left, Right, Ltrim, Rtrim, Btrim };
 struct Expr {
     EKind kind = EKind::Col;
     int col = -1;  // Col: index into the input schema
@@ -60,8 +64,31 @@ struct Expr {
     std::string lit_kind;                      // literals: the ScalarValue variant ("Int32", "Float64", ...; empty: a bare JSON value)
     Fn fn = Fn::Abs;                           // Func: the function (`s`: its canonical name; `i`: the cal::Unit of date_trunc / date_part, else -1; `list`: the value
                                                // arguments -- one, none for now(); the unit literal is folded into `i`)
+    int64_t slice_n = 0;                       // Func, a slice function: split_part's field, left's / right's count
+    std::string slice_arg;                     // Func, a slice function: split_part's delimiter, the trims' characters (`slice_has_arg`: written in the call)
+    bool slice_has_arg = false;
 };
 inline bool fn_is_math(Fn f) { return f <= Fn::Sqrt; }
+inline bool fn_is_slice(Fn f) { return f >= Fn::SplitPart; }
+inline SliceFn slice_fn_of(Fn f) { return (SliceFn)((int)f - (int)Fn::SplitPart); }
+// A slice call as text, the way explain prints it: split_part(url, '/', 4), btrim(split_part(description, ',', 1)), ltrim(name).  Identical calls
+// give identical text: the key under which one source table holds a slice once.  (`e` a slice Func; a cast in front of the value argument is not printed.)
+inline std::string slice_text(const Expr *e, const std::vector<std::string> &col_names) {
+    const Expr *v = e->list[0].get();
+    while (v->kind == EKind::Cast) v = v->l.get();
+    std::string t = e->s + "(";
+    if (v->kind == EKind::Func) t += slice_text(v, col_names);
+    else if (v->kind == EKind::Col && v->col >= 0 && (size_t)v->col < col_names.size()) t += col_names[(size_t)v->col];
+    else t += "#" + std::to_string(v->col);
+    if (e->slice_has_arg) t += ", '" + e->slice_arg + "'";
+    if (e->fn == Fn::SplitPart || e->fn == Fn::Left || e->fn == Fn::Right) t += ", " + std::to_string(e->slice_n);
+    return t + ")";
+}
+// how deep slice calls nest in `e` (a column: 0)
+inline int slice_depth(const Expr *e) {
+    while (e->kind == EKind::Cast) e = e->l.get();
+    return e->kind == EKind::Func && fn_is_slice(e->fn) ? 1 + slice_depth(e->list[0].get()) : 0;
+}
 // the result is a Timestamp(Millisecond): CAST(x AS Timestamp), date_trunc, now()
 inline bool expr_is_ts(const Expr *e) {
     return (e->kind == EKind::Cast && e->cast_ts) || (e->kind == EKind::Func && (e->fn == Fn::DateTrunc || e->fn == Fn::Now));
@@ -91,7 +118,7 @@ inline int expr_static_type(const Expr *e, const std::vector<Field> &schema) {
             if (e->s == "Multiply" && (e->l->kind == EKind::LitF || e->r->kind == EKind::LitF)) return 3;
             return -2;
         }
-        case EKind::Func: return fn_is_math(e->fn) ? 3 : (e->fn == Fn::DateTrunc || e->fn == Fn::Now) ? 1 : 0;
+        case EKind::Func: return fn_is_slice(e->fn) ? 4 : fn_is_math(e->fn) ? 3 : (e->fn == Fn::DateTrunc || e->fn == Fn::Now) ? 1 : 0;
         case EKind::Case: {
             int t = -1;
             for (size_t i = 1; i < e->list.size() && t == -1; i += 2) t = expr_static_type(e->list[i].get(), schema);
@@ -460,15 +487,17 @@ struct Builder {
         if (name == "character_length" || name == "length") name = "char_length";
         static const std::pair<const char *, Fn> known[] = {{"abs", Fn::Abs}, {"signum", Fn::Signum}, {"floor", Fn::Floor}, {"ceil", Fn::Ceil}, {"round", Fn::Round},
                                                             {"trunc", Fn::Trunc}, {"sqrt", Fn::Sqrt}, {"date_trunc", Fn::DateTrunc}, {"date_part", Fn::DatePart},
-                                                            {"octet_length", Fn::OctetLength}, {"char_length", Fn::CharLength}, {"now", Fn::Now}};
+                                                            {"octet_length", Fn::OctetLength}, {"char_length", Fn::CharLength}, {"now", Fn::Now},
+                                                            {"split_part", Fn::SplitPart}, {"left", Fn::Left}, {"right", Fn::Right}, {"ltrim", Fn::Ltrim},
+                                                            {"rtrim", Fn::Rtrim}, {"btrim", Fn::Btrim}};
         const std::pair<const char *, Fn> *k = nullptr;
         for (auto &c : known)
             if (name == c.first) k = &c;
         if (!k) {
             for (const char *f : {"exp", "ln", "log", "log2", "log10", "power", "sin", "cos", "tan", "asin", "acos", "atan"})
                 if (name == f) return refuse("function '" + name + "' has no bit-exact counterpart on the device");
-            for (const char *f : {"substr", "lower", "upper", "trim", "ltrim", "rtrim", "btrim", "concat", "concat_ws", "lpad", "rpad", "left", "right", "repeat", "replace",
-                                  "reverse", "split_part", "initcap", "translate", "to_hex", "chr", "md5", "sha256"})
+            for (const char *f : {"substr", "lower", "upper", "trim", "concat", "concat_ws", "lpad", "rpad", "repeat", "replace",
+                                  "reverse", "initcap", "translate", "to_hex", "chr", "md5", "sha256"})
                 if (name == f) return refuse("function '" + name + "' produces text: not yet");
             if (name == "starts_with") return refuse("function 'starts_with' yields a Boolean (no Boolean columns at this boundary)");
             return refuse("function '" + name + "' is not supported");
@@ -527,6 +556,58 @@ struct Builder {
             if (!av.empty()) return refuse("function 'now' with " + std::to_string(av.size()) + " arguments: it takes none");
             rt = ColType::I64;
             rts = true;
+        } else if (fn_is_slice(x->fn)) {   // textslice.hpp A-SL1..A-SL5
+            const bool split = x->fn == Fn::SplitPart, count = x->fn == Fn::Left || x->fn == Fn::Right;
+            const std::string who = "function '" + name + "'";
+            if (split ? av.size() != 3 : count ? av.size() != 2 : (av.size() != 1 && av.size() != 2))
+                return refuse(who + " with " + std::to_string(av.size()) + " arguments: it takes " +
+                              (split ? "(string, delimiter, n)" : count ? "(string, n)" : "(string) or (string, characters)"));
+            // the value: a Utf8 column or a slice function of one
+            const Expr *v = no_utf8_cast(av[0].get());
+            const bool inner = v->kind == EKind::Func && fn_is_slice(v->fn);
+            if (!inner && !(v->kind == EKind::Col && schema[(size_t)v->col].type == ColType::UTF8)) {
+                const char *what = v->kind == EKind::LitS || v->kind == EKind::LitNull ? "a literal" : v->kind == EKind::Case ? "a CASE" : v->kind == EKind::Col ? "a column that is not Utf8" : "a computed value";
+                return refuse(who + ": the value argument is " + what + ", it takes a Utf8 column or a slice function (split_part, left, right, ltrim, rtrim, btrim) of one");
+            }
+            if (1 + slice_depth(v) > kSliceMaxDepth) return refuse(who + ": slice functions nested more than " + std::to_string(kSliceMaxDepth) + " deep");
+            // the others: literals (a cast to the literal's own type may sit in front)
+            auto literal = [&](const Expr *a, bool text, const char *arg, const Expr **out) -> bool {
+                while (a->kind == EKind::Cast && (text ? a->cast_to == ColType::UTF8 : (a->cast_to == ColType::I32 || a->cast_to == ColType::I64) && !a->cast_ts)) a = a->l.get();
+                if (a->kind == EKind::LitNull) { refuse(who + ": a NULL literal as " + arg); return false; }
+                if (a->kind != (text ? EKind::LitS : EKind::LitI)) {
+                    const bool lit = a->kind == EKind::LitI || a->kind == EKind::LitF || a->kind == EKind::LitS || a->kind == EKind::LitB;
+                    refuse(who + ": " + arg + (lit ? std::string(" is not ") + (text ? "a Utf8 literal" : "an integer literal")
+                                                   : std::string(" is ") + (a->kind == EKind::Col ? "a column" : "a computed value") + ", it takes a literal"));
+                    return false;
+                }
+                *out = a;
+                return true;
+            };
+            const Expr *lit = nullptr;
+            if (split || !count) {
+                if (av.size() >= 2) {
+                    if (!literal(av[1].get(), true, split ? "the delimiter" : "the characters", &lit)) return nullptr;
+                    x->slice_arg = lit->s;
+                    x->slice_has_arg = true;
+                } else {
+                    x->slice_arg = " ";   // the one-argument trims strip U+0020
+                }
+                if (split && x->slice_arg.empty()) return refuse(who + ": an empty delimiter");
+                if (split && x->slice_arg.size() > (size_t)kSliceMaxDelimBytes) return refuse(who + ": a delimiter of more than " + std::to_string(kSliceMaxDelimBytes) + " bytes");
+                if (!split) {
+                    size_t cps = 0;
+                    for (unsigned char ch : x->slice_arg) cps += (ch & 0xc0u) != 0x80u;
+                    if (cps > (size_t)kSliceMaxTrimChars) return refuse(who + ": more than " + std::to_string(kSliceMaxTrimChars) + " characters to strip");
+                }
+            }
+            if (split || count) {
+                if (!literal(av[split ? 2 : 1].get(), false, "n", &lit)) return nullptr;
+                if (lit->big_unsigned || lit->i < INT32_MIN || lit->i > INT32_MAX) return refuse(who + ": n beyond Int32");
+                if (split && lit->i <= 0) return refuse(who + ": n = " + std::to_string(lit->i) + ", the field number is positive");
+                x->slice_n = lit->i;
+            }
+            av.resize(1);
+            rt = ColType::UTF8;
         } else {
             if (av.size() != 1) return refuse("function '" + name + "' with " + std::to_string(av.size()) + " arguments: it takes one");
             const Expr *c = no_utf8_cast(av[0].get());
@@ -577,8 +658,15 @@ struct Builder {
 
     // A text-valued expression (textsel.hpp A-T1) in a value position: its sources -- distinct literals and columns -- are collected for the A-T5
     // limits; a branch of another type is refused.
-    bool text_sources(const Expr *e, const std::vector<Field> &schema, std::set<std::string> *lits, std::set<int> *cols) {
+    bool text_sources(const Expr *e, const std::vector<Field> &schema, std::set<std::string> *lits, std::set<int> *cols, std::set<std::string> *slices) {
         switch (e->kind) {
+            case EKind::Func: {   // a slice function (textslice.hpp): one source, identical calls once
+                if (!fn_is_slice(e->fn)) return fail("CASE branches of different types");
+                std::vector<std::string> names;
+                for (auto &f : schema) names.push_back(f.name);
+                slices->insert(slice_text(e, names));
+                return true;
+            }
             case EKind::LitS: lits->insert(e->s); return true;
             case EKind::LitNull: return true;
             case EKind::Col:
@@ -589,12 +677,12 @@ struct Builder {
                 if (e->cast_to != ColType::UTF8) return fail("CASE branches of different types");
                 const int from = expr_static_type(e->l.get(), schema);
                 if (from != 4 && from != -1) return fail("CAST between other than numeric types inside a computed expression");
-                return text_sources(e->l.get(), schema, lits, cols);
+                return text_sources(e->l.get(), schema, lits, cols, slices);
             }
             case EKind::Case:
                 for (size_t i = 1; i < e->list.size(); i += 2)
-                    if (!text_sources(e->list[i].get(), schema, lits, cols)) return false;
-                return !e->r || text_sources(e->r.get(), schema, lits, cols);
+                    if (!text_sources(e->list[i].get(), schema, lits, cols, slices)) return false;
+                return !e->r || text_sources(e->r.get(), schema, lits, cols, slices);
             default: return fail("CASE branches of different types");
         }
     }
@@ -602,8 +690,9 @@ struct Builder {
     bool check_text(const Expr *e, const std::vector<Field> &schema) {
         std::set<std::string> lits;
         std::set<int> cols;
-        if (!text_sources(e, schema, &lits, &cols)) return false;
-        if (lits.size() + cols.size() > (size_t)kTextMaxSources)
+        std::set<std::string> slices;
+        if (!text_sources(e, schema, &lits, &cols, &slices)) return false;
+        if (lits.size() + cols.size() + slices.size() > (size_t)kTextMaxSources)
             return fail("more than " + std::to_string(kTextMaxSources) + " distinct sources (literals plus columns) in one Utf8-valued expression");
         size_t bytes = 0;
         for (auto &l : lits) bytes += l.size();

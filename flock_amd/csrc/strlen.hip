@@ -8,6 +8,8 @@
 //                        barrier a lane takes rows: it counts the bits of the mask words its row covers in this round (64 positions per word) and adds
 //                        them to the row's count in LDS.  A row that straddles rounds collects its count over them; a row longer than a round is
 //                        just more words.  Global loads: the offsets and the chunks, none under a per-row branch.
+//                        A second instance (kRange) counts inside a per-row range [rb[i], re[i]) of the value -- an inner text slice
+//                        (textslice.hpp) -- instead of the whole value; the plain instance's code is what it was.
 #include <algorithm>
 
 #include "gather.hpp"
@@ -33,17 +35,24 @@ __device__ __forceinline__ uint32_t lead_mask4(uint32_t w) {
     return ((lead >> 7) & 1u) | ((lead >> 14) & 2u) | ((lead >> 21) & 4u) | ((lead >> 28) & 8u);
 }
 
+template <bool kRange>
 __global__ __launch_bounds__(kBlock) void utf8_chars_kernel(const int32_t *__restrict__ off, const uint8_t *__restrict__ bytes, int64_t n_rows,
-                                                            int32_t *__restrict__ out) {
+                                                            const int32_t *__restrict__ rb, const int32_t *__restrict__ re, int32_t *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint16_t s_mask[kLenChunks + 4];   // (+ 4: the last word read whole)
     __shared__ int32_t s_off[kLenRows + 1];
     __shared__ int32_t s_cnt[kLenRows];
+    __shared__ int32_t s_rb[kRange ? kLenRows : 1], s_re[kRange ? kLenRows : 1];   // kRange: the rows' ranges
     const int tid = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kLenRows;
     const int32_t nr = (int32_t)(row0 >= n_rows ? 0 : (n_rows - row0 < kLenRows ? n_rows - row0 : kLenRows));
     if (nr <= 0) return;   // (block-uniform)
     for (int i = tid; i <= nr; i += kBlock) s_off[i] = off[row0 + i];
     for (int i = tid; i < nr; i += kBlock) s_cnt[i] = 0;
+    if (kRange)
+        for (int i = tid; i < nr; i += kBlock) {
+            s_rb[i] = rb[row0 + i];
+            s_re[i] = re[row0 + i];
+        }
     if (tid < 4) s_mask[kLenChunks + tid] = 0;
     __syncthreads();
     const int64_t B0 = s_off[0], B1 = s_off[nr];
@@ -72,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void utf8_chars_kernel(const int32_t *__res
         for (int i = 0; i < kLenChunks / kBlock; ++i) s_mask[i * kBlock + tid] = (uint16_t)m[i];
         __syncthreads();
         for (int r = tid; r < nr; r += kBlock) {
-            int64_t a = (int64_t)s_off[r] - base, b = (int64_t)s_off[r + 1] - base;   // the row's positions in this round: [a, b)
+            int64_t a = (int64_t)(kRange ? s_rb[r] : s_off[r]) - base, b = (int64_t)(kRange ? s_re[r] : s_off[r + 1]) - base;   // the row's positions in this round: [a, b)
             a = a < 0 ? 0 : a;
             b = b > kLenRoundBytes ? kLenRoundBytes : b;
             if (a >= b) continue;
@@ -95,13 +104,15 @@ __global__ __launch_bounds__(kBlock) void utf8_chars_kernel(const int32_t *__res
 
 namespace flockgpu {
 
-int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out) {
+int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out, const int32_t *range_begin,
+                 const int32_t *range_end) {
     int32_t *len = nullptr;
     FG_TRY(arena_get_t(ctx, name, (size_t)std::max<int64_t>(rows, 0) + 4, &len));
     *out = len;
     if (rows <= 0) return FLOCKGPU_OK;
     if (rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^31 rows", name);
     if (col.type != ColType::UTF8 || !col.offsets) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: not a Utf8 column", name);
+    if ((range_begin == nullptr) != (range_end == nullptr) || (range_begin && !code_points)) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: a range takes both arrays and counts code points", name);
     if (!code_points) {
         const unsigned grid = (unsigned)std::min<int64_t>(div_up(rows, kBlock), (int64_t)ctx->num_cus * 16);
         LaunchScope ls(ctx, "utf8_octets_kernel");
@@ -109,7 +120,10 @@ int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int6
         return check_launch(ctx, "utf8_octets_kernel");
     }
     LaunchScope ls(ctx, "utf8_chars_kernel");
-    hipLaunchKernelGGL(utf8_chars_kernel, dim3((unsigned)div_up(rows, kLenRows)), dim3(kBlock), 0, ctx->stream, col.offsets, static_cast<const uint8_t *>(col.values), rows, len);
+    const dim3 grid((unsigned)div_up(rows, kLenRows));
+    const uint8_t *bytes = static_cast<const uint8_t *>(col.values);
+    if (range_begin) hipLaunchKernelGGL(utf8_chars_kernel<true>, grid, dim3(kBlock), 0, ctx->stream, col.offsets, bytes, rows, range_begin, range_end, len);
+    else hipLaunchKernelGGL(utf8_chars_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, col.offsets, bytes, rows, nullptr, nullptr, len);
     return check_launch(ctx, "utf8_chars_kernel");
 }
 

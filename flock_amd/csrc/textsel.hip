@@ -8,7 +8,8 @@
 //                         non-temporal stores; only the first and last 16-byte chunk of a tile, which it shares with its neighbours, go out
 //                         byte by byte.  The source table lives in LDS (literals: the pool, read as aligned dwords -- every literal starts on a
 //                         4-byte boundary).  Two instances of each kernel: kCols = false (literals alone: NEXMark q14's labels) has no global
-//                         load besides the selector.
+//                         load besides the selector; a third, kSlices, reads a value's range through a slice source's per-row (begin, end) arrays
+//                         (textslice.hpp) where the source has them -- the two instances without it are what they were.
 //   textsel_emit_long_kernel  the bytes of every tile beyond the stage (long column values): the take's chunk-wise copy for long values, shared
 //                         (utf8_chunks.hpp), over the tile's (address, length) list in LDS.
 //   textsel_fill_kernel   a bare literal: offsets i * len and the literal over and over, 16 bytes per lane and step.
@@ -39,14 +40,28 @@ struct SharedTable {
     uint32_t pool[kPoolWords];
 };
 
-template <bool kCols>
-__device__ __forceinline__ void load_table(const TextSources &S, SharedTable &t) {
+// ... with the slice sources' per-row arrays (kSlices)
+struct SharedSliceTable : SharedTable {
+    const int32_t *begin[kTextMaxSources];
+    const int32_t *end[kTextMaxSources];
+};
+template <bool kSlices>
+struct TableOf { using type = SharedTable; };
+template <>
+struct TableOf<true> { using type = SharedSliceTable; };
+
+template <bool kCols, bool kSlices>
+__device__ __forceinline__ void load_table(const TextSources &S, typename TableOf<kSlices>::type &t) {
     if (threadIdx.x < (unsigned)kTextMaxSources) {
         const TextSource &s = S.src[threadIdx.x];
         if (kCols) {
             t.offsets[threadIdx.x] = s.offsets;
             t.bytes[threadIdx.x] = s.bytes;
             t.valid[threadIdx.x] = s.valid;
+        }
+        if constexpr (kSlices) {
+            t.begin[threadIdx.x] = s.begin;
+            t.end[threadIdx.x] = s.end;
         }
         t.lit_off[threadIdx.x] = s.lit_off;
         t.lit_len[threadIdx.x] = s.lit_len;
@@ -64,8 +79,8 @@ __device__ __forceinline__ int2 off_pair(const int32_t *__restrict__ off, int64_
 
 // A lane's four rows: len[j] bytes each (0: a NULL, an empty value, a row past the end), from pool byte `at[j]` (literal) or from `ptr[j]`
 // (column; null for a literal).  `vbytes`: the four validity bytes, 1 = the row has a value.
-template <bool kCols>
-__device__ __forceinline__ void pick4(const SharedTable &t, int32_t k, const int32_t *__restrict__ sel, const uint8_t *__restrict__ sel_valid, int64_t i0, int64_t n,
+template <bool kCols, bool kSlices>
+__device__ __forceinline__ void pick4(const typename TableOf<kSlices>::type &t, int32_t k, const int32_t *__restrict__ sel, const uint8_t *__restrict__ sel_valid, int64_t i0, int64_t n,
                                       uint32_t (&len)[4], uint32_t (&at)[4], const uint8_t *(&ptr)[4], uint32_t *vbytes) {
     int32_t s[4] = {0, 0, 0, 0};
     uint32_t v = 0x01010101u;
@@ -102,7 +117,15 @@ __device__ __forceinline__ void pick4(const SharedTable &t, int32_t k, const int
             const uint8_t *sv = t.valid[si];
             if (ok && sv && !sv[i0 + j]) ok = false;
             if (ok) {
-                const int2 o = off_pair(t.offsets[si], i0 + j);
+                int2 o;
+                bool sliced = false;
+                if constexpr (kSlices) {
+                    if (t.begin[si]) {
+                        o = make_int2(t.begin[si][i0 + j], t.end[si][i0 + j]);
+                        sliced = true;
+                    }
+                }
+                if (!sliced) o = off_pair(t.offsets[si], i0 + j);
                 len[j] = (uint32_t)(o.y - o.x);
                 ptr[j] = t.bytes[si] + (uint32_t)o.x;
             }
@@ -115,15 +138,15 @@ __device__ __forceinline__ void pick4(const SharedTable &t, int32_t k, const int
     *vbytes = out_v;
 }
 
-template <bool kCols>
+template <bool kCols, bool kSlices>
 __global__ __launch_bounds__(kBlock) void textsel_len_kernel(TextSources S, const int32_t *__restrict__ sel, const uint8_t *__restrict__ sel_valid, int64_t n,
                                                              uint32_t *__restrict__ counts, uint8_t *__restrict__ out_valid) {
-    __shared__ SharedTable t;
-    load_table<kCols>(S, t);
+    __shared__ typename TableOf<kSlices>::type t;
+    load_table<kCols, kSlices>(S, t);
     const int64_t i0 = (int64_t)blockIdx.x * kTextTile + (int64_t)threadIdx.x * kRowsPerLane;
     uint32_t len[4], at[4], vb;
     const uint8_t *ptr[4];
-    pick4<kCols>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
+    pick4<kCols, kSlices>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
     if (out_valid) {
         if (i0 + 4 <= n) {
             *reinterpret_cast<uint32_t *>(out_valid + i0) = vb;
@@ -174,18 +197,18 @@ __device__ __forceinline__ void copy_bytes(uint8_t *stage, uint32_t at, const Wo
     if (todo) few(todo);
 }
 
-template <bool kCols>
+template <bool kCols, bool kSlices>
 __global__ __launch_bounds__(kBlock) void textsel_emit_kernel(TextSources S, const int32_t *__restrict__ sel, const uint8_t *__restrict__ sel_valid, int64_t n,
                                                               const uint32_t *__restrict__ counts, const uint64_t *__restrict__ tile_base,
                                                               int32_t *__restrict__ out_off, uint8_t *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t s_stage[kTextStageBytes];
-    __shared__ SharedTable t;
-    load_table<kCols>(S, t);
+    __shared__ typename TableOf<kSlices>::type t;
+    load_table<kCols, kSlices>(S, t);
     const int wave = threadIdx.x >> 6;
     const int64_t i0 = (int64_t)blockIdx.x * kTextTile + (int64_t)threadIdx.x * kRowsPerLane;
     uint32_t len[4], at[4], vb;
     const uint8_t *ptr[4];
-    pick4<kCols>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
+    pick4<kCols, kSlices>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
     const uint32_t mine = len[0] + len[1] + len[2] + len[3];
     const uint4 wc = *reinterpret_cast<const uint4 *>(counts + (size_t)blockIdx.x * kWavesPerBlock);
     const uint32_t tile_bytes = wc.x + wc.y + wc.z + wc.w;
@@ -230,24 +253,25 @@ __global__ __launch_bounds__(kBlock) void textsel_emit_kernel(TextSources S, con
 // The bytes of the tiles that do not fit the stage (values of more than 16 bytes on average -- an auction's description -- up to single values of
 // any length): the take's chunk-wise emit for long values (utf8_chunks.hpp), over this tile's (address, length) list.  A literal's address lies in
 // `pool`, the table's literal pool in global memory.  Offsets are textsel_emit_kernel's.
+template <bool kSlices>
 __global__ __launch_bounds__(kBlock) void textsel_emit_long_kernel(TextSources S, const uint8_t *__restrict__ pool, const int32_t *__restrict__ sel,
                                                                    const uint8_t *__restrict__ sel_valid, int64_t n, const uint32_t *__restrict__ counts,
                                                                    const uint64_t *__restrict__ tile_base, uint8_t *__restrict__ out) {
     __shared__ uint32_t s_end[kTextTile];
     __shared__ uint64_t s_addr[kTextTile];
     __shared__ uint16_t s_first[kLongMapChunks];
-    __shared__ SharedTable t;
+    __shared__ typename TableOf<kSlices>::type t;
     const uint4 wc = *reinterpret_cast<const uint4 *>(counts + (size_t)blockIdx.x * kWavesPerBlock);
     const uint32_t tile_bytes = wc.x + wc.y + wc.z + wc.w;
     const uint64_t base = tile_base[blockIdx.x];
     const uint32_t phase = (uint32_t)(base & 15), end = phase + tile_bytes;
     if (tile_bytes == 0 || end <= (uint32_t)kTextStageBytes) return;   // (block-uniform: the staged kernel's tile)
-    load_table<true>(S, t);
+    load_table<true, kSlices>(S, t);
     const int wave = threadIdx.x >> 6;
     const int64_t i0 = (int64_t)blockIdx.x * kTextTile + (int64_t)threadIdx.x * kRowsPerLane;
     uint32_t len[4], at[4], vb;
     const uint8_t *ptr[4];
-    pick4<true>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
+    pick4<true, kSlices>(t, S.k, sel, sel_valid, i0, n, len, at, ptr, &vb);
     const uint32_t mine = len[0] + len[1] + len[2] + len[3];
     uint32_t start[4], index[4];
     start[0] = phase + (wave > 0 ? wc.x : 0u) + (wave > 1 ? wc.y : 0u) + (wave > 2 ? wc.z : 0u) + wave_incl_scan_u32(mine) - mine;
@@ -337,11 +361,12 @@ int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &S, const
     FG_TRY(arena_get_t(ctx, (base + ".base").c_str(), (size_t)tiles + 1, &tile_base));
     FG_TRY(pinned_get_t(ctx, (base + ".total").c_str(), 1, &h_total));
     *h_total = 0;
-    const bool cols = S.n_cols > 0;
+    const bool cols = S.n_cols > 0, slices = S.n_slices > 0;   // (a table without a slice source takes the instances it always took)
     {
         LaunchScope ls(ctx, "textsel_len_kernel");
-        if (cols) hipLaunchKernelGGL(textsel_len_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, o_v);
-        else hipLaunchKernelGGL(textsel_len_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, o_v);
+        if (slices) hipLaunchKernelGGL((textsel_len_kernel<true, true>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, o_v);
+        else if (cols) hipLaunchKernelGGL((textsel_len_kernel<true, false>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, o_v);
+        else hipLaunchKernelGGL((textsel_len_kernel<false, false>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, o_v);
     }
     FG_TRY(check_launch(ctx, "textsel_len_kernel"));
     FG_TRY(launch_tile_scan(ctx, counts, (int32_t)tiles, tile_base, nullptr, 0, nullptr));
@@ -352,8 +377,9 @@ int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &S, const
     FG_TRY(arena_get_t(ctx, (base + ".bytes").c_str(), (size_t)total + 16, &o_b));
     {
         LaunchScope ls(ctx, "textsel_emit_kernel");
-        if (cols) hipLaunchKernelGGL(textsel_emit_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, tile_base, o_off, o_b);
-        else hipLaunchKernelGGL(textsel_emit_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, tile_base, o_off, o_b);
+        if (slices) hipLaunchKernelGGL((textsel_emit_kernel<true, true>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, tile_base, o_off, o_b);
+        else if (cols) hipLaunchKernelGGL((textsel_emit_kernel<true, false>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, tile_base, o_off, o_b);
+        else hipLaunchKernelGGL((textsel_emit_kernel<false, false>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, sel, sel_valid, n, counts, tile_base, o_off, o_b);
     }
     FG_TRY(check_launch(ctx, "textsel_emit_kernel"));
     // tiles beyond the stage: possible with a column source, or with literals of more than a stage per tile
@@ -367,7 +393,8 @@ int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &S, const
         FG_HIP(ctx, hipMemcpyAsync(d_pool, h_pool, sizeof(S.pool), hipMemcpyHostToDevice, ctx->stream));
         {
             LaunchScope ls(ctx, "textsel_emit_long_kernel");
-            hipLaunchKernelGGL(textsel_emit_long_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, d_pool, sel, sel_valid, n, counts, tile_base, o_b);
+            if (slices) hipLaunchKernelGGL(textsel_emit_long_kernel<true>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, d_pool, sel, sel_valid, n, counts, tile_base, o_b);
+            else hipLaunchKernelGGL(textsel_emit_long_kernel<false>, dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream, S, d_pool, sel, sel_valid, n, counts, tile_base, o_b);
         }
         FG_TRY(check_launch(ctx, "textsel_emit_long_kernel"));
     }

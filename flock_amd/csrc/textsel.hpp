@@ -2,8 +2,9 @@
 // (valprog.hpp) stays what it was: the expression is lowered on the host (plan.hip text_compile) into
 //   a SELECTOR  the same CASE with every text branch replaced by the index of its SOURCE (0 .. K - 1) and NULL kept NULL: an Int32 program of
 //               the existing interpreter, nested CASE as nested Select.  A bare literal or column has no selector;
-//   a SOURCE TABLE (TextSources, passed by value): K entries, each a literal (offset and length in a pool of at most kTextMaxLiteralBytes) or a
-//               Utf8 column of the input (offsets, bytes, validity bytes);
+//   a SOURCE TABLE (TextSources, passed by value): K entries, each a literal (offset and length in a pool of at most kTextMaxLiteralBytes), a
+//               Utf8 column of the input (offsets, bytes, validity bytes) or a SLICE of such a column (textslice.hpp: per row the begin and end of the
+//               value inside the column's bytes, in place of its two offsets);
 // and two kernels turn (selector, table) into an ordinary Utf8 column -- int32 offsets, bytes, validity bytes:
 //   length pass  per row the selected source's length (a literal's from the table in LDS, a column's from its two offsets) -> one byte count per
 //                wave for the tile scan (scan.hpp), and the result's validity bytes where a NULL can occur;
@@ -31,8 +32,11 @@
 //   A-T5 refused by name at create / explain: more than kTextMaxSources distinct sources (literals plus columns) in one expression, more than
 //        kTextMaxLiteralBytes bytes of (distinct) literals in one expression.  Refused at execute: a result of 2^31 bytes or more, checked on
 //        the published total before any byte is written.
-//   Still refused, as before: a Utf8 column or literal inside a condition or under an operator, LIKE inside a computed expression, text-producing
-//   scalar functions, Boolean projections, hash partitioning on a computed expression, MIN / MAX of text.
+//   A-T6 the slice functions split_part / left / right / ltrim / rtrim / btrim of a Utf8 column (textslice.hpp A-SL1..A-SL8) are text-valued
+//        expressions too: one slice expression is one source, identical ones count once.
+//   Still refused, as before: a Utf8 column or literal inside a condition or under an operator, LIKE inside a computed expression, the other
+//   text-producing scalar functions (substr, lower, upper, trim, concat, ...), Boolean projections, hash partitioning on a computed expression,
+//   MIN / MAX of text.
 #pragma once
 #include <cstring>
 #include <string>
@@ -52,12 +56,14 @@ struct TextSource {
     const uint8_t *bytes;
     const uint8_t *valid;     // column source with NULLs: one byte per row
     uint32_t lit_off, lit_len;   // literal: where it lies in the pool (a multiple of four), its length
+    const int32_t *begin, *end;  // a slice of the column: row i's value is bytes [begin[i], end[i]); null: [offsets[i], offsets[i + 1])
 };
 struct TextSources {
     TextSource src[kTextMaxSources];
     uint32_t pool[(kTextMaxLiteralBytes + 4 * kTextMaxSources) / 4];   // the literals, each from a 4-byte boundary on
     int32_t k = 0;
     int32_t n_cols = 0;   // column sources among the k
+    int32_t n_slices = 0; // slices among the column sources
 };
 
 // Host-side assembly: every add returns the source's index (a literal or column that is already there: its index), -1 when the table is full.
@@ -65,24 +71,42 @@ struct TextTable {
     TextSources s{};
     uint32_t pool_used = 0;
     std::vector<std::string> lits;   // by source index ("" for a column)
+    std::vector<std::string> slice_keys;   // by source index: the slice expression's text ("" for anything else)
     int add_literal(const std::string &v) {
         for (int i = 0; i < s.k; ++i)
             if (!s.src[i].offsets && lits[(size_t)i] == v) return i;
         if (s.k >= kTextMaxSources || pool_used + v.size() > sizeof(s.pool)) return -1;
         TextSource &t = s.src[s.k];
-        t = TextSource{nullptr, nullptr, nullptr, pool_used, (uint32_t)v.size()};
+        t = TextSource{nullptr, nullptr, nullptr, pool_used, (uint32_t)v.size(), nullptr, nullptr};
         std::memcpy(reinterpret_cast<uint8_t *>(s.pool) + pool_used, v.data(), v.size());
         pool_used = (pool_used + (uint32_t)v.size() + 3u) & ~3u;
         lits.push_back(v);
+        slice_keys.emplace_back();
         return s.k++;
     }
     int add_column(const DevColumn &c) {
         for (int i = 0; i < s.k; ++i)
-            if (s.src[i].offsets == c.offsets && s.src[i].bytes == c.values && s.src[i].valid == c.valid) return i;
+            if (s.src[i].offsets == c.offsets && s.src[i].bytes == c.values && s.src[i].valid == c.valid && !s.src[i].begin) return i;
         if (s.k >= kTextMaxSources) return -1;
-        s.src[s.k] = TextSource{c.offsets, static_cast<const uint8_t *>(c.values), c.valid, 0, 0};
+        s.src[s.k] = TextSource{c.offsets, static_cast<const uint8_t *>(c.values), c.valid, 0, 0, nullptr, nullptr};
         lits.emplace_back();
+        slice_keys.emplace_back();
         ++s.n_cols;
+        return s.k++;
+    }
+    // the slice expression `key` (its text: identical expressions are one source) already in the table: its index, else -1
+    int find_slice(const std::string &key) const {
+        for (int i = 0; i < s.k; ++i)
+            if (s.src[i].begin && slice_keys[(size_t)i] == key) return i;
+        return -1;
+    }
+    int add_slice(const DevColumn &c, const int32_t *begin, const int32_t *end, const std::string &key) {
+        if (s.k >= kTextMaxSources) return -1;
+        s.src[s.k] = TextSource{c.offsets, static_cast<const uint8_t *>(c.values), c.valid, 0, 0, begin, end};
+        lits.emplace_back();
+        slice_keys.push_back(key);
+        ++s.n_cols;
+        ++s.n_slices;
         return s.k++;
     }
 };

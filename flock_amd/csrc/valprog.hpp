@@ -208,6 +208,8 @@ int valprog_to_rows(flockgpu_ctx *ctx, const char *name, const ValProgram &prog,
 int valprog_to_flags(flockgpu_ctx *ctx, const char *name, const ValProgram &prog, int64_t rows, const uint32_t **flag_words, const uint32_t **wave_counts, int32_t *n_tiles);
 // octet_length / char_length of a Utf8 column (A-F7; strlen.hip): one Int32 per row in an arena buffer called `name`, NULL rows included (their bytes are
 // whatever the column holds: the consumer reads the source's validity).  No host wait.
-int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out);
+// (range_begin / range_end, both or neither, code points only: the count inside [range_begin[i], range_end[i]) of the value -- an inner text slice)
+int utf8_lengths(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, bool code_points, int32_t **out, const int32_t *range_begin = nullptr,
+                 const int32_t *range_end = nullptr);
 
 }  // namespace flockgpu

@@ -94,7 +94,10 @@ typedef struct flockgpu_plan flockgpu_plan;
  * Float64 / Timestamp(Millisecond) values (Utf8: =, <>, IN, IS NULL against literals).  A computed value may also be TEXT: a Utf8 literal, a Utf8
  * column (under a cast to Utf8) or a case_expr whose THEN / ELSE branches are such or NULL -- as a projected column, a GROUP BY / ORDER BY key, the
  * argument of COUNT / COUNT(DISTINCT); at most 16 distinct sources and 1024 bytes of literals per expression, a result below 2^31 bytes; text inside a
- * condition or under an operator stays refused.  Both operands of a binary operator have one type,
+ * condition or under an operator stays refused.  Text slice functions (scalar_function_expr split_part(s, delim, n), left(s, n), right(s, n), ltrim /
+ * rtrim / btrim(s [, chars])) of a Utf8 column or of another slice of one, at most four deep, are text-valued too: delim (1 to 16 bytes), chars (at
+ * most 16 code points) and n (within Int32; split_part: n >= 1) are literals; NULL in gives NULL out; every other text-producing function (substr,
+ * lower, upper, trim, concat, ...) stays refused.  Both operands of a binary operator have one type,
  * as the reference's planner leaves them.  At execute, integer division / modulo by zero in a row whose operands are not NULL and a
  * CAST whose value does not fit its target are FLOCKGPU_ERR_INVALID for the call (the reference's execute fails with an ArrowError);
  * TRY_CAST yields NULL instead. */

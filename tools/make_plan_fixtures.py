@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/plans/*.json: the physical plans of the five NEXMark target queries (and q7, q13) in the
-serde_json dialect of the reference's DataFusion fork, and bids_above_average.json (a cross join against a global aggregate).
+serde_json dialect of the reference's DataFusion fork, bids_above_average.json (a cross join against a global aggregate), and
+q22_url_dirs.json / person_email_domains.json (text slice functions as projected columns and as a GROUP BY key).
 
 The fork's serialiser cannot be run here (no Rust toolchain), so the plans are AUTHORED from
   * the grammar of the checked-in fixtures flock/src/tests/data/plan/{simple_select,aggregate,join}.json
@@ -467,8 +468,38 @@ def bids_above_average():
     return proj(keep, [(col(f["name"], i), f["name"]) for i, f in enumerate(three + avgp)], three + avgp)
 
 
+def scalar_fn(name, args, return_type):
+    return {"physical_expr": "scalar_function_expr", "name": name, "args": args, "return_type": return_type}
+
+
+def q22_url_dirs():
+    """NEXMark q22 `SELECT auction, bidder, price, split_part(url, '/', 4) AS dir1, split_part(url, '/', 5) AS dir2 FROM bid` over a bid relation
+    that carries a url column (the text slice functions, textslice.hpp): one projection over the scan."""
+    bid = BID[:3] + [field("url", "Utf8")]
+    out = BID[:3] + [field("dir1", "Utf8", True), field("dir2", "Utf8", True)]
+    part = lambda n: scalar_fn("split_part", [col("url", 3), lit("Utf8", "/"), lit("Int64", n)], "Utf8")
+    return proj(rr(memory(bid, [0, 1, 2, 3], "bid")),
+                [(col("auction", 0), "auction"), (col("bidder", 1), "bidder"), (col("price", 2), "price"), (part(4), "dir1"), (part(5), "dir2")], out)
+
+
+def person_email_domains():
+    """`SELECT split_part(email_address, '@', 2) AS domain, COUNT(*) FROM person GROUP BY 1`: the two-phase aggregate with the slice as its key."""
+    inp = [field("email_address", "Utf8")]
+    key = scalar_fn("split_part", [col("email_address", 0), lit("Utf8", "@"), lit("Int64", 2)], "Utf8")
+    part = [field("domain", "Utf8", True), field("COUNT(UInt8(1))[count]", "UInt64", True)]
+    fin = [field("domain", "Utf8", True), field("COUNT(UInt8(1))", "UInt64", True)]
+    cnt = [{"aggregate_expr": "count", "name": "COUNT(UInt8(1))", "data_type": "UInt64", "nullable": True, "expr": lit("UInt8", 1)}]
+    partial = agg(rr(memory(PERSON, [2], "person")), "Partial", [(key, "domain")], cnt, inp, part)
+    final = agg(coalesce(hashp(partial, [col("domain", 0)])), "FinalPartitioned", [(col("domain", 0), "domain")], cnt, inp, fin)
+    return proj(final, [(col("domain", 0), "domain"), (col("COUNT(UInt8(1))", 1), "COUNT(UInt8(1))")], fin)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    for name, fn in (("q22_url_dirs", q22_url_dirs), ("person_email_domains", person_email_domains)):
+        with open(os.path.join(OUT, name + ".json"), "w") as f:
+            json.dump(fn(), f, indent=1, sort_keys=True)
+            f.write("\n")
     with open(os.path.join(OUT, "bids_above_average.json"), "w") as f:
         json.dump(bids_above_average(), f, indent=1, sort_keys=True)
         f.write("\n")
