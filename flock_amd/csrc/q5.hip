@@ -431,11 +431,10 @@ __device__ __forceinline__ void q5_count_tile(const int32_t *__restrict__ auctio
         mn = min(mn, min(min(k[it][0], k[it][1]), min(k[it][2], k[it][3])));
         mx = max(mx, max(max(k[it][0], k[it][1]), max(k[it][2], k[it][3])));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = min(mn, __shfl_xor(mn, o, 64));
-        mx = max(mx, __shfl_xor(mx, o, 64));
-    }
+    // (DPP ladders, scan.hpp: as __shfl_xor steps these were 12 ds_bpermute in six dependent LDS round trips per wave, between the arrival of
+    // the tile's keys and the barrier that opens the LDS phase, on the pipe that phase is bound by; profiles/q5_small_passes.md)
+    mn = wave_min_i32(mn);
+    mx = wave_max_i32(mx);
     if (lane == 0) {
         s_red[wave] = mn;
         s_red[4 + wave] = mx;

@@ -153,6 +153,35 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return v;
 }
 
+// Wave minimum / maximum on the same DPP ladder (row shifts inside the 16-lane rows, then row broadcasts): 6 DPP
+// moves + 6 VALU ops and no LDS crossbar traffic, where a __shfl_xor ladder is 6 dependent ds_bpermute round trips.
+// A lane whose source is outside its row (or masked by the bank / row mask) takes `ident`, the operation's identity
+// (bound_ctrl off).  The total forms in lane 63 and is handed to every lane through readlane.  All 64 lanes must be
+// active.  Used where the reduction sits on a kernel's critical path (q5_count_tile: between the arrival of a tile's
+// keys and its LDS phase); the __shfl_xor forms (wave_max_u32, wave_sum_u64) serve the epilogues everywhere else.
+template <int kCtrl, int kRowMask, int kBankMask>
+__device__ __forceinline__ int dpp_fetch(int ident, int v) {
+    return __builtin_amdgcn_update_dpp(ident, v, kCtrl, kRowMask, kBankMask, false);
+}
+template <class Op>
+__device__ __forceinline__ int wave_reduce_to_lane63(int v, const int ident, Op op) {
+    v = op(v, dpp_fetch<0x111, 0xf, 0xf>(ident, v));   // row_shr:1
+    v = op(v, dpp_fetch<0x112, 0xf, 0xf>(ident, v));   // row_shr:2                  -> four lanes
+    v = op(v, dpp_fetch<0x114, 0xf, 0xe>(ident, v));   // row_shr:4, banks 1-3       -> eight
+    v = op(v, dpp_fetch<0x118, 0xf, 0xc>(ident, v));   // row_shr:8, banks 2-3       -> lane 15 of a row: the row
+    v = op(v, dpp_fetch<0x142, 0xa, 0xf>(ident, v));   // row_bcast:15 into rows 1, 3
+    v = op(v, dpp_fetch<0x143, 0xc, 0xf>(ident, v));   // row_bcast:31 into rows 2, 3 -> lane 63: the wave
+    return v;
+}
+__device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
+    v = wave_reduce_to_lane63(v, 0x7fffffff, [](int a, int b) { return a < b ? a : b; });
+    return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
+    v = wave_reduce_to_lane63(v, (int)0x80000000, [](int a, int b) { return a > b ? a : b; });
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
 // ---- count -> scan -> emit --------------------------------------------------------------------------------
 // The order-preserving operators that replaced the striped scan run as three launches with NO dependence between
 // workgroups inside a launch (nothing to deadlock, no residency assumption, every launch a plain streaming grid):
