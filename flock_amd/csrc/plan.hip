@@ -23,6 +23,7 @@
 #include "cross.hpp"
 #include "pred.hpp"
 #include "distinct.hpp"
+#include "groupwide.hpp"
 #include "reduce.hpp"
 #include "strmatch.hpp"
 #include "textsel.hpp"
@@ -3128,8 +3129,12 @@ struct Exec {
         // ---- key shapes the paths below do not take -- three or more columns, two other than (Int32, Int32) / DISTINCT (Int32, Utf8), NULLs in
         // a two-column key -- group on composite-key ids (relops.hpp key_codes): groups in order of first appearance
         // ... and so does every node with a distinct count, whatever its key: the ids index the ordinary accumulators and the distinct counts alike
-        bool composite = n->group.size() > 2 || distinct;
-        if (n->group.size() == 2 && !distinct) {
+        // ... and every node with five or more accumulators: one pass over the ids updates all of them (groupwide.hpp)
+        int n_accs = 0;
+        for (auto &a : n->aggs) n_accs += ir::agg_accumulators(a.fn);
+        const bool wide = n_accs > kMaxGroupAggs;
+        bool composite = n->group.size() > 2 || distinct || wide;
+        if (n->group.size() == 2 && !distinct && !wide) {
             const TCol &a = in.cols[(size_t)n->group[0]], &b = in.cols[(size_t)n->group[1]];
             composite = a.c.type != ColType::I32 || a.c.valid || b.c.valid || b.c.type != (n->aggs.empty() ? ColType::UTF8 : ColType::I32);
             if (a.c.type == ColType::F64 || b.c.type == ColType::F64) composite = false;   // (refused below with today's message)
@@ -3191,7 +3196,7 @@ struct Exec {
             }
             return FLOCKGPU_OK;
         };
-        AggSpec specs[kMaxGroupAggs];
+        AggSpec specs[kMaxWideAggs];   // (the tables of relops.hpp take kMaxGroupAggs of them; more go through group_by_ids_wide)
         int n_specs = 0;
         struct Out { int first = 0, count = 1; };  // accumulators of aggregate a
         std::vector<Out> outs;
@@ -3206,7 +3211,7 @@ struct Exec {
             Out o;
             o.first = n_specs;
             o.count = ir::agg_accumulators(a.fn);
-            if (n_specs + o.count > kMaxGroupAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxGroupAggs);
+            if (n_specs + o.count > kMaxWideAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxWideAggs);
             // (every accumulator carries its argument's validity: NULLs are skipped, a group without a valid value comes out NULL)
             if (a.fn == AggFn::CountDistinct) {   // no accumulator: a table of its own over the group ids, below
                 const TCol *v = a.arg >= 0 && (size_t)a.arg < in.cols.size() ? &in.cols[(size_t)a.arg] : nullptr;
@@ -3244,7 +3249,7 @@ struct Exec {
         }
         GroupResultN g;
         const int32_t *gid = nullptr;
-        if (composite) FG_TRY(group_composite(n, in, specs, n_specs, &g, &gid));
+        if (composite) FG_TRY(group_composite(n, in, specs, wide ? 0 : n_specs, &g, &gid));   // (wide: the ids and first rows only)
         // A dense integer key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer
         // keys") -- slot = key - min over the column's exact range, no hashing, no int64 copy of the key column.  Everything else (Utf8 /
         // two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
@@ -3313,9 +3318,52 @@ struct Exec {
         t->cols[0].c.nullable = n->schema[0].nullable;
         // ---- aggregate / state columns
         size_t oc = n->group.size();
+        // five or more accumulators: one pass over the ids, and a finish that writes every result column -- AVG's division, the Float64 sum state of a
+        // Partial's AVG, Int32 results, validity bytes -- on the device
+        WideGroupResult wres;
+        std::vector<int> wide_out(n->aggs.size(), -1);   // per aggregate: its first result column in wres
+        if (wide) {
+            WideAggSpec ws[kMaxWideAggs];
+            for (int a = 0; a < n_specs; ++a) ws[a] = WideAggSpec{specs[a].op, specs[a].values, specs[a].type, specs[a].valid};
+            WideOut wo[kMaxWideAggs];
+            int n_wo = 0;
+            size_t c = oc;
+            for (size_t ai = 0; ai < n->aggs.size(); ++ai) {
+                const Agg &a = n->aggs[ai];
+                const Out &o = outs[ai];
+                wide_out[ai] = n_wo;
+                if (a.fn == AggFn::CountDistinct) {
+                    c += 1;
+                } else if (a.fn == AggFn::Avg && (n->single_pass || is_final)) {   // AVG over no valid value is NULL
+                    wo[n_wo++] = WideOut{n->single_pass ? WideOutKind::AvgInt : WideOutKind::AvgF64, o.first, o.first + 1, ColType::F64, 2};
+                    c += 1;
+                } else if (a.fn == AggFn::Avg) {   // its state: [count UInt64, sum Float64]
+                    wo[n_wo++] = WideOut{WideOutKind::Value, o.first, -1, ColType::U64, 0};
+                    wo[n_wo++] = WideOut{WideOutKind::SumAsF64, o.first + 1, -1, ColType::F64, 0};
+                    c += 2;
+                } else {
+                    const ColType want = n->schema[c].type;
+                    const bool f64_acc = specs[o.first].op == AggOp::MAX_F64 || specs[o.first].op == AggOp::MIN_F64;
+                    if (want == ColType::UTF8 || (want == ColType::F64) != f64_acc)
+                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
+                    wo[n_wo++] = WideOut{WideOutKind::Value, o.first, -1, want, a.fn != AggFn::Count ? 1 : 0};   // MIN / MAX / SUM over nothing but NULLs is NULL; COUNT(col) is 0
+                    c += 1;
+                }
+            }
+            FG_TRY(group_by_ids_wide(ctx, node_key(pl, n, "wide").c_str(), gid, in.rows, g.n_groups, ws, n_specs, wo, n_wo, &wres));
+        }
         for (size_t ai = 0; ai < n->aggs.size(); ++ai) {
             const Agg &a = n->aggs[ai];
             const Out &o = outs[ai];
+            if (wide && a.fn != AggFn::CountDistinct) {
+                const int cols = a.fn == AggFn::Avg && !n->single_pass && !is_final ? 2 : 1;
+                for (int k = 0; k < cols; ++k, ++oc) {
+                    t->cols[oc] = dev_col(n->schema[oc].type, wres.col[wide_out[ai] + k], nullptr, 0, n->schema[oc].is_ts);
+                    t->cols[oc].c.nullable = true;
+                    t->cols[oc].c.valid = wres.valid[wide_out[ai] + k];
+                }
+                continue;
+            }
             auto narrow_if_i32 = [&](uint64_t *acc, ColType want, bool ts, size_t col) -> int {
                 if (want == ColType::I32) {
                     int32_t *v = nullptr;

@@ -185,6 +185,7 @@ inline int agg_state_cols(AggFn fn) { return fn == AggFn::Avg ? 2 : 1; }
 inline int agg_accumulators(AggFn fn) { return fn == AggFn::CountDistinct ? 0 : agg_state_cols(fn); }
 constexpr int kMaxDistinctCounts = 4;          // of one aggregate node
 constexpr int kMaxUngroupedAccumulators = 8;   // of one aggregate without GROUP BY (AVG takes two)
+constexpr int kMaxGroupedAccumulators = 16;    // of one GROUP BY (AVG takes two): groupwide.hpp kMaxWideAggs
 // key pairs of one HashJoinExec (the composite-key path, relops.hpp key_codes, takes up to eight columns)
 constexpr int kMaxJoinPairs = 8;
 // One column of a WindowAggExec: ROW_NUMBER(), or an aggregate over the default frame (RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW: the
@@ -982,6 +983,10 @@ struct Builder {
                     if (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(a.fn) && a.fn != AggFn::Count)) { fail(std::string(agg_fn_name(a.fn)) + " needs an integer column"); return nullptr; }
                 }
                 if (accs > kMaxUngroupedAccumulators) { fail("more than " + std::to_string(kMaxUngroupedAccumulators) + " accumulators in one ungrouped aggregate"); return nullptr; }
+            } else {   // GROUP BY: up to four in the tables of relops.hpp, five to sixteen in the one pass over group ids of groupwide.hpp
+                int accs = 0;
+                for (auto &a : n->aggs) accs += agg_accumulators(a.fn);
+                if (accs > kMaxGroupedAccumulators) { fail("more than " + std::to_string(kMaxGroupedAccumulators) + " accumulators in one GROUP BY"); return nullptr; }
             }
             n->in.push_back(std::move(in));
         } else if (t == "hash_join_exec") {

@@ -3,6 +3,7 @@
 // normalised keys, global-memory hash tables; exact for any input.
 #include <algorithm>
 
+#include "orderkey.hpp"
 #include "relops.hpp"
 
 using namespace flockgpu;
@@ -110,12 +111,7 @@ struct AggSpecs {
     int32_t n;
     uint32_t *seen;   // slots x n counters of valid contributions (null when no spec carries validity)
 };
-// doubles <-> unsigned keys of the same order (negative values: all bits flipped; others: the sign bit set)
-__device__ __forceinline__ uint64_t f64_order_key(double d) {
-    const uint64_t b = (uint64_t)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ uint64_t f64_from_order_key(uint64_t k) { return (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k; }
+// (doubles <-> unsigned keys of the same order: orderkey.hpp)
 __device__ __forceinline__ uint64_t agg_identity(int32_t op) {
     switch (op) {
         case (int32_t)AggOp::MAX_S: return (uint64_t)INT64_MIN;

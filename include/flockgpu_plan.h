@@ -85,7 +85,7 @@ typedef struct flockgpu_plan flockgpu_plan;
  * expression or type the engine does not execute (flockgpu_last_error names it).
  * Nodes (`execution_plan` tags): memory_exec, filter_exec, projection_exec, hash_aggregate_exec (Partial / Final / FinalPartitioned: count, max, min,
  * sum, avg; without GROUP BY any list of them over Int32 / Int64 / UInt64 / Timestamp / Float64 columns -- SUM / AVG of integer columns only, up to
- * eight accumulators, AVG taking two -- gives exactly one row in every mode, also over no rows), hash_join_exec (Inner; Semi / Anti: the left input's rows that have / lack a partner, left schema), repartition_exec, coalesce_batches_exec / coalesce_partitions_exec / merge_exec (transparent), sort_exec,
+ * eight accumulators, AVG taking two -- gives exactly one row in every mode, also over no rows; with GROUP BY up to sixteen accumulators per node), hash_join_exec (Inner; Semi / Anti: the left input's rows that have / lack a partner, left schema), repartition_exec, coalesce_batches_exec / coalesce_partitions_exec / merge_exec (transparent), sort_exec,
  * global_limit_exec / local_limit_exec, window_agg_exec (ROW_NUMBER()), cross_join_exec (`left`, `right`: the left input's columns followed by the right
  * input's, L x R rows, pair (left row i, right row j) at output row i * R + j however the inputs were fed; a result of 2^31 rows or more, or an output
  * Utf8 column of 2^31 bytes or more, fails the execute with FLOCKGPU_ERR_UNSUPPORTED before anything is allocated or launched).
