@@ -306,7 +306,7 @@ namespace flockgpu {
 
 int wide_group_bins(int n_specs) { return n_specs <= 8 ? 448 : 224; }
 
-int group_by_ids_wide(flockgpu_ctx *ctx, const char *name, const int32_t *gid, int64_t rows, int64_t n_groups, const WideAggSpec *specs, int n_specs,
+int group_by_ids_wide(flockgpu_ctx *ctx, const char *name, const int32_t *gid, int64_t rows, int64_t n_groups, const AggSpec *specs, int n_specs,
                       const WideOut *outs, int n_outs, WideGroupResult *out) {
     *out = WideGroupResult{};
     const std::string base = name;
@@ -334,7 +334,7 @@ int group_by_ids_wide(flockgpu_ctx *ctx, const char *name, const int32_t *gid, i
     constexpr uint64_t kSign = 0x8000000000000000ull;
     // (the columns that carry values first: a COUNT(col) then finds its validity column among them)
     for (int a = 0; a < n_specs; ++a) {
-        const WideAggSpec &s = specs[a];
+        const AggSpec &s = specs[a];
         col_of[a] = col_cell_of[a] = -1;
         if (s.op == AggOp::COUNT) continue;
         if (!s.values || s.type == ColType::UTF8) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: an accumulator without an integer or Float64 argument", name);

@@ -18,18 +18,15 @@ namespace flockgpu {
 constexpr int kMaxWideAggs = 16;   // accumulators of one node (AVG takes two)
 constexpr int kMaxWideCols = 16;   // distinct (values, validity) argument columns of one node: every accumulator may read a column of its own (a Final's state columns do)
 
-struct WideAggSpec {
-    AggOp op = AggOp::COUNT;
-    const void *values = nullptr;   // null for COUNT
-    ColType type = ColType::I64;    // storage type of `values`
-    const uint8_t *valid = nullptr; // validity of the argument (may be null)
-};
-// What the finish writes for one result column from the accumulators acc (and acc2), narrowed to Int32 where `type` says so
+// One result column of an aggregate node, described from the node's accumulators.  The lowering of plan.hip (lower_aggregates) writes one per column
+// behind the keys, and all three back-ends read the same list: this pass finishes its columns on the device, the tables of relops.hpp finish them
+// with helper launches, the ungrouped pass (reduce.hpp) restates them as its outputs.  Int32 results are narrowed where `type` says so.
 enum class WideOutKind : int32_t {
-    Value = 0,      // the accumulator: a count, a sum, a minimum or maximum (Float64 ones back from their order keys)
-    SumAsF64 = 1,   // (double) the signed integer sum: the sum state of a Partial's AVG
-    AvgInt = 2,     // (double) integer sum acc2 / (double) count acc: AVG in one pass
-    AvgF64 = 3,     // Float64 sum acc2 / (double) count acc: AVG in Final mode
+    Value = 0,          // the accumulator: a count, a sum, a minimum or maximum (Float64 ones back from their order keys)
+    SumAsF64 = 1,       // (double) the integer sum: the sum state of a Partial's AVG
+    AvgInt = 2,         // (double) integer sum acc2 / (double) count acc: AVG in one pass
+    AvgF64 = 3,         // Float64 sum acc2 / (double) count acc: AVG in Final mode
+    DistinctCount = 4,  // no accumulator: a table of its own over the group ids (distinct.hpp); `acc` is the aggregate's place in the node.  Never handed to this pass.
 };
 struct WideOut {
     WideOutKind kind = WideOutKind::Value;
@@ -46,7 +43,7 @@ struct WideGroupResult {
 // LDS bins per tile for a node of n_specs accumulators (a tile whose ids span more goes to the global cells directly)
 int wide_group_bins(int n_specs);
 // gid[i] in [0, n_groups): one Int32 per row (key_codes').  Launches only: an id outside [0, n_groups) reaches no cell.
-int group_by_ids_wide(flockgpu_ctx *ctx, const char *name, const int32_t *gid, int64_t rows, int64_t n_groups, const WideAggSpec *specs, int n_specs,
+int group_by_ids_wide(flockgpu_ctx *ctx, const char *name, const int32_t *gid, int64_t rows, int64_t n_groups, const AggSpec *specs, int n_specs,
                       const WideOut *outs, int n_outs, WideGroupResult *out);
 
 }  // namespace flockgpu

@@ -2500,7 +2500,7 @@ struct Exec {
                 if (x.arg >= 0) {
                     const TCol &a = in.cols[(size_t)x.arg];
                     if (!a.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: a window argument column was not materialised");
-                    if (x.fn != AggFn::Count && (a.c.type == ColType::UTF8 || (a.c.type == ColType::F64 && !agg_is_minmax(x.fn))))
+                    if (!agg_takes(x.fn, a.c.type))
                         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", agg_fn_name(x.fn));
                     g.values = a.c.values;
                     g.type = a.c.type;
@@ -2944,17 +2944,101 @@ struct Exec {
         }
     }
 
-    // ---- no GROUP BY: COUNT / SUM / MIN / MAX / AVG, any list of them, in Partial and Final mode -> ONE row in every case (reduce.hpp): one streaming
-    // pass for all accumulators, a fold that writes the row on the device, no wait.  Directly over a filter the filter is not materialised: its
-    // predicate pass leaves flag words and the pass reads the filter's input columns under them.
+    // ---- HashAggregateExec.  lower_aggregates restates a node's aggregates ONCE, as accumulators and as result columns described from them (WideOut,
+    // groupwide.hpp).  Three back-ends run the two lists: the ungrouped streaming pass (reduce.hpp), the tables of relops.hpp (at most kMaxGroupAggs
+    // accumulators) and the one pass over group ids of groupwide.hpp (up to kMaxWideAggs).  A new aggregate function is added in the lowering, with a
+    // kernel op where it needs one.
+    struct AggAcc {
+        AggOp op = AggOp::COUNT;
+        int col = -1;             // input column of the argument (-1: COUNT(*)): an index -- each back-end resolves pointers under its own rule
+        bool with_valid = true;   // NULL arguments reach no accumulator (false: a Final's sums of states, which read every state row)
+    };
+    struct AggLowering {
+        AggAcc accs[kMaxWideAggs];
+        int n_accs = 0;
+        std::vector<WideOut> outs;   // one per column of the node's schema behind the keys
+    };
+    // `grouped` stands for the differences between the back-ends that the node's result or refusal depends on; each is marked "(back-ends)" below.
+    // Every refusal of an aggregate is made here, before a table runs, one aggregate after the other.  A node that earns two refusals at once can so
+    // name another of them than it did while the checks were spread out: "into a column of another kind" used to follow the grouped tables (and the
+    // refusals of number_groups: pair key types, a Float64 key), and to precede, aggregate by aggregate, the ungrouped pass's "more than %d argument
+    // columns", which now follows the whole list.
+    int lower_aggregates(const Node *n, const Table &in, bool grouped, AggLowering *L) {
+        const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
+        // (back-ends) an argument nobody materialised because it holds nothing but NULLs: the ungrouped pass takes it (no program column, every
+        // result over it NULL or 0), the grouped tables read pointers and refuse it
+        auto readable = [&](const TCol &v) { return v.present || (!grouped && v.c.all_null); };
+        auto need = [&](const TCol *v, AggFn as, const char *what) -> int {
+            if (!v || !agg_takes(as, v->c.type) || !readable(*v)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", what);
+            return FLOCKGPU_OK;
+        };
+        auto acc = [&](AggOp op, int col, bool with_valid) {
+            L->accs[L->n_accs] = AggAcc{op, col, with_valid};
+            return L->n_accs++;
+        };
+        for (size_t ai = 0; ai < n->aggs.size(); ++ai) {
+            const Agg &a = n->aggs[ai];
+            // (the ungrouped pass has refused more than kReduceMaxSlots before it comes here)
+            if (L->n_accs + ir::agg_accumulators(a.fn) > kMaxWideAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxWideAggs);
+            const TCol *v = a.arg >= 0 && (size_t)a.arg < in.cols.size() ? &in.cols[(size_t)a.arg] : nullptr;
+            const size_t oc = n->group.size() + L->outs.size();
+            const ColType want = oc < n->schema.size() ? n->schema[oc].type : ColType::U64;
+            if (a.fn == AggFn::CountDistinct) {   // no accumulator: a table of its own, behind the others on the stream
+                if (!v || !agg_takes(a.fn, v->c.type) || !(v->present || v->c.all_null))
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: distinct_count needs an integer or Utf8 column");
+                L->outs.push_back(WideOut{WideOutKind::DistinctCount, (int)ai, -1, ColType::U64, 0});
+            } else if (a.fn == AggFn::Count && is_final) {   // the sum of the count states, every state row read: over no state row it is 0, not NULL
+                FG_TRY(need(v, AggFn::Sum, "the COUNT state"));
+                L->outs.push_back(WideOut{WideOutKind::Value, acc(AggOp::SUM_INT, a.arg, false), -1, want, 0});
+            } else if (a.fn == AggFn::Count) {   // COUNT(*) / COUNT(UInt8(1)) counts rows, COUNT(col) the rows whose col is not NULL: only its validity is read
+                // (back-ends) grouped, any column will do; the ungrouped pass streams fixed-width columns -- no Utf8 -- and wants the column
+                // materialised where it has validity to read
+                if (!grouped && a.arg >= 0) {
+                    if (!v || v->c.type == ColType::UTF8) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: count needs an integer column");
+                    if (v->c.all_null || v->c.valid) FG_TRY(need(v, AggFn::Count, "count"));
+                }
+                L->outs.push_back(WideOut{WideOutKind::Value, acc(AggOp::COUNT, a.arg, true), -1, want, 0});
+            } else if (a.fn != AggFn::Avg) {   // SUM of an integer column; MIN / MAX of an integer or a Float64 one
+                FG_TRY(need(v, a.fn, agg_fn_name(a.fn)));
+                const ColType at = v->c.type;
+                // ... into a column of another kind.  (back-ends) The grouped finish narrows a 64-bit accumulator into an Int32 column and checks SUM
+                // as well; the ungrouped fold writes 64-bit words, so MIN / MAX there keep Int32 to Int32, and SUM goes unchecked
+                const bool other = want == ColType::UTF8 || (want == ColType::F64) != (at == ColType::F64) || (!grouped && (want == ColType::I32) != (at == ColType::I32));
+                if (other && (grouped || agg_is_minmax(a.fn)))
+                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
+                // MIN / MAX / SUM over nothing but NULLs is NULL
+                L->outs.push_back(WideOut{WideOutKind::Value, acc(agg_op_for(a.fn, at), a.arg, true), -1, want, 1});
+            } else if (is_final) {   // avg: (count, sum) states -> sum / count; over no valid value it is NULL
+                FG_TRY(need(v, AggFn::Sum, "the AVG count state"));
+                const TCol *sm = a.arg2 >= 0 && (size_t)a.arg2 < in.cols.size() ? &in.cols[(size_t)a.arg2] : nullptr;
+                if (!sm || sm->c.type != ColType::F64 || (grouped && !sm->present)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: the AVG sum state must be Float64");
+                if (!readable(*sm)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: the AVG sum state needs an integer column");
+                const int cnt = acc(AggOp::SUM_INT, a.arg, false);
+                L->outs.push_back(WideOut{WideOutKind::AvgF64, cnt, acc(AggOp::SUM_F64, a.arg2, false), ColType::F64, 2});
+            } else {   // (execute-time messages say AVG, create-time ones avg)
+                FG_TRY(need(v, AggFn::Avg, "AVG"));
+                const int cnt = acc(AggOp::COUNT, a.arg, true), sum = acc(AggOp::SUM_INT, a.arg, true);
+                if (n->single_pass) {   // what Final makes of the one state row: (double) integer sum / (double) count
+                    L->outs.push_back(WideOut{WideOutKind::AvgInt, cnt, sum, ColType::F64, 2});
+                } else {   // its state: [count UInt64, sum Float64]
+                    L->outs.push_back(WideOut{WideOutKind::Value, cnt, -1, ColType::U64, 0});
+                    L->outs.push_back(WideOut{WideOutKind::SumAsF64, sum, -1, ColType::F64, 0});
+                }
+            }
+        }
+        return FLOCKGPU_OK;
+    }
+
+    // ---- no GROUP BY: any list of aggregates, in Partial and Final mode -> ONE row in every case (reduce.hpp): one streaming pass for all
+    // accumulators, a fold that writes the row on the device, no wait.  Directly over a filter the filter is not materialised: its predicate pass
+    // leaves flag words and the pass reads the filter's input columns under them.
     int exec_global_aggregate(const Node *n, Table *t) {
         Table in;
         const uint32_t *flags = nullptr, *wave_counts = nullptr;
         int32_t flag_tiles = 0;
         std::vector<int> map;
         // (a distinct count reads its argument column as a whole: under it the filter is materialised as ever)
-        const bool distinct = ir::has_distinct_count(n);
-        const Node *f = distinct ? nullptr : filter_below(n->in[0].get(), &map);
+        const Node *f = ir::has_distinct_count(n) ? nullptr : filter_below(n->in[0].get(), &map);
         if (f) {
             Table fin;
             FG_TRY(filter_flags(f, &fin, &flags, &wave_counts, &flag_tiles));
@@ -2964,124 +3048,336 @@ struct Exec {
         } else {
             FG_TRY(exec(n->in[0].get(), &in));
         }
-        const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
-        ReduceProgram P;
-        // the program's column for input column c (*out = -1: the column holds nothing but NULLs)
-        auto col_of = [&](int c, const char *what, bool allow_f64, int *out) -> int {
-            if (c < 0 || (size_t)c >= in.cols.size() || in.cols[(size_t)c].c.type == ColType::UTF8 || (in.cols[(size_t)c].c.type == ColType::F64 && !allow_f64) ||
-                (!in.cols[(size_t)c].present && !in.cols[(size_t)c].c.all_null))
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", what);
-            const DevColumn &d = in.cols[(size_t)c].c;
-            *out = -1;
-            if (d.all_null) return FLOCKGPU_OK;
-            for (int i = 0; i < P.n_cols; ++i)
-                if (P.cols[i].values == d.values && P.cols[i].valid == d.valid && P.cols[i].type == (int32_t)d.type) *out = i;
-            if (*out >= 0) return FLOCKGPU_OK;
-            if (P.n_cols == kReduceMaxCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d argument columns in one ungrouped aggregate", kReduceMaxCols);
-            P.cols[P.n_cols].values = d.values;
-            P.cols[P.n_cols].valid = d.valid;
-            P.cols[P.n_cols].type = (int32_t)d.type;
-            *out = P.n_cols++;
-            return FLOCKGPU_OK;
-        };
-        auto slot_of = [&](ReduceKind kind, int col, uint64_t flip, bool f64, bool inv, int *out) -> int {
-            *out = -1;
-            if (col < 0) return FLOCKGPU_OK;
-            for (int i = 0; i < P.n_slots; ++i)
-                if (P.slots[i].kind == (int32_t)kind && P.slots[i].col == col && P.slots[i].flip == flip) *out = i;
-            if (*out >= 0) return FLOCKGPU_OK;
-            if (P.n_slots == kReduceMaxSlots) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one ungrouped aggregate", kReduceMaxSlots);
-            P.slots[P.n_slots].kind = (int32_t)kind;
-            P.slots[P.n_slots].col = col;
-            P.slots[P.n_slots].flip = flip;
-            P.slots[P.n_slots].f64 = f64;
-            P.slots[P.n_slots].inv = inv;
-            *out = P.n_slots++;
-            return FLOCKGPU_OK;
-        };
-        auto emit = [&](ReduceOutKind kind, int col, int a, int b) {
-            ReduceOut &o = P.outs[P.n_outs++];
-            o.kind = (int32_t)kind;
-            o.col = col;
-            o.a = a;
-            o.b = b;
-        };
-        if (ir::ungrouped_accumulators(n) > kReduceMaxSlots)
+        if (ir::node_accumulators(n) > kReduceMaxSlots)
             return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one ungrouped aggregate", kReduceMaxSlots);
+        AggLowering L;
+        FG_TRY(lower_aggregates(n, in, false, &L));
+        // ---- the accumulators as program columns (distinct ones) and slots (distinct ones).  Validity is the column's here, not the accumulator's:
+        // a state column that carries validity is read under it.
+        ReduceProgram P;
         constexpr uint64_t kSign = 0x8000000000000000ull;
-        for (auto &a : n->aggs) {
-            const size_t oc = (size_t)P.n_outs;
-            int c = -1, s = -1, s2 = -1;
-            if (a.fn == AggFn::CountDistinct) {   // its place in the row: distinct_count_by_group writes the value below, behind the fold on the stream
-                if (a.arg < 0 || (size_t)a.arg >= in.cols.size() || in.cols[(size_t)a.arg].c.type == ColType::F64 ||
-                    (!in.cols[(size_t)a.arg].present && !in.cols[(size_t)a.arg].c.all_null))
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: distinct_count needs an integer or Utf8 column");
-                emit(ReduceOutKind::Rows, -1, -1, -1);
-            } else if (a.fn == AggFn::Count) {
-                if (is_final) {   // the sum of the count states; over no state row it is 0, not NULL
-                    FG_TRY(col_of(a.arg, "the COUNT state", false, &c));
-                    FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
-                    emit(ReduceOutKind::ValueAlways, c, s, -1);
-                } else if (a.arg < 0) {   // COUNT(*) / COUNT(UInt8(1))
-                    emit(ReduceOutKind::Rows, -1, -1, -1);
-                } else {
-                    if ((size_t)a.arg >= in.cols.size() || in.cols[(size_t)a.arg].c.type == ColType::UTF8)
-                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: count needs an integer column");
-                    const DevColumn &d = in.cols[(size_t)a.arg].c;
-                    if (!d.all_null && !d.valid) {   // no NULL among the values: the rows selected
-                        emit(ReduceOutKind::Rows, -1, -1, -1);
-                    } else {
-                        FG_TRY(col_of(a.arg, "count", true, &c));
-                        emit(ReduceOutKind::ColCount, c, -1, -1);
-                    }
-                }
-            } else if (a.fn == AggFn::Sum) {
-                FG_TRY(col_of(a.arg, "sum", false, &c));
-                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
-                emit(ReduceOutKind::Value, c, s, -1);
-            } else if (agg_is_minmax(a.fn)) {
-                FG_TRY(col_of(a.arg, agg_fn_name(a.fn), true, &c));
-                const ColType at = in.cols[(size_t)a.arg].c.type, want = n->schema[oc].type;
-                if ((want == ColType::F64) != (at == ColType::F64) || (want == ColType::I32) != (at == ColType::I32) || want == ColType::UTF8)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
-                const bool inv = a.fn == AggFn::Min;
-                FG_TRY(slot_of(ReduceKind::UMax, c, (at == ColType::U64 ? 0 : kSign) ^ (inv ? ~uint64_t(0) : 0), at == ColType::F64, inv, &s));
-                emit(ReduceOutKind::Value, c, s, -1);
-            } else if (is_final) {   // avg: (count, sum) states -> sum / count
-                FG_TRY(col_of(a.arg, "the AVG count state", false, &c));
-                int c2 = -1;
-                if (a.arg2 < 0 || (size_t)a.arg2 >= in.cols.size() || in.cols[(size_t)a.arg2].c.type != ColType::F64)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: the AVG sum state must be Float64");
-                FG_TRY(col_of(a.arg2, "the AVG sum state", true, &c2));
-                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
-                FG_TRY(slot_of(ReduceKind::SumF64, c2, 0, true, false, &s2));
-                emit(ReduceOutKind::AvgFinal, c, s, s2);
-            } else if (n->single_pass) {   // avg in one pass: what Final makes of the one state row -- (double) integer sum / (double) count
-                FG_TRY(col_of(a.arg, "AVG", false, &c));
-                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
-                emit(ReduceOutKind::AvgOnePass, c, s, in.cols[(size_t)a.arg].c.type == ColType::U64 ? 1 : 0);
-            } else {   // avg -> its state: [count UInt64, sum Float64]
-                FG_TRY(col_of(a.arg, "AVG", false, &c));
-                FG_TRY(slot_of(ReduceKind::SumInt, c, 0, false, false, &s));
-                emit(ReduceOutKind::ColCount, c, -1, -1);
-                emit(ReduceOutKind::SumAsF64, c, s, in.cols[(size_t)a.arg].c.type == ColType::U64 ? 1 : 0);
+        int pcol[kMaxWideAggs], pslot[kMaxWideAggs];   // per accumulator; -1: no column (nothing but NULLs, or none read) / no slot (a count)
+        bool rows_count[kMaxWideAggs];                 // a COUNT that is the count of the selected rows
+        bool uns[kMaxWideAggs];
+        for (int a = 0; a < L.n_accs; ++a) {
+            const AggAcc &A = L.accs[a];
+            pcol[a] = pslot[a] = -1;
+            uns[a] = false;
+            // COUNT(*), and COUNT over a column without validity: the rows selected, no column read.  (The count state of a Partial's AVG over such a
+            // column was the column's count, ColCount, before the lowering was shared: the same number -- every selected row reaches the column's
+            // slots -- from the same launches.)
+            rows_count[a] = A.col < 0 || (A.op == AggOp::COUNT && !in.cols[(size_t)A.col].c.all_null && !in.cols[(size_t)A.col].c.valid);
+            if (rows_count[a]) continue;
+            const DevColumn &d = in.cols[(size_t)A.col].c;
+            uns[a] = d.type == ColType::U64;
+            if (d.all_null) continue;
+            for (int i = 0; i < P.n_cols; ++i)
+                if (P.cols[i].values == d.values && P.cols[i].valid == d.valid && P.cols[i].type == (int32_t)d.type) pcol[a] = i;
+            if (pcol[a] < 0) {
+                if (P.n_cols == kReduceMaxCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d argument columns in one ungrouped aggregate", kReduceMaxCols);
+                P.cols[P.n_cols].values = d.values;
+                P.cols[P.n_cols].valid = d.valid;
+                P.cols[P.n_cols].type = (int32_t)d.type;
+                pcol[a] = P.n_cols++;
+            }
+            if (A.op == AggOp::COUNT) continue;   // (the pass counts every column's rows)
+            ReduceSlot s;
+            s.col = pcol[a];
+            if (A.op == AggOp::SUM_INT) {
+                s.kind = (int32_t)ReduceKind::SumInt;
+            } else if (A.op == AggOp::SUM_F64) {
+                s.kind = (int32_t)ReduceKind::SumF64;
+                s.f64 = 1;
+            } else {   // a maximum of order keys; a minimum is the maximum of the complement
+                s.kind = (int32_t)ReduceKind::UMax;
+                s.inv = A.op == AggOp::MIN_S || A.op == AggOp::MIN_U || A.op == AggOp::MIN_F64;
+                s.f64 = A.op == AggOp::MAX_F64 || A.op == AggOp::MIN_F64;
+                s.flip = (A.op == AggOp::MAX_U || A.op == AggOp::MIN_U ? 0 : kSign) ^ (s.inv ? ~uint64_t(0) : 0);
+            }
+            for (int i = 0; i < P.n_slots; ++i)
+                if (P.slots[i].kind == s.kind && P.slots[i].col == s.col && P.slots[i].flip == s.flip) pslot[a] = i;
+            if (pslot[a] < 0) {
+                if (P.n_slots == kReduceMaxSlots) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one ungrouped aggregate", kReduceMaxSlots);
+                P.slots[P.n_slots] = s;
+                pslot[a] = P.n_slots++;
             }
         }
-        if ((size_t)P.n_outs != n->schema.size()) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: an ungrouped aggregate whose schema is not its aggregates'");
+        // ---- the result columns as the fold's outputs
+        if (L.outs.size() != n->schema.size() || L.outs.size() > (size_t)kReduceMaxOuts)
+            return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: an ungrouped aggregate whose schema is not its aggregates'");
+        for (const WideOut &w : L.outs) {
+            ReduceOut &o = P.outs[P.n_outs++];
+            const int a = w.kind == WideOutKind::DistinctCount ? -1 : w.kind == WideOutKind::AvgInt ? w.acc2 : w.acc;   // the accumulator whose column is counted
+            o.col = a < 0 ? -1 : pcol[a];
+            o.a = a < 0 ? -1 : pslot[a];
+            o.b = -1;
+            switch (w.kind) {
+                case WideOutKind::DistinctCount: o.kind = (int32_t)ReduceOutKind::Rows; break;   // its place in the row, valid: distinct_count_by_group writes the value below
+                case WideOutKind::Value:
+                    if (L.accs[a].op == AggOp::COUNT) o.kind = (int32_t)(rows_count[a] ? ReduceOutKind::Rows : ReduceOutKind::ColCount);
+                    else o.kind = (int32_t)(w.validity ? ReduceOutKind::Value : ReduceOutKind::ValueAlways);
+                    break;
+                // (back-ends) a UInt64 sum becomes a double as unsigned here; both grouped finishes convert the 64-bit sum as signed
+                case WideOutKind::SumAsF64: o.kind = (int32_t)ReduceOutKind::SumAsF64; o.b = uns[a] ? 1 : 0; break;
+                case WideOutKind::AvgInt: o.kind = (int32_t)ReduceOutKind::AvgOnePass; o.b = uns[a] ? 1 : 0; break;
+                case WideOutKind::AvgF64: o.kind = (int32_t)ReduceOutKind::AvgFinal; o.b = pslot[w.acc2]; break;
+            }
+        }
         uint64_t *out = nullptr;
         FG_TRY(arena_get_t(ctx, node_key(pl, n, "gagg").c_str(), (size_t)kReduceMaxOuts + kReduceMaxOuts / 8 + 2, &out));
         uint8_t *ov = reinterpret_cast<uint8_t *>(out + kReduceMaxOuts);
         FG_TRY(reduce_global(ctx, node_key(pl, n, "gred").c_str(), P, in.rows, flags, wave_counts, flag_tiles, out, ov));
         // the distinct counts: every row in one group, the count straight into the row (never NULL: the fold marked the place valid)
-        for (size_t i = 0; i < n->aggs.size() && distinct; ++i)
-            if (n->aggs[i].fn == AggFn::CountDistinct)
-                FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", (int)i).c_str(), nullptr, 1, in.cols[(size_t)n->aggs[i].arg].c, in.rows, out + i));
+        for (size_t o = 0; o < L.outs.size(); ++o)
+            if (L.outs[o].kind == WideOutKind::DistinctCount)
+                FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", L.outs[o].acc).c_str(), nullptr, 1, in.cols[(size_t)n->aggs[(size_t)L.outs[o].acc].arg].c, in.rows, out + o));
         t->rows = 1;
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->schema.size(); ++i) {
             t->cols[i] = dev_col(n->schema[i].type, out + i, nullptr, 0, n->schema[i].is_ts);
             t->cols[i].c.valid = ov + i;
             t->cols[i].c.nullable = true;
+        }
+        return FLOCKGPU_OK;
+    }
+
+    // ---- no GROUP BY: MAX of one integer column -> one row (NULL over no input)
+    int exec_lone_max(const Node *n, const Table &in, Table *t) {
+        const ColType at = n->aggs.size() == 1 && n->aggs[0].arg >= 0 ? in.cols[(size_t)n->aggs[0].arg].c.type : ColType::UTF8;
+        if (n->aggs.size() != 1 || n->aggs[0].fn != AggFn::Max || at == ColType::UTF8 || at == ColType::F64 || !in.cols[(size_t)n->aggs[0].arg].present)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: global aggregate other than MAX over an integer column");
+        const TCol &a = in.cols[(size_t)n->aggs[0].arg];
+        int64_t mx = 0;
+        int any = 0;
+        if (!a.c.all_null) FG_TRY(reduce_max(ctx, a.c, in.rows, &mx, &any));
+        int64_t *d = nullptr;
+        FG_TRY(arena_get_t(ctx, node_key(pl, n, "max").c_str(), 2, &d));
+        // the one value travels as kernel arguments (a host-to-device copy call costs ~10 us of host time; Int32 reads the low word)
+        FG_TRY(fill_words(ctx, FillList().add(d, (uint32_t)(uint64_t)mx, 1).add(reinterpret_cast<uint32_t *>(d) + 1, (uint32_t)((uint64_t)mx >> 32), 1)));
+        t->rows = 1;
+        t->cols[0] = dev_col(at, d, nullptr, 0, a.c.is_ts);
+        t->cols[0].c.nullable = true;
+        t->cols[0].c.all_null = !any;
+        return FLOCKGPU_OK;
+    }
+
+    // ---- DISTINCT (Int32, Utf8)
+    int exec_distinct_pair(const Node *n, const Table &in, Table *t) {
+        const TCol &k = in.cols[(size_t)n->group[0]], &s = in.cols[(size_t)n->group[1]];
+        if (k.c.type != ColType::I32 || s.c.type != ColType::UTF8 || !k.present || !s.present)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: two-column GROUP BY other than (Int32, Utf8)");
+        if (k.c.valid || s.c.valid) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: DISTINCT over columns that hold NULLs");
+        int32_t *rows = nullptr;
+        int64_t n_out = 0;
+        FG_TRY(distinct_i32_utf8(ctx, node_key(pl, n, "dist").c_str(), static_cast<const int32_t *>(k.c.values),
+                                 flockgpu_utf8{s.c.offsets, static_cast<const uint8_t *>(s.c.values)}, in.rows, &rows, &n_out));
+        t->rows = n_out;
+        FG_TRY(take_column(ctx, node_key(pl, n, "take", 0).c_str(), k.c, rows, n_out, &t->cols[0].c));
+        FG_TRY(take_column(ctx, node_key(pl, n, "take", 1).c_str(), s.c, rows, n_out, &t->cols[1].c));
+        t->cols[0].present = t->cols[1].present = true;
+        return FLOCKGPU_OK;
+    }
+
+    // ---- the key shapes of GROUP BY, chosen once per execute from the node and its input's columns
+    enum class KeyShape {
+        Int,              // one Int32 / Int64 / UInt64 / Timestamp column: the dense (direct-address) table where number_groups finds it fits, else the hashed one
+        Utf8,             // one Utf8 column, grouped on its dictionary codes: dense by construction where the accumulators allow, else hashed
+        PairI32,          // (Int32, Int32) without NULLs, packed into one 64-bit key
+        DistinctI32Utf8,  // DISTINCT (Int32, Utf8): no aggregates
+        Composite,        // ids of composite keys (relops.hpp key_codes), groups in order of first appearance: three or more columns, two other than the
+                          // pairs above, NULLs in a two-column key -- and every node that needs the ids themselves (a distinct count; more than
+                          // kMaxGroupAggs accumulators), whatever its key
+    };
+    struct KeyPlan {
+        KeyShape shape = KeyShape::Composite;
+        // NULL group keys form ONE group (DataFusion groups NULLs together): an Int32 key column widened to 64 bits has room for a value no Int32
+        // takes (kNullKey), and so have a Utf8 column's dictionary codes (row numbers) ...
+        bool null_keys = false;
+        // ... and a 64-bit key (Int64 / UInt64 / Timestamp) hands its validity to the GROUP BY itself, which keeps the NULLs in a slot of their own
+        bool null_in_table = false;
+    };
+    static constexpr int64_t kNullKey = int64_t(1) << 40;
+    int choose_key_shape(const Node *n, const Table &in, bool needs_ids, KeyPlan *kp) {
+        bool composite = n->group.size() > 2 || needs_ids;
+        if (n->group.size() == 2 && !needs_ids) {
+            const TCol &a = in.cols[(size_t)n->group[0]], &b = in.cols[(size_t)n->group[1]];
+            composite = a.c.type != ColType::I32 || a.c.valid || b.c.valid || b.c.type != (n->aggs.empty() ? ColType::UTF8 : ColType::I32);
+            if (a.c.type == ColType::F64 || b.c.type == ColType::F64) composite = false;   // (refused by the pair's own path, with its message)
+        }
+        if (composite) {
+            if (n->group.size() > (size_t)kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than %d columns", kMaxKeyCols);
+            for (int c : n->group)
+                if (in.cols[(size_t)c].c.type == ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a Float64 column");
+            kp->shape = KeyShape::Composite;
+            return FLOCKGPU_OK;
+        }
+        const TCol &k = in.cols[(size_t)n->group[0]];
+        if (n->group.size() == 2) kp->shape = n->aggs.empty() ? KeyShape::DistinctI32Utf8 : KeyShape::PairI32;
+        else kp->shape = k.c.type == ColType::UTF8 ? KeyShape::Utf8 : KeyShape::Int;
+        if (kp->shape == KeyShape::DistinctI32Utf8) return FLOCKGPU_OK;
+        kp->null_keys = k.c.valid != nullptr;
+        if (kp->null_keys && kp->shape == KeyShape::PairI32) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: NULLs in a two-column GROUP BY key");
+        kp->null_in_table = kp->null_keys && kp->shape == KeyShape::Int && k.c.type != ColType::I32;
+        return FLOCKGPU_OK;
+    }
+
+    // ---- number the groups: runs the table the key shape takes over `specs`.  *gid: the rows' group ids (Composite alone).
+    int number_groups(const Node *n, const Table &in, const KeyPlan &kp, const AggSpec *specs, int n_specs, GroupResultN *g, const int32_t **gid) {
+        if (kp.shape == KeyShape::Composite) return group_composite(n, in, specs, n_specs, g, gid);
+        const TCol &k = in.cols[(size_t)n->group[0]];
+        // A dense key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer keys").
+        // Everything else (two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
+        const bool fit = specs_fit_dense(specs, n_specs) && !kp.null_keys && k.present && in.rows > 0;
+        int64_t *keys = nullptr;   // the hash table's: every key normalised to one int64 per row
+        if (kp.shape == KeyShape::PairI32) {
+            const TCol &k2 = in.cols[(size_t)n->group[1]];
+            if (k.c.type != ColType::I32 || k2.c.type != ColType::I32 || !k.present || !k2.present)
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: two-column GROUP BY other than (Int32, Int32) / (Int32, Utf8)");
+            if (k2.c.valid) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: NULLs in a two-column GROUP BY key");
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "gk").c_str(), (size_t)in.rows + 2, &keys));
+            FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(k.c.values), static_cast<const int32_t *>(k2.c.values), in.rows, keys));
+        } else if (kp.shape == KeyShape::Utf8) {   // group on the strings' dictionary codes; the key column is taken from the first rows
+            if (!k.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
+            FG_TRY(arena_get_t(ctx, node_key(pl, n, "gk").c_str(), (size_t)in.rows + 2, &keys));
+            FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), k.c, in.rows, keys, nullptr, 0, nullptr));
+            // The codes are row numbers of the key's own relation: dense by construction.  The code of a group IS a row that carries the group's
+            // string, so it also stands in for the first row the key column is taken from.
+            if (fit && in.rows < (int64_t(1) << 31)) {
+                FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), plain_col(ColType::I64, keys), in.rows, 0, in.rows - 1, specs, n_specs, g));
+                int32_t *rep = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "rep").c_str(), (size_t)g->n_groups + 4, &rep));
+                FG_TRY(narrow_i64_to_i32(ctx, g->keys, g->n_groups, rep));
+                g->first_row = rep;
+                return FLOCKGPU_OK;
+            }
+            // (a NULL's bytes are whatever its slot holds -- usually nothing, which is also the empty string's code: NULLs get their own key;
+            // the group's key comes out NULL through the validity of its first row, write_key_columns)
+            if (kp.null_keys) FG_TRY(replace_invalid_i64(ctx, keys, k.c.valid, in.rows, kNullKey));
+        } else {
+            // slot = key - min over the column's exact range: no hashing, no int64 copy of the key column
+            if (fit && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64) && stats_worth_it(k, in.rows)) {
+                int64_t kmin = 0, kmax = 0;
+                FG_TRY(int_col_stats(k, in.rows, &kmin, &kmax));
+                if (dense_range_ok(kmin, kmax, in.rows, k.c.type == ColType::U64)) return group_by_dense(ctx, node_key(pl, n, "grp").c_str(), k.c, in.rows, kmin, kmax, specs, n_specs, g);
+            }
+            if (k.c.type == ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a Float64 column");
+            FG_TRY(key_i64(n, k, in.rows, "gk", &keys));
+            if (kp.null_keys && !kp.null_in_table) FG_TRY(replace_invalid_i64(ctx, keys, k.c.valid, in.rows, kNullKey));
+        }
+        return group_by_key64_n(ctx, node_key(pl, n, "grp").c_str(), keys, in.rows, specs, n_specs, g, kp.null_in_table ? k.c.valid : nullptr);
+    }
+
+    // ---- the key columns of the groups
+    int write_key_columns(const Node *n, const Table &in, const KeyPlan &kp, const GroupResultN &g, Table *t) {
+        const TCol &k = in.cols[(size_t)n->group[0]];
+        switch (kp.shape) {
+            case KeyShape::Composite:   // each group's key values are those of its first row (validity taken along)
+                for (size_t c = 0; c < n->group.size(); ++c) {
+                    const TCol &src = in.cols[(size_t)n->group[c]];
+                    FG_TRY(take_column(ctx, node_key(pl, n, "take", (int)c).c_str(), src.c, g.first_row, g.n_groups, &t->cols[c].c));
+                    t->cols[c].present = true;
+                    t->cols[c].c.is_ts = n->schema[c].is_ts;
+                    t->cols[c].c.nullable = n->schema[c].nullable;
+                }
+                break;
+            case KeyShape::PairI32: {
+                int32_t *ka = nullptr, *kb = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk").c_str(), (size_t)g.n_groups + 4, &ka));
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk2").c_str(), (size_t)g.n_groups + 4, &kb));
+                FG_TRY(unpack_i32_pair(ctx, g.keys, g.n_groups, ka, kb));
+                t->cols[0] = dev_col(ColType::I32, ka);
+                t->cols[1] = dev_col(ColType::I32, kb);
+                t->cols[1].c.nullable = n->schema[1].nullable;
+                break;
+            }
+            case KeyShape::Utf8:
+                FG_TRY(take_column(ctx, node_key(pl, n, "take", 0).c_str(), k.c, g.first_row, g.n_groups, &t->cols[0].c));
+                t->cols[0].present = true;
+                break;
+            case KeyShape::DistinctI32Utf8: break;   // (exec_distinct_pair writes its own)
+            case KeyShape::Int:
+                if (k.c.type == ColType::I32) {
+                    int32_t *nk = nullptr;
+                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk").c_str(), (size_t)g.n_groups + 4, &nk));
+                    FG_TRY(narrow_i64_to_i32(ctx, g.keys, g.n_groups, nk));
+                    t->cols[0] = dev_col(ColType::I32, nk);
+                    if (kp.null_keys) {   // the NULL group's key is NULL again
+                        uint8_t *kv = nullptr;
+                        FG_TRY(arena_get_t(ctx, node_key(pl, n, "nkv").c_str(), (size_t)g.n_groups + 16, &kv));
+                        FG_TRY(valid_from_i64(ctx, g.keys, g.n_groups, kNullKey, kv));
+                        t->cols[0].c.valid = kv;
+                    }
+                } else {
+                    t->cols[0] = dev_col(k.c.type, g.keys, nullptr, 0, k.c.is_ts);
+                    if (kp.null_in_table) t->cols[0].c.valid = g.key_valid;
+                }
+                if (!kp.null_keys) t->cols[0].subset_of = k.subset_of ? k.subset_of : k.c.values;   // (a group's key is one of the input's keys)
+                break;
+        }
+        t->cols[0].c.nullable = n->schema[0].nullable;
+        return FLOCKGPU_OK;
+    }
+
+    // ---- the result columns of the groups, from the accumulators of one of the tables (g.agg) -- or, `wide`, of the one pass over the ids, which
+    // runs here and finishes every column but the distinct counts on the device.  The distinct counts run over the ids in both cases.
+    int write_result_columns(const Node *n, const Table &in, const AggLowering &L, const AggSpec *specs, const GroupResultN &g, const int32_t *gid, bool wide, Table *t) {
+        const int64_t G = g.n_groups;
+        WideGroupResult wres;
+        std::vector<int> wide_col(L.outs.size(), -1);   // per result column: its place among the wide pass's (it takes no distinct count)
+        if (wide) {
+            WideOut wo[kMaxWideAggs];
+            int n_wo = 0;
+            for (size_t o = 0; o < L.outs.size(); ++o)
+                if (L.outs[o].kind != WideOutKind::DistinctCount) wo[wide_col[o] = n_wo++] = L.outs[o];
+            FG_TRY(group_by_ids_wide(ctx, node_key(pl, n, "wide").c_str(), gid, in.rows, G, specs, L.n_accs, wo, n_wo, &wres));
+        }
+        for (size_t o = 0; o < L.outs.size(); ++o) {
+            const WideOut &w = L.outs[o];
+            const size_t oc = n->group.size() + o;
+            const int col = (int)oc;
+            TCol &out = t->cols[oc];
+            if (w.kind == WideOutKind::DistinctCount) {
+                uint64_t *dc = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", col).c_str(), (size_t)G + 2, &dc));
+                if (G > 0) FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", w.acc).c_str(), gid, G, in.cols[(size_t)n->aggs[(size_t)w.acc].arg].c, in.rows, dc));
+                out = dev_col(ColType::U64, dc);
+            } else if (wide) {
+                out = dev_col(n->schema[oc].type, wres.col[wide_col[o]], nullptr, 0, n->schema[oc].is_ts);
+                out.c.valid = wres.valid[wide_col[o]];
+            } else if (w.kind == WideOutKind::Value) {
+                if (w.type == ColType::I32) {
+                    int32_t *v = nullptr;
+                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", col).c_str(), (size_t)G + 4, &v));
+                    FG_TRY(narrow_i64_to_i32(ctx, reinterpret_cast<const int64_t *>(g.agg[w.acc]), G, v));
+                    out = dev_col(ColType::I32, v);
+                } else {
+                    out = dev_col(w.type, g.agg[w.acc], nullptr, 0, n->schema[oc].is_ts);
+                }
+                if (w.validity == 1) out.c.valid = g.agg_valid[w.acc];   // (null where the argument carried no validity)
+            } else if (w.kind == WideOutKind::SumAsF64) {   // the sum state of a Partial's AVG
+                // (back-ends) the 64-bit integer sum becomes a double as signed, here and in the wide finish; the ungrouped fold converts a UInt64 sum as unsigned
+                double *sum = nullptr;
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", col).c_str(), (size_t)G + 2, &sum));
+                FG_TRY(i64_to_f64(ctx, reinterpret_cast<const int64_t *>(g.agg[w.acc]), G, sum));
+                out = dev_col(ColType::F64, sum);
+            } else {   // AVG finished: sum / count, NULL over no valid value
+                const double *sum = reinterpret_cast<const double *>(g.agg[w.acc2]);   // (AvgF64: the Float64 sum of the states)
+                double *avg = nullptr;
+                uint8_t *av = nullptr;
+                if (w.kind == WideOutKind::AvgInt) {   // (signed, as above)
+                    double *s = nullptr;
+                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "avs", col).c_str(), (size_t)G + 2, &s));
+                    FG_TRY(i64_to_f64(ctx, reinterpret_cast<const int64_t *>(g.agg[w.acc2]), G, s));
+                    sum = s;
+                }
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", col).c_str(), (size_t)G + 2, &avg));
+                FG_TRY(arena_get_t(ctx, node_key(pl, n, "avv", col).c_str(), (size_t)G + 16, &av));
+                FG_TRY(avg_finish(ctx, sum, g.agg[w.acc], G, avg));
+                FG_TRY(valid_from_i64(ctx, reinterpret_cast<const int64_t *>(g.agg[w.acc]), G, 0, av));
+                out = dev_col(ColType::F64, avg);
+                out.c.valid = av;
+            }
+            out.c.nullable = true;
         }
         return FLOCKGPU_OK;
     }
@@ -3099,335 +3395,33 @@ struct Exec {
         if (n->group.empty() && !ir::lone_integer_max(n)) return exec_global_aggregate(n, t);
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
-        const bool is_final = n->mode != AggMode::Partial && !n->single_pass;
-        const bool distinct = ir::has_distinct_count(n);
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->schema.size(); ++i) {
             t->cols[i].c.type = n->schema[i].type;
             t->cols[i].c.is_ts = n->schema[i].is_ts;
             t->cols[i].c.nullable = n->schema[i].nullable;
         }
-        // ---- no GROUP BY: MAX of one integer column -> one row (NULL over no input)
-        if (n->group.empty()) {
-            const ColType at = n->aggs.size() == 1 && n->aggs[0].arg >= 0 ? in.cols[(size_t)n->aggs[0].arg].c.type : ColType::UTF8;
-            if (n->aggs.size() != 1 || n->aggs[0].fn != AggFn::Max || at == ColType::UTF8 || at == ColType::F64 || !in.cols[(size_t)n->aggs[0].arg].present)
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: global aggregate other than MAX over an integer column");
-            const TCol &a = in.cols[(size_t)n->aggs[0].arg];
-            int64_t mx = 0;
-            int any = 0;
-            if (!a.c.all_null) FG_TRY(reduce_max(ctx, a.c, in.rows, &mx, &any));
-            int64_t *d = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "max").c_str(), 2, &d));
-            // the one value travels as kernel arguments (a host-to-device copy call costs ~10 us of host time; Int32 reads the low word)
-            FG_TRY(fill_words(ctx, FillList().add(d, (uint32_t)(uint64_t)mx, 1).add(reinterpret_cast<uint32_t *>(d) + 1, (uint32_t)((uint64_t)mx >> 32), 1)));
-            t->rows = 1;
-            t->cols[0] = dev_col(at, d, nullptr, 0, a.c.is_ts);
-            t->cols[0].c.nullable = true;
-            t->cols[0].c.all_null = !any;
-            return FLOCKGPU_OK;
-        }
-        // ---- key shapes the paths below do not take -- three or more columns, two other than (Int32, Int32) / DISTINCT (Int32, Utf8), NULLs in
-        // a two-column key -- group on composite-key ids (relops.hpp key_codes): groups in order of first appearance
-        // ... and so does every node with a distinct count, whatever its key: the ids index the ordinary accumulators and the distinct counts alike
-        // ... and every node with five or more accumulators: one pass over the ids updates all of them (groupwide.hpp)
-        int n_accs = 0;
-        for (auto &a : n->aggs) n_accs += ir::agg_accumulators(a.fn);
-        const bool wide = n_accs > kMaxGroupAggs;
-        bool composite = n->group.size() > 2 || distinct || wide;
-        if (n->group.size() == 2 && !distinct && !wide) {
-            const TCol &a = in.cols[(size_t)n->group[0]], &b = in.cols[(size_t)n->group[1]];
-            composite = a.c.type != ColType::I32 || a.c.valid || b.c.valid || b.c.type != (n->aggs.empty() ? ColType::UTF8 : ColType::I32);
-            if (a.c.type == ColType::F64 || b.c.type == ColType::F64) composite = false;   // (refused below with today's message)
-        }
-        if (composite) {
-            if (n->group.size() > (size_t)kMaxKeyCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than %d columns", kMaxKeyCols);
-            for (int c : n->group)
-                if (in.cols[(size_t)c].c.type == ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a Float64 column");
-        }
-        // ---- DISTINCT (Int32, Utf8)
-        if (n->group.size() == 2 && n->aggs.empty() && !composite) {
-            const TCol &k = in.cols[(size_t)n->group[0]], &s = in.cols[(size_t)n->group[1]];
-            if (k.c.type != ColType::I32 || s.c.type != ColType::UTF8 || !k.present || !s.present)
-                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: two-column GROUP BY other than (Int32, Utf8)");
-            if (k.c.valid || s.c.valid) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: DISTINCT over columns that hold NULLs");
-            int32_t *rows = nullptr;
-            int64_t n_out = 0;
-            FG_TRY(distinct_i32_utf8(ctx, node_key(pl, n, "dist").c_str(), static_cast<const int32_t *>(k.c.values),
-                                     flockgpu_utf8{s.c.offsets, static_cast<const uint8_t *>(s.c.values)}, in.rows, &rows, &n_out));
-            t->rows = n_out;
-            FG_TRY(take_column(ctx, node_key(pl, n, "take", 0).c_str(), k.c, rows, n_out, &t->cols[0].c));
-            FG_TRY(take_column(ctx, node_key(pl, n, "take", 1).c_str(), s.c, rows, n_out, &t->cols[1].c));
-            t->cols[0].present = t->cols[1].present = true;
-            return FLOCKGPU_OK;
-        }
-        // ---- GROUP BY one integer column or two Int32 columns; COUNT / MAX / MIN / SUM / AVG of integer columns.
-        // Partial: accumulators over the rows -> state columns (agg_state_cols); Final: the same accumulators over the states.
-        const bool pair = n->group.size() == 2 && !composite;
-        if (n->group.empty() || (n->group.size() > 2 && !composite)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY more than two columns");
-        const TCol &k = in.cols[(size_t)n->group[0]];
-        int64_t *keys = nullptr;
-        // NULL group keys form ONE group (DataFusion groups NULLs together): an Int32 key column widened to 64 bits has room for a value
-        // no Int32 takes, and so have a Utf8 column's dictionary codes (row numbers); other key types with NULLs are handed back
-        constexpr int64_t kNullKey = int64_t(1) << 40;
-        const bool null_keys = k.c.valid != nullptr && !composite;
-        // ... and a 64-bit key (Int64 / UInt64 / Timestamp) hands its validity to the GROUP BY itself, which keeps the NULLs in a slot of their own
-        const bool wide_null_keys = null_keys && !pair && k.c.type != ColType::I32 && k.c.type != ColType::UTF8 && k.c.type != ColType::F64;
-        if (null_keys && pair) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: NULLs in a two-column GROUP BY key");
-        // the generic table's keys: every key column normalised to one int64 per row (not needed by the dense path below)
-        auto prepare_keys = [&]() -> int {
-            if (pair) {
-                const TCol &k2 = in.cols[(size_t)n->group[1]];
-                if (k.c.type != ColType::I32 || k2.c.type != ColType::I32 || !k.present || !k2.present)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: two-column GROUP BY other than (Int32, Int32) / (Int32, Utf8)");
-                if (k2.c.valid) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: NULLs in a two-column GROUP BY key");
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "gk").c_str(), (size_t)in.rows + 2, &keys));
-                FG_TRY(pack_i32_pair(ctx, static_cast<const int32_t *>(k.c.values), static_cast<const int32_t *>(k2.c.values), in.rows, keys));
-            } else if (k.c.type == ColType::UTF8) {  // group on the strings' dictionary codes; the key column is taken from the first rows
-                if (!k.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "gk").c_str(), (size_t)in.rows + 2, &keys));
-                FG_TRY(utf8_codes(ctx, node_key(pl, n, "codes").c_str(), k.c, in.rows, keys, nullptr, 0, nullptr));
-                // (a NULL's bytes are whatever its slot holds -- usually nothing, which is also the empty string's code: NULLs get their own key;
-                // the group's key comes out NULL through the validity of its first row, take_column below)
-                if (null_keys) FG_TRY(replace_invalid_i64(ctx, keys, k.c.valid, in.rows, kNullKey));
-            } else {
-                if (k.c.type == ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: GROUP BY a Float64 column");
-                FG_TRY(key_i64(n, k, in.rows, "gk", &keys));
-                if (null_keys && !wide_null_keys) FG_TRY(replace_invalid_i64(ctx, keys, k.c.valid, in.rows, kNullKey));
-            }
-            return FLOCKGPU_OK;
-        };
-        AggSpec specs[kMaxWideAggs];   // (the tables of relops.hpp take kMaxGroupAggs of them; more go through group_by_ids_wide)
-        int n_specs = 0;
-        struct Out { int first = 0, count = 1; };  // accumulators of aggregate a
-        std::vector<Out> outs;
-        auto int_col = [&](int c, const char *what) -> const TCol * {
-            if (c < 0 || !in.cols[(size_t)c].present || in.cols[(size_t)c].c.type == ColType::UTF8 || in.cols[(size_t)c].c.type == ColType::F64) {
-                fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s needs an integer column", what);
-                return nullptr;
-            }
-            return &in.cols[(size_t)c];
-        };
-        for (auto &a : n->aggs) {
-            Out o;
-            o.first = n_specs;
-            o.count = ir::agg_accumulators(a.fn);
-            if (n_specs + o.count > kMaxWideAggs) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: more than %d accumulators in one GROUP BY", kMaxWideAggs);
-            // (every accumulator carries its argument's validity: NULLs are skipped, a group without a valid value comes out NULL)
-            if (a.fn == AggFn::CountDistinct) {   // no accumulator: a table of its own over the group ids, below
-                const TCol *v = a.arg >= 0 && (size_t)a.arg < in.cols.size() ? &in.cols[(size_t)a.arg] : nullptr;
-                if (!v || v->c.type == ColType::F64 || (!v->present && !v->c.all_null))
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: distinct_count needs an integer or Utf8 column");
-            } else if (a.fn == AggFn::Count) {
-                if (is_final) {
-                    const TCol *st = int_col(a.arg, "the COUNT state");
-                    if (!st) return FLOCKGPU_ERR_UNSUPPORTED;
-                    specs[n_specs++] = AggSpec{AggOp::SUM_INT, st->c.values, st->c.type, nullptr};
-                } else {   // COUNT(*) / COUNT(UInt8(1)) counts rows, COUNT(col) the rows whose col is not NULL
-                    specs[n_specs++] = AggSpec{AggOp::COUNT, nullptr, ColType::I64, a.arg >= 0 ? in.cols[(size_t)a.arg].c.valid : nullptr};
-                }
-            } else if (a.fn != AggFn::Avg) {   // SUM of an integer column; MIN / MAX of an integer or a Float64 one
-                const bool f64 = agg_is_minmax(a.fn) && a.arg >= 0 && in.cols[(size_t)a.arg].present && in.cols[(size_t)a.arg].c.type == ColType::F64;
-                const TCol *v = f64 ? &in.cols[(size_t)a.arg] : int_col(a.arg, agg_fn_name(a.fn));
-                if (!v) return FLOCKGPU_ERR_UNSUPPORTED;
-                specs[n_specs++] = AggSpec{agg_op_for(a.fn, v->c.type), v->c.values, v->c.type, v->c.valid};
-            } else {  // avg: (count, sum)
-                if (is_final) {
-                    const TCol *cnt = int_col(a.arg, "the AVG count state");
-                    if (!cnt) return FLOCKGPU_ERR_UNSUPPORTED;
-                    const TCol &sm = in.cols[(size_t)a.arg2];
-                    if (!sm.present || sm.c.type != ColType::F64) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: the AVG sum state must be Float64");
-                    specs[n_specs++] = AggSpec{AggOp::SUM_INT, cnt->c.values, cnt->c.type, nullptr};
-                    specs[n_specs++] = AggSpec{AggOp::SUM_F64, sm.c.values, ColType::F64, nullptr};
-                } else {
-                    const TCol *v = int_col(a.arg, "AVG");
-                    if (!v) return FLOCKGPU_ERR_UNSUPPORTED;
-                    specs[n_specs++] = AggSpec{AggOp::COUNT, nullptr, ColType::I64, v->c.valid};
-                    specs[n_specs++] = AggSpec{AggOp::SUM_INT, v->c.values, v->c.type, v->c.valid};
-                }
-            }
-            outs.push_back(o);
+        if (n->group.empty()) return exec_lone_max(n, in, t);
+        // five or more accumulators go through one pass over group ids (groupwide.hpp), and a distinct count runs over ids too
+        const bool wide = ir::node_accumulators(n) > kMaxGroupAggs;
+        KeyPlan kp;
+        FG_TRY(choose_key_shape(n, in, wide || ir::has_distinct_count(n), &kp));
+        if (kp.shape == KeyShape::DistinctI32Utf8) return exec_distinct_pair(n, in, t);
+        // Partial: accumulators over the rows -> state columns (agg_state_cols); Final: the same accumulators over the states
+        AggLowering L;
+        FG_TRY(lower_aggregates(n, in, true, &L));
+        AggSpec specs[kMaxWideAggs];   // a COUNT reads validity alone
+        for (int a = 0; a < L.n_accs; ++a) {
+            const AggAcc &A = L.accs[a];
+            const DevColumn *d = A.col >= 0 ? &in.cols[(size_t)A.col].c : nullptr;
+            specs[a] = A.op == AggOp::COUNT ? AggSpec{A.op, nullptr, ColType::I64, d ? d->valid : nullptr} : AggSpec{A.op, d->values, d->type, A.with_valid ? d->valid : nullptr};
         }
         GroupResultN g;
         const int32_t *gid = nullptr;
-        if (composite) FG_TRY(group_composite(n, in, specs, wide ? 0 : n_specs, &g, &gid));   // (wide: the ids and first rows only)
-        // A dense integer key without NULLs under integer accumulators without NULLs: the perfect-hash GROUP BY (relops.hpp "dense integer
-        // keys") -- slot = key - min over the column's exact range, no hashing, no int64 copy of the key column.  Everything else (Utf8 /
-        // two-column keys, NULLs, Float64 accumulators, keys spread wider than their row count) takes the hash table.
-        const bool fit = specs_fit_dense(specs, n_specs);
-        bool dense = fit && !composite && !pair && !null_keys && k.present && in.rows > 0 && (k.c.type == ColType::I32 || k.c.type == ColType::I64 || k.c.type == ColType::U64);
-        int64_t kmin = 0, kmax = 0;
-        if (dense && !stats_worth_it(k, in.rows)) dense = false;
-        if (dense) {
-            FG_TRY(int_col_stats(k, in.rows, &kmin, &kmax));
-            dense = dense_range_ok(kmin, kmax, in.rows, k.c.type == ColType::U64);
-        }
-        // A Utf8 key's dictionary codes are row numbers of its own relation: dense by construction.  The code of a group IS a row that
-        // carries the group's string, so it also stands in for the first row the key column is taken from.
-        const bool dense_codes = fit && !composite && !pair && !null_keys && k.present && k.c.type == ColType::UTF8 && in.rows > 0 && in.rows < (int64_t(1) << 31);
-        if (dense_codes) {
-            FG_TRY(prepare_keys());   // (utf8_codes)
-            FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), plain_col(ColType::I64, keys), in.rows, 0, in.rows - 1, specs, n_specs, &g));
-            int32_t *rep = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "rep").c_str(), (size_t)g.n_groups + 4, &rep));
-            FG_TRY(narrow_i64_to_i32(ctx, g.keys, g.n_groups, rep));
-            g.first_row = rep;
-        } else if (dense) {
-            FG_TRY(group_by_dense(ctx, node_key(pl, n, "grp").c_str(), k.c, in.rows, kmin, kmax, specs, n_specs, &g));
-        } else if (!composite) {
-            FG_TRY(prepare_keys());
-            FG_TRY(group_by_key64_n(ctx, node_key(pl, n, "grp").c_str(), keys, in.rows, specs, n_specs, &g, wide_null_keys ? k.c.valid : nullptr));
-        }
+        FG_TRY(number_groups(n, in, kp, specs, wide ? 0 : L.n_accs, &g, &gid));   // (wide: the ids and first rows only)
         t->rows = g.n_groups;
-        // ---- key columns
-        if (composite) {   // each group's key values are those of its first row (validity taken along)
-            for (size_t c = 0; c < n->group.size(); ++c) {
-                const TCol &src = in.cols[(size_t)n->group[c]];
-                FG_TRY(take_column(ctx, node_key(pl, n, "take", (int)c).c_str(), src.c, g.first_row, g.n_groups, &t->cols[c].c));
-                t->cols[c].present = true;
-                t->cols[c].c.is_ts = n->schema[c].is_ts;
-                t->cols[c].c.nullable = n->schema[c].nullable;
-            }
-        } else if (pair) {
-            int32_t *ka = nullptr, *kb = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk").c_str(), (size_t)g.n_groups + 4, &ka));
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk2").c_str(), (size_t)g.n_groups + 4, &kb));
-            FG_TRY(unpack_i32_pair(ctx, g.keys, g.n_groups, ka, kb));
-            t->cols[0] = dev_col(ColType::I32, ka);
-            t->cols[1] = dev_col(ColType::I32, kb);
-            t->cols[1].c.nullable = n->schema[1].nullable;
-        } else if (k.c.type == ColType::UTF8) {
-            FG_TRY(take_column(ctx, node_key(pl, n, "take", 0).c_str(), k.c, g.first_row, g.n_groups, &t->cols[0].c));
-            t->cols[0].present = true;
-        } else if (k.c.type == ColType::I32) {
-            int32_t *nk = nullptr;
-            FG_TRY(arena_get_t(ctx, node_key(pl, n, "nk").c_str(), (size_t)g.n_groups + 4, &nk));
-            FG_TRY(narrow_i64_to_i32(ctx, g.keys, g.n_groups, nk));
-            t->cols[0] = dev_col(ColType::I32, nk);
-            if (!null_keys) t->cols[0].subset_of = k.subset_of ? k.subset_of : k.c.values;   // (a group's key is one of the input's keys)
-            if (null_keys) {   // the NULL group's key is NULL again
-                uint8_t *kv = nullptr;
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "nkv").c_str(), (size_t)g.n_groups + 16, &kv));
-                FG_TRY(valid_from_i64(ctx, g.keys, g.n_groups, kNullKey, kv));
-                t->cols[0].c.valid = kv;
-            }
-        } else {
-            t->cols[0] = dev_col(k.c.type, g.keys, nullptr, 0, k.c.is_ts);
-            if (wide_null_keys) t->cols[0].c.valid = g.key_valid;
-            else if (!null_keys) t->cols[0].subset_of = k.subset_of ? k.subset_of : k.c.values;
-        }
-        t->cols[0].c.nullable = n->schema[0].nullable;
-        // ---- aggregate / state columns
-        size_t oc = n->group.size();
-        // five or more accumulators: one pass over the ids, and a finish that writes every result column -- AVG's division, the Float64 sum state of a
-        // Partial's AVG, Int32 results, validity bytes -- on the device
-        WideGroupResult wres;
-        std::vector<int> wide_out(n->aggs.size(), -1);   // per aggregate: its first result column in wres
-        if (wide) {
-            WideAggSpec ws[kMaxWideAggs];
-            for (int a = 0; a < n_specs; ++a) ws[a] = WideAggSpec{specs[a].op, specs[a].values, specs[a].type, specs[a].valid};
-            WideOut wo[kMaxWideAggs];
-            int n_wo = 0;
-            size_t c = oc;
-            for (size_t ai = 0; ai < n->aggs.size(); ++ai) {
-                const Agg &a = n->aggs[ai];
-                const Out &o = outs[ai];
-                wide_out[ai] = n_wo;
-                if (a.fn == AggFn::CountDistinct) {
-                    c += 1;
-                } else if (a.fn == AggFn::Avg && (n->single_pass || is_final)) {   // AVG over no valid value is NULL
-                    wo[n_wo++] = WideOut{n->single_pass ? WideOutKind::AvgInt : WideOutKind::AvgF64, o.first, o.first + 1, ColType::F64, 2};
-                    c += 1;
-                } else if (a.fn == AggFn::Avg) {   // its state: [count UInt64, sum Float64]
-                    wo[n_wo++] = WideOut{WideOutKind::Value, o.first, -1, ColType::U64, 0};
-                    wo[n_wo++] = WideOut{WideOutKind::SumAsF64, o.first + 1, -1, ColType::F64, 0};
-                    c += 2;
-                } else {
-                    const ColType want = n->schema[c].type;
-                    const bool f64_acc = specs[o.first].op == AggOp::MAX_F64 || specs[o.first].op == AggOp::MIN_F64;
-                    if (want == ColType::UTF8 || (want == ColType::F64) != f64_acc)
-                        return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
-                    wo[n_wo++] = WideOut{WideOutKind::Value, o.first, -1, want, a.fn != AggFn::Count ? 1 : 0};   // MIN / MAX / SUM over nothing but NULLs is NULL; COUNT(col) is 0
-                    c += 1;
-                }
-            }
-            FG_TRY(group_by_ids_wide(ctx, node_key(pl, n, "wide").c_str(), gid, in.rows, g.n_groups, ws, n_specs, wo, n_wo, &wres));
-        }
-        for (size_t ai = 0; ai < n->aggs.size(); ++ai) {
-            const Agg &a = n->aggs[ai];
-            const Out &o = outs[ai];
-            if (wide && a.fn != AggFn::CountDistinct) {
-                const int cols = a.fn == AggFn::Avg && !n->single_pass && !is_final ? 2 : 1;
-                for (int k = 0; k < cols; ++k, ++oc) {
-                    t->cols[oc] = dev_col(n->schema[oc].type, wres.col[wide_out[ai] + k], nullptr, 0, n->schema[oc].is_ts);
-                    t->cols[oc].c.nullable = true;
-                    t->cols[oc].c.valid = wres.valid[wide_out[ai] + k];
-                }
-                continue;
-            }
-            auto narrow_if_i32 = [&](uint64_t *acc, ColType want, bool ts, size_t col) -> int {
-                if (want == ColType::I32) {
-                    int32_t *v = nullptr;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)col).c_str(), (size_t)g.n_groups + 4, &v));
-                    FG_TRY(narrow_i64_to_i32(ctx, reinterpret_cast<const int64_t *>(acc), g.n_groups, v));
-                    t->cols[col] = dev_col(ColType::I32, v);
-                } else {
-                    t->cols[col] = dev_col(want, acc, nullptr, 0, ts);
-                }
-                t->cols[col].c.nullable = true;
-                return FLOCKGPU_OK;
-            };
-            if (a.fn == AggFn::CountDistinct) {
-                uint64_t *dc = nullptr;
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc).c_str(), (size_t)g.n_groups + 2, &dc));
-                if (g.n_groups > 0) FG_TRY(distinct_count_by_group(ctx, node_key(pl, n, "dc", (int)ai).c_str(), gid, g.n_groups, in.cols[(size_t)a.arg].c, in.rows, dc));
-                t->cols[oc] = dev_col(ColType::U64, dc);
-                t->cols[oc].c.nullable = true;
-                oc += 1;
-            } else if (a.fn == AggFn::Avg && n->single_pass) {   // what Final makes of a group's one state row: (double) integer sum / (double) count
-                double *sum = nullptr, *avg = nullptr;
-                uint8_t *av = nullptr;
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "avs", (int)oc).c_str(), (size_t)g.n_groups + 2, &sum));
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc).c_str(), (size_t)g.n_groups + 2, &avg));
-                FG_TRY(arena_get_t(ctx, node_key(pl, n, "avv", (int)oc).c_str(), (size_t)g.n_groups + 16, &av));
-                FG_TRY(i64_to_f64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first + 1]), g.n_groups, sum));
-                FG_TRY(avg_finish(ctx, sum, g.agg[o.first], g.n_groups, avg));
-                FG_TRY(valid_from_i64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first]), g.n_groups, 0, av));   // AVG over no valid value is NULL
-                t->cols[oc] = dev_col(ColType::F64, avg);
-                t->cols[oc].c.nullable = true;
-                t->cols[oc].c.valid = av;
-                oc += 1;
-            } else if (a.fn == AggFn::Avg) {
-                if (is_final) {
-                    double *avg = nullptr;
-                    uint8_t *av = nullptr;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc).c_str(), (size_t)g.n_groups + 2, &avg));
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "avv", (int)oc).c_str(), (size_t)g.n_groups + 16, &av));
-                    FG_TRY(avg_finish(ctx, reinterpret_cast<const double *>(g.agg[o.first + 1]), g.agg[o.first], g.n_groups, avg));
-                    FG_TRY(valid_from_i64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first]), g.n_groups, 0, av));   // AVG over no valid value is NULL
-                    t->cols[oc] = dev_col(ColType::F64, avg);
-                    t->cols[oc].c.nullable = true;
-                    t->cols[oc].c.valid = av;
-                    oc += 1;
-                } else {
-                    double *sum = nullptr;
-                    FG_TRY(arena_get_t(ctx, node_key(pl, n, "av", (int)oc + 1).c_str(), (size_t)g.n_groups + 2, &sum));
-                    FG_TRY(i64_to_f64(ctx, reinterpret_cast<const int64_t *>(g.agg[o.first + 1]), g.n_groups, sum));
-                    t->cols[oc] = dev_col(ColType::U64, g.agg[o.first]);
-                    t->cols[oc + 1] = dev_col(ColType::F64, sum);
-                    t->cols[oc].c.nullable = t->cols[oc + 1].c.nullable = true;
-                    oc += 2;
-                }
-            } else {
-                const ColType want = n->schema[oc].type;
-                const bool f64_acc = specs[o.first].op == AggOp::MAX_F64 || specs[o.first].op == AggOp::MIN_F64;
-                if (want == ColType::UTF8 || (want == ColType::F64) != f64_acc)
-                    return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: %s of a column into a column of another kind", agg_fn_name(a.fn));
-                FG_TRY(narrow_if_i32(g.agg[o.first], want, n->schema[oc].is_ts, oc));
-                if (a.fn != AggFn::Count) t->cols[oc].c.valid = g.agg_valid[o.first];   // MIN / MAX / SUM over nothing but NULLs is NULL; COUNT(col) is 0
-                oc += 1;
-            }
-        }
-        return FLOCKGPU_OK;
+        FG_TRY(write_key_columns(n, in, kp, g, t));
+        return write_result_columns(n, in, L, specs, g, gid, wide, t);
     }
 };
 

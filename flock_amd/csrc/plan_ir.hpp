@@ -159,6 +159,13 @@ inline bool parse_agg_mode(const std::string &name, AggMode *out) {
 }
 inline bool is_distinct_count_tag(const std::string &name) { return name == "distinct_count" || name == "count_distinct"; }
 inline bool agg_is_minmax(AggFn f) { return f == AggFn::Min || f == AggFn::Max; }
+// The argument types an aggregate takes -- in GROUP BY, without one and as a window function: COUNT any column, MIN / MAX integers and Float64,
+// SUM / AVG integers, a distinct count integers and Utf8.  Every check of an argument's type, at create and at execute, asks here.
+inline bool agg_takes(AggFn f, ColType t) {
+    if (t == ColType::UTF8) return f == AggFn::Count || f == AggFn::CountDistinct;
+    if (t == ColType::F64) return f == AggFn::Count || agg_is_minmax(f);
+    return true;
+}
 // The 64-bit accumulator of COUNT / SUM / MIN / MAX over a column of type `t` (GROUP BY's and the window aggregates'; AVG: its sum -- the count
 // beside it is the caller's)
 inline AggOp agg_op_for(AggFn f, ColType t) {
@@ -246,7 +253,7 @@ inline bool has_distinct_count(const Node *n) {
         if (a.fn == AggFn::CountDistinct) return true;
     return false;
 }
-inline int ungrouped_accumulators(const Node *n) {
+inline int node_accumulators(const Node *n) {
     int accs = 0;
     for (auto &a : n->aggs) accs += agg_accumulators(a.fn);
     return accs;
@@ -949,7 +956,7 @@ struct Builder {
                             return nullptr;
                         }
                     }
-                    if (dc && in->schema[(size_t)a.arg].type == ColType::F64) { fail("distinct_count needs an integer or Utf8 column"); return nullptr; }
+                    if (dc && !agg_takes(a.fn, in->schema[(size_t)a.arg].type)) { fail("distinct_count needs an integer or Utf8 column"); return nullptr; }
                     if (a.fn == AggFn::Count || dc) a.type = ColType::U64;
                     if (a.fn == AggFn::Avg) a.type = ColType::F64;
                     Field f;
@@ -973,14 +980,15 @@ struct Builder {
                     }
                     n->aggs.push_back(a);
                 }
-            // no GROUP BY (reduce.hpp): the argument types of the GROUP BY path, refused in its words; up to eight accumulators (AVG takes two)
+            // no GROUP BY (reduce.hpp): the argument types of agg_takes, less COUNT of a Utf8 column (the pass streams fixed-width columns); up to eight
+            // accumulators (AVG takes two)
             if (n->group.empty()) {
                 int accs = 0;
                 for (auto &a : n->aggs) {
                     accs += agg_accumulators(a.fn);
                     if (a.arg < 0 || a.fn == AggFn::CountDistinct) continue;
                     const ColType at = in->schema[(size_t)a.arg].type;
-                    if (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(a.fn) && a.fn != AggFn::Count)) { fail(std::string(agg_fn_name(a.fn)) + " needs an integer column"); return nullptr; }
+                    if (!agg_takes(a.fn, at) || at == ColType::UTF8) { fail(std::string(agg_fn_name(a.fn)) + " needs an integer column"); return nullptr; }
                 }
                 if (accs > kMaxUngroupedAccumulators) { fail("more than " + std::to_string(kMaxUngroupedAccumulators) + " accumulators in one ungrouped aggregate"); return nullptr; }
             } else {   // GROUP BY: up to four in the tables of relops.hpp, five to sixteen in the one pass over group ids of groupwide.hpp
@@ -1158,9 +1166,8 @@ struct Builder {
                         fail("window aggregate '" + fn + "' over a literal");
                         return nullptr;
                     }
-                    // the argument types of the GROUP BY path (plan.hip exec_aggregate), refused in its words
                     const ColType at = x.arg >= 0 ? in->schema[(size_t)x.arg].type : ColType::U64;
-                    if (x.fn != AggFn::Count && (at == ColType::UTF8 || (at == ColType::F64 && !agg_is_minmax(x.fn)))) {
+                    if (!agg_takes(x.fn, at)) {
                         fail(fn + " needs an integer column");
                         return nullptr;
                     }
