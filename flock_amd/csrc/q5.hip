@@ -48,6 +48,16 @@ constexpr int kHotMin = 16;                     // a candidate seen in fewer lan
 constexpr int kMaxWinPanes = 8;                 // windows of more panes use the hash tables only
 constexpr uint32_t kWideTile = 0x40000000u;     // slow-list tag: declined for its key spread (not for being ragged)
 
+using u16x2 = unsigned short __attribute__((ext_vector_type(2)));   // a counter word as the two 16-bit counts it holds
+__device__ __forceinline__ u16x2 as_u16x2(uint32_t w) { return __builtin_bit_cast(u16x2, w); }
+// {c.x != 0, c.y != 0} as ONE v_pk_min_u16 with {1, 1}: __builtin_elementwise_min(c, {1, 1}) is rewritten into two compares, two selects and a
+// v_perm per word before instruction selection sees it
+__device__ __forceinline__ u16x2 nonzero_u16x2(u16x2 c) {
+    uint32_t r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(__builtin_bit_cast(uint32_t, c)), "s"(0x00010001u));
+    return as_u16x2(r);
+}
+
 struct PaneDesc {
     int64_t base;      // first key of the pane's direct-address range (multiple of 8)
     uint64_t cnt_off;  // offset of the pane's counters in the counter arena (in counters, multiple of 8)
@@ -312,9 +322,13 @@ __device__ __forceinline__ void q5_layout_block(const int32_t *__restrict__ rng,
 __global__ __launch_bounds__(kBlock) void q5_clear_kernel(uint32_t *__restrict__ counters, uint64_t cnt_host,
                                                           uint64_t cnt_from, uint64_t *__restrict__ tables, uint64_t table_words,
                                                           uint64_t *__restrict__ meta, uint64_t meta_words, int32_t *__restrict__ slow_list,
-                                                          uint32_t *__restrict__ block_max, uint64_t block_max_words, int c16, LayoutArgs lay) {
+                                                          uint32_t *__restrict__ block_max, uint64_t block_max_words, int c16, LayoutArgs lay,
+                                                          const uint64_t *__restrict__ cnt_info) {
     if (lay.rng && blockIdx.x == 0) q5_layout_block(lay.rng, lay.pane_win_ptr, lay.seg_off, lay.n_panes, lay.n_win, lay.capacity, lay.budget_bytes, lay.panes, lay.wins, lay.info);
     uint64_t cnt = cnt_host;                // counters to zero (a speculating call: all the arena holds -- the layout is being made next door) ...
+    // the clean-up queued behind q5_finish_kernel, before the host knows the layout: the counters in use as the device layout left them
+    // (never more than the arena holds; a declined layout counted nothing)
+    if (cnt_info) cnt = cnt_info[2] ? (cnt_info[0] < cnt_host ? cnt_info[0] : cnt_host) : 0;
     if (c16) cnt = (cnt + 1) / 2;           // ... and the 32-bit words that hold them (cnt_from is in words, too)
     const uint64_t i0 = (uint64_t)blockIdx.x * kBlock + threadIdx.x, stride = (uint64_t)gridDim.x * kBlock;
     const uint4 z = make_uint4(0, 0, 0, 0);
@@ -956,6 +970,67 @@ __global__ __launch_bounds__(kBlock) void q5_hop2_scan_kernel(const PaneDesc *__
     };
     const uint32_t ng = pd.range / G;   // (ranges are multiples of 8)
     const uint32_t *mine = counters + (k16 ? pd.cnt_off / 2 : pd.cnt_off), *theirs = counters + (k16 ? next.cnt_off / 2 : next.cnt_off);
+    // The max pass over 16-bit counters, no straggler-table entries in either window (block-uniform; the usual case): a word stays the two
+    // counts it is.  Window count = packed saturating add, maximum = packed max, groups and the pane's counter sum = dot products with
+    // {1, 1} into 32-bit accumulators (v_pk_add_u16 clamp, v_pk_max_u16, v_pk_min_u16, v_dot2_u32_u16): ~6 VALU instructions per word of
+    // two counts where the unpacked form below spends ~14.  The next pane's group is loaded together with the lane's own, from a clamped
+    // address, and zeroed where that pane does not cover it.  A window count can pass 65535 while both pane counts fit: the add then
+    // stops at 65535, the packed maximum shows it, and the lane walks its groups again with 32-bit sums (below the loop; NEXMark never does).
+    bool packed_done = false;
+    if constexpr (k16 && !SELECT) {
+        if (!tab_a && !tab_b) {   // (block-uniform)
+            packed_done = true;
+            const u16x2 one = {1, 1};
+            u16x2 pk_a = {0, 0}, pk_b = {0, 0};
+            uint32_t sum32 = 0;   // (a lane's share of one pane's rows: below 2^32 as the window's rows are)
+            const uint32_t i_first = blockIdx.x * kBlock + threadIdx.x, i_step = gridDim.x * kBlock;
+            for (uint32_t i = i_first; i < ng; i += i_step) {
+                const int64_t k0 = pd.base + (int64_t)i * G;
+                const uint64_t idx = (uint64_t)(k0 - next.base);
+                const bool cov = act_b && idx < (uint64_t)next.range;
+                const uint4 m4 = *reinterpret_cast<const uint4 *>(mine + (uint64_t)i * 4);
+                uint4 o4 = *reinterpret_cast<const uint4 *>(theirs + (cov ? idx / 2 : uint64_t(0)));   // (uncovered: the next pane's first group -- the arena's, if there is no next pane -- read and dropped)
+                o4.x = cov ? o4.x : 0u;
+                o4.y = cov ? o4.y : 0u;
+                o4.z = cov ? o4.z : 0u;
+                o4.w = cov ? o4.w : 0u;
+                const uint32_t mw[4] = {m4.x, m4.y, m4.z, m4.w}, ow[4] = {o4.x, o4.y, o4.z, o4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum32 = __builtin_amdgcn_udot2(as_u16x2(mw[j]), one, sum32, false);
+                if (act_b) {   // (block-uniform)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const u16x2 c = __builtin_elementwise_add_sat(as_u16x2(mw[j]), as_u16x2(ow[j]));
+                        pk_b = __builtin_elementwise_max(pk_b, c);
+                        groups_b = __builtin_amdgcn_udot2(nonzero_u16x2(c), one, groups_b, false);
+                    }
+                }
+                if (act_a && !((uint64_t)(k0 - prev.base) < (uint64_t)prev.range)) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const u16x2 c = as_u16x2(mw[j]);
+                        pk_a = __builtin_elementwise_max(pk_a, c);
+                        groups_a = __builtin_amdgcn_udot2(nonzero_u16x2(c), one, groups_a, false);
+                    }
+                }
+            }
+            sum = sum32;
+            best_a = max((uint32_t)pk_a.x, (uint32_t)pk_a.y);
+            best_b = max((uint32_t)pk_b.x, (uint32_t)pk_b.y);
+            if (best_b == 0xFFFFu) {   // a sum of this lane reached 65535 or stopped there: its groups again, in 32 bits (role b's maximum only: the group count stands)
+                for (uint32_t i = i_first; i < ng; i += i_step) {
+                    const uint64_t idx = (uint64_t)(pd.base + (int64_t)i * G - next.base);
+                    if (!(idx < (uint64_t)next.range)) continue;
+                    uint32_t me[G], o[G];
+                    unpack(*reinterpret_cast<const uint4 *>(mine + (uint64_t)i * 4), me);
+                    unpack(*reinterpret_cast<const uint4 *>(theirs + idx / 2), o);
+#pragma unroll
+                    for (int j = 0; j < G; ++j) best_b = max(best_b, me[j] + o[j]);
+                }
+            }
+        }
+    }
+    if (!packed_done)   // (the unpacked walk: 32-bit counters, the select pass, windows with straggler-table entries)
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < ng; i += gridDim.x * kBlock) {
         const int64_t k0 = pd.base + (int64_t)i * G;
         uint32_t me[G];
@@ -1603,6 +1678,8 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
     auto words_of = [&](uint64_t n_counters) -> uint64_t { return c16 ? (n_counters + 1) / 2 : n_counters; };
     if (speculate) {
         // window pane ranges for the device pass (bases / ranges are filled in there); counters for the previous call's size + 1/8
+        // (+ 8 words: the clear kernel's last 16-byte store, and the max pass's packed walk, which reads the 16 bytes at the NEXT pane's cnt_off
+        // -- a multiple of 8 counters, at most the counters in use -- for every group that pane does not cover, and drops them)
         FG_TRY(arena_get_t(ctx, "q5.counters", (size_t)words_of((uint64_t)hint[0] + (uint64_t)hint[0] / 8) + 8, &counters));
         capacity = (ctx->arena["q5.counters"].cap / sizeof(uint32_t) - 8) * (c16 ? 2 : 1);
         if (preclean[0] == (int64_t)reinterpret_cast<uintptr_t>(counters)) clean_upto = (uint64_t)preclean[1];
@@ -1685,7 +1762,7 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
                 LaunchScope ls(ctx, "q5_clear_kernel");
                 hipLaunchKernelGGL(q5_clear_kernel, dim3(cg), dim3(kBlock), 0, ctx->stream, counters, speculate ? capacity : cnt_total,
                                    (attempt == 0 && speculate) ? (clean_upto & ~uint64_t(3)) : uint64_t(0), tables, (uint64_t)cap * n_win, d_meta, (uint64_t)n_meta_all,
-                                   slow_list, block_max, n_block_max, c16 ? 1 : 0, speculate ? lay : LayoutArgs{});
+                                   slow_list, block_max, n_block_max, c16 ? 1 : 0, speculate ? lay : LayoutArgs{}, (const uint64_t *)nullptr);
                 if (speculate) clean_upto = std::max(clean_upto, words_of(capacity));   // (the arena is zero up to there now; only [0, counters in use) gets dirty)
             }
             FG_TRY(check_launch(ctx, "q5_clear_kernel"));
@@ -1837,13 +1914,35 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
         FG_TRY(pinned_get_t(ctx, "q5.finish", n_meta + 8 + (size_t)n_win + 2, &h_fin));
         FG_TRY(arena_get_t(ctx, "q5.out_auction", (size_t)kFinishMax + 1, &fin_a));
         FG_TRY(arena_get_t(ctx, "q5.out_num", (size_t)kFinishMax + 1, &fin_n));
+        // The host learns the results by polling the pinned block (common.hpp: wait_pinned), ~6 us sooner than from a finished stream: the one
+        // workgroup of q5_finish_kernel writes every word of [0, n_meta + 5) exactly once, and the n_win + 1 offsets behind them when it ordered
+        // the winners; none of them can hold the pending pattern (counts below 2^32, flags, {cursor, err} with err 0 / 1, offsets).  What the
+        // host reads besides that block -- the weight totals, the wide mode's sample -- arrives by copy nodes: those calls wait for the stream.
+        const bool poll = !d_wsum && !wide;
+        if (poll) pinned_pending(h_fin, (int)(n_meta + 5 + (size_t)n_win + 1));
         {
             LaunchScope ls(ctx, "q5_finish_kernel");
             hipLaunchKernelGGL(q5_finish_kernel, dim3(1), dim3(kFinishThreads), 0, ctx->stream, d_meta, (uint32_t)n_meta, n_win, spec_info, slow_list, o_win, o_key, out_cap,
                                fin_a, fin_n, h_fin, c16 && pane_walk ? d_pane_sum : (const unsigned long long *)nullptr, d_tab_rows, st.seg_off, d_ptr, n_panes);
         }
         FG_TRY(check_launch(ctx, "q5_finish_kernel"));
-        FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        // Clean-up after use, queued BEHIND the finish kernel and BEFORE the wait: the counters are dead once select has run, so their zeroing
+        // starts the moment the results are out instead of a host wake-up and a launch later.  The host does not know the layout yet: the kernel
+        // takes the counters in use from the device's record (d_info), bounded by the arena.  An attempt that is repeated cleaned up for
+        // nothing -- its repeat clears everything itself, `preclean` is written only by the attempt that returns (below).  The host does not
+        // wait for the clean-up: a fault in it is reported by the next call on this ctx, not by this one.
+        if (speculate && dense) {
+            LaunchScope ls(ctx, "q5_clear_kernel");
+            const unsigned cg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(div_up((int64_t)words_of(cnt_total) / 4 + 1, kBlock), (int64_t)ctx->num_cus * 16));
+            hipLaunchKernelGGL(q5_clear_kernel, dim3(cg), dim3(kBlock), 0, ctx->stream, counters, capacity, uint64_t(0), (uint64_t *)nullptr,
+                               uint64_t(0), (uint64_t *)nullptr, uint64_t(0), slow_list, (uint32_t *)nullptr, uint64_t(0), c16 ? 1 : 0, LayoutArgs{}, d_info);
+        }
+        FG_TRY(check_launch(ctx, "q5_clear_kernel"));
+        if (poll) {
+            FG_TRY(wait_pinned(ctx, h_fin, (int)(n_meta + 5)));
+            if (h_fin[n_meta + 4]) FG_TRY(wait_pinned(ctx, h_fin + n_meta + 5, n_win + 1));
+        } else
+            FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
         std::copy(h_fin, h_fin + n_meta, h_meta);
         if (speculate) std::copy(h_fin + n_meta, h_fin + n_meta + 3, h_info);
         h_slow_count = (uint32_t)h_fin[n_meta + 3];
@@ -1975,7 +2074,7 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
         out->win_max = wmax.data();
         out->win_groups = wgrp.data();
         out->rows = n_sel;
-        return FLOCKGPU_OK;   // (the rare many-ties path leaves the clean-up to the next call)
+        return FLOCKGPU_OK;   // (the rare many-ties path leaves `preclean` void: the next call clears everything itself)
     }
     if (!fin_sorted) {
     // more winners than the finish kernel orders, fewer than the device sorts pay for: ordered by (window, auction) on the host
@@ -2010,16 +2109,7 @@ static int q5_run(flockgpu_ctx *ctx, const int32_t *auction, const uint32_t *wei
     out->win_groups = wgrp.data();
     out->rows = n_sel;
     }
-    if (speculate && dense && cnt_total > 0) {   // clean up after use (see `preclean` above); the results above are already on their way
-        int32_t *slow_list = nullptr;
-        FG_TRY(arena_get_t(ctx, "q5.slow_list", (size_t)st.n_tiles + 2, &slow_list));
-        {
-            LaunchScope ls(ctx, "q5_clear_kernel");
-            const unsigned cg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(div_up((int64_t)words_of(cnt_total) / 4 + 1, kBlock), (int64_t)ctx->num_cus * 16));
-            hipLaunchKernelGGL(q5_clear_kernel, dim3(cg), dim3(kBlock), 0, ctx->stream, counters, cnt_total, uint64_t(0), (uint64_t *)nullptr,
-                               uint64_t(0), (uint64_t *)nullptr, uint64_t(0), slow_list, (uint32_t *)nullptr, uint64_t(0), c16 ? 1 : 0, LayoutArgs{});
-        }
-        FG_TRY(check_launch(ctx, "q5_clear_kernel"));
+    if (speculate && dense && cnt_total > 0) {   // the returning attempt's clean-up is on the stream (queued behind its finish kernel): see `preclean` above
         preclean[0] = (int64_t)reinterpret_cast<uintptr_t>(counters);
         preclean[1] = (int64_t)std::max<uint64_t>(clean_upto, words_of(cnt_total));
     }
