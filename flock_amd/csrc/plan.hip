@@ -21,6 +21,7 @@
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
 #include "cross.hpp"
+#include "union.hpp"
 #include "pred.hpp"
 #include "distinct.hpp"
 #include "groupwide.hpp"
@@ -773,7 +774,7 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
 // keys_only: `n` lies under the right input of a Semi / Anti join, which reads that side for its key columns alone -- a scan there says which of its
 // columns the plan uploads
 void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstream &os, bool keys_only = false) {
-    static const char *kinds[] = {"Scan", "Filter", "Project", "Aggregate", "Join", "Repartition", "Sort", "Limit", "Window"};
+    static const char *kinds[] = {"Scan", "Filter", "Project", "Aggregate", "Join", "Repartition", "Sort", "Limit", "Window", "Union"};
     const char *kind = kinds[(int)n->kind];
     if (n->kind == NKind::Join && n->join_type == JoinType::Semi) kind = "SemiJoin";
     if (n->kind == NKind::Join && n->join_type == JoinType::Anti) kind = "AntiJoin";
@@ -783,6 +784,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Repartition) os << (n->hash_diff ? "(HashDiff, " : "(Hash, ") << n->n_parts << ")";
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
+    if (n->kind == NKind::Union) os << "(" << n->in.size() << " inputs)";
     if (n->kind == NKind::Filter && (holds_like(n->pred.get()) || holds_func(n->pred.get()))) {
         os << "(";
         pred_text(n->pred.get(), n->schema, os);
@@ -839,7 +841,8 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (f != kNone) return;  // the fused pipeline swallows the sub-tree
     for (size_t i = 0; i < n->in.size(); ++i)
         describe(pl, n->in[i].get(), depth + 1, os,   // (a cross join prunes both sides to what is read above it: its scans say what they upload, too)
-                 keys_only || (n->kind == NKind::Join && (n->join_type == JoinType::Cross || (i == 1 && n->join_type != JoinType::Inner))));
+                 // (so does a union: with it, leaves of one relation upload the columns ANY of them reads -- union.hpp A-U7)
+                 keys_only || n->kind == NKind::Union || (n->kind == NKind::Join && (n->join_type == JoinType::Cross || (i == 1 && n->join_type != JoinType::Inner))));
 }
 
 // The whole plan is one NEXMark pipeline when, below pure projections, its root is a fused node (or q1's projection).
@@ -893,6 +896,7 @@ void node_sig(const flockgpu_plan *pl, const Node *n, bool top, std::string *o, 
     *o += std::to_string(n->n_parts) + (n->hash_diff ? "d" : "") + "|";
     for (auto &k : n->sort_cols) *o += std::to_string(k.col) + (k.descending ? "d" : "a") + (k.nulls_first ? "f" : "l") + ",";
     *o += std::to_string(n->limit) + "|";
+    if (n->kind == NKind::Union) *o += "U" + std::to_string(n->in.size()) + "|";   // (its inputs follow below, in order)
     for (auto &x : n->win) {   // (Window: each column's function, argument, PARTITION BY and ORDER BY)
         *o += (x.row_number ? std::string("rn") : std::to_string((int)x.fn) + "." + std::to_string(x.arg) + "." + std::to_string((int)x.type)) + ":";
         for (int c : x.part) *o += std::to_string(c) + ",";
@@ -1142,6 +1146,12 @@ struct Exec {
             if ((int)o == leaf || pl->leaves[o].rows == 0) continue;
             const Leaf &other = pl->ir.leaves[o];
             bool ok = true;
+            // (union.hpp A-U7) under COUNT(*) a branch of a union needs no column at all, and "every column it needs" holds of ANY fed leaf: an
+            // input that was fed no rows would count another relation's.  In a plan with a union such a leaf reads only a leaf of its own field list.
+            if (pl->ir.has_union && std::find(me.needed.begin(), me.needed.end(), 1) == me.needed.end()) {
+                ok = other.schema.size() == me.schema.size();
+                for (size_t c = 0; c < me.schema.size() && ok; ++c) ok = other.schema[c].name == me.schema[c].name && other.schema[c].type == me.schema[c].type;
+            }
             for (size_t c = 0; c < me.schema.size() && ok; ++c) {
                 if (!me.needed[c]) continue;
                 ok = false;
@@ -2349,6 +2359,7 @@ struct Exec {
             case NKind::Window: return exec_window(n, t);
             case NKind::Limit: return exec_limit(n, t);
             case NKind::Join: return n->join_type == JoinType::Cross ? exec_cross(n, t) : exec_join(n, t);
+            case NKind::Union: return exec_union(n, t);
             case NKind::Aggregate: {
                 const std::string &sig = pl->twin_sig[(size_t)n->id];
                 if (sig.empty()) return exec_aggregate(n, t);
@@ -2750,6 +2761,94 @@ struct Exec {
             const std::string name = node_key(pl, n, "cross", (int)i);
             if (left) FG_TRY(cross_repeat(ctx, name.c_str(), c.c, L, R, &o.c));
             else FG_TRY(cross_tile(ctx, name.c_str(), c.c, R, L, &o.c));
+        }
+        return FLOCKGPU_OK;
+    }
+
+    // UnionExec (union.hpp A-U1..7): the inputs' rows one input after the other, for the columns somebody reads.  Every input arrives lazily: the
+    // fixed-width columns and validity bytes of an input with a row list (a filter directly below) are read THROUGH the list by the union's kernels,
+    // its Utf8 columns are taken once and concatenated.  The operator queues launches only; a wait is an input's own (its filter's count, its take).
+    // Exactly one input with rows, and that one a plain table: its columns ARE the result -- no kernel, no copy.
+    int exec_union(const Node *n, Table *t) {
+        const size_t K = n->in.size(), C = n->schema.size();
+        std::vector<Lazy> Z(K);
+        std::vector<int64_t> rows(K, 0);
+        for (size_t k = 0; k < K; ++k) {
+            FG_TRY(exec_lazy(n->in[k].get(), &Z[k]));
+            if (Z[k].base.cols.size() != C) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: union (node %d): input %zu is not of the union's schema", n->id, k);
+            rows[k] = std::max<int64_t>(Z[k].rows, 0);
+        }
+        // (A-U6) the row count, before anything of the result exists
+        int64_t total = 0;
+        if (!union_rows_ok(rows.data(), (int)K, &total))
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: union (node %d) of %zu inputs: more than 2^31 rows", n->id, K);
+        t->rows = total;
+        t->cols.assign(C, TCol{});
+        for (size_t i = 0; i < C; ++i) {
+            t->cols[i].c.type = n->schema[i].type;
+            t->cols[i].c.is_ts = n->schema[i].is_ts;
+            t->cols[i].c.nullable = n->schema[i].nullable;
+        }
+        size_t with_rows = 0, only = 0;
+        for (size_t k = 0; k < K; ++k)
+            if (rows[k] > 0) { ++with_rows; only = k; }
+        if (with_rows == 1) {
+            const Lazy &z = Z[only];
+            if (z.via) return take_table(n->in[only].get(), z.base, n->required, z.via, z.rows, 0, t);   // (the one take a filter's result costs anyway)
+            for (size_t i = 0; i < C; ++i) {
+                const bool nullable = t->cols[i].c.nullable;
+                t->cols[i] = z.base.cols[i];
+                t->cols[i].c.nullable = nullable;
+                if (!n->required[i]) t->cols[i].present = false;
+            }
+            return FLOCKGPU_OK;
+        }
+        // the Utf8 columns of an input with a row list: ONE take of those somebody reads (the buffers are named after the input's node, which
+        // materialises nothing itself on this path)
+        std::vector<char> text(C, 0);
+        bool any_text = false;
+        for (size_t i = 0; i < C; ++i) {
+            text[i] = n->required[i] && n->schema[i].type == ColType::UTF8;
+            any_text = any_text || text[i];
+        }
+        std::vector<Table> taken(K);
+        for (size_t k = 0; k < K && any_text; ++k) {
+            if (!Z[k].via || rows[k] == 0) continue;
+            taken[k].rows = rows[k];
+            taken[k].cols.assign(C, TCol{});
+            FG_TRY(take_table(n->in[k].get(), Z[k].base, text, Z[k].via, rows[k], 0, &taken[k]));
+        }
+        std::vector<std::vector<UnionInput>> ins(C);
+        for (size_t i = 0; i < C; ++i) {
+            if (!n->required[i]) continue;
+            const bool utf8 = n->schema[i].type == ColType::UTF8;
+            ins[i].resize(K);
+            std::vector<int64_t> bytes(K, 0);
+            for (size_t k = 0; k < K; ++k) {
+                const bool was_taken = utf8 && Z[k].via && rows[k] > 0;
+                const TCol &c = was_taken ? taken[k].cols[i] : Z[k].base.cols[i];
+                if (rows[k] > 0 && !c.present && !c.c.all_null)
+                    return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: union (node %d): column '%s' of input %zu was not materialised", n->id, n->schema[i].name.c_str(), k);
+                if (c.c.type != n->schema[i].type)
+                    return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: union (node %d): column '%s' of input %zu arrives in another type", n->id, n->schema[i].name.c_str(), k);
+                ins[i][k].col = c.c;
+                ins[i][k].via = utf8 ? nullptr : Z[k].via;
+                ins[i][k].rows = rows[k];
+                if (utf8 && rows[k] > 0 && !c.c.all_null) bytes[k] = c.c.bytes;
+            }
+            // (A-U6) every Utf8 column's bytes, before anything of the result exists
+            int64_t sum = 0;
+            if (utf8 && !union_bytes_ok(bytes.data(), (int)K, &sum))
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan execute: union (node %d) of %zu inputs: Utf8 column '%s' exceeds 2^31 bytes", n->id, K, n->schema[i].name.c_str());
+        }
+        for (size_t i = 0; i < C; ++i) {
+            if (!n->required[i]) continue;
+            TCol &o = t->cols[i];
+            const bool nullable = o.c.nullable;
+            FG_TRY(union_column(ctx, node_key(pl, n, "union", (int)i).c_str(), ins[i].data(), (int)K, &o.c));
+            o.c.is_ts = n->schema[i].is_ts;
+            o.c.nullable = nullable || o.c.valid || o.c.all_null;
+            o.present = true;
         }
         return FLOCKGPU_OK;
     }

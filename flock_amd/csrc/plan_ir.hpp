@@ -12,6 +12,8 @@
 // Left / Right / Full joins, unknown expressions / types) makes the plan UNSUPPORTED: the host keeps its own engine for it.
 // cross_join_exec (cross.hpp A-X1..6) is a Join node of JoinType::Cross without key pairs: left ++ right columns, L x R rows, pair (i, j) at row i * R + j.
 // (The fork's typetag name cannot be checked -- its DataFusion source is not under the reference --: it follows the naming of every tag seen so far.)
+// union_exec (union.hpp A-U1..7) is a Union node over `inputs`: UNION ALL, the inputs' rows one input after the other; a union directly under a union
+// (also through the transparent nodes) is flattened, and in a plan that holds one the leaves of identical field lists share their `needed` masks.
 // hash_aggregate_exec takes COUNT / SUM / MIN / MAX / AVG and COUNT(DISTINCT x) -- an aggr_expr entry tagged "distinct_count" (alias "count_distinct") with
 // its one argument under `exprs` or `expr` (distinct.hpp A-D1..A-D7).  That aggregate's Partial state is a List column, which this boundary does not
 // carry: Final / FinalPartitioned over the Partial of the same plan becomes ONE single-pass node over the Partial's input (Node::single_pass); a Partial
@@ -129,7 +131,7 @@ inline int expr_static_type(const Expr *e, const std::vector<Field> &schema) {
     return -2;
 }
 
-enum class NKind { Scan, Filter, Project, Aggregate, Join, Repartition, Sort, Limit, Window };
+enum class NKind { Scan, Filter, Project, Aggregate, Join, Repartition, Sort, Limit, Window, Union };
 struct SortCol {
     int col = -1;            // input column
     bool descending = false;
@@ -206,6 +208,7 @@ struct WinExpr {
     std::vector<int> part;         // input columns of the PARTITION BY
     std::vector<SortCol> order;    // aggregate: input columns of the ORDER BY (they delimit the peer groups; the input arrives sorted)
 };
+constexpr int kMaxUnionInputs = 64;   // inputs of one union_exec after flattening (union.hpp kUnionMaxInputs)
 constexpr int kMaxWindowKeys = 4;   // PARTITION BY / ORDER BY columns of an aggregate window (each)
 enum class JoinType { Inner, Semi, Anti, Cross };   // Cross: cross_join_exec -- no key pairs (`on` empty), every pair of rows
 // a join key pair that can compare: two Utf8 columns, or two integer columns of one signedness (Float64 keys are refused)
@@ -277,6 +280,7 @@ struct Plan {
     std::vector<Leaf> leaves;
     int n_nodes = 0;
     std::string why;  // reason when unsupported
+    bool has_union = false;   // a union_exec somewhere: leaves of identical field lists share their `needed` masks (union.hpp A-U7)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1083,6 +1087,59 @@ struct Builder {
             }
             n->in.push_back(std::move(l));
             n->in.push_back(std::move(r));
+        } else if (t == "union_exec") {
+            // UnionExec (union.hpp): `inputs`, optionally `schema`.  A union that arrives as an input -- node() has already looked through the
+            // transparent nodes above it -- gives its inputs to this one
+            n->kind = NKind::Union;
+            plan->has_union = true;
+            const JValue *ins = j->get("inputs");
+            if (!ins || ins->kind != JValue::Arr || ins->arr.empty()) { fail("Union: no inputs (union_exec takes `inputs`, a list of at least one plan)"); return nullptr; }
+            for (auto &x : ins->arr) {
+                auto c = node(x.get(), depth + 1);
+                if (!c) return nullptr;
+                if (c->kind == NKind::Union) {
+                    for (auto &g : c->in) n->in.push_back(std::move(g));
+                } else {
+                    n->in.push_back(std::move(c));
+                }
+                if (n->in.size() > (size_t)kMaxUnionInputs) {
+                    fail("Union: more than " + std::to_string(kMaxUnionInputs) + " inputs after flattening (at least " + std::to_string(n->in.size()) + ")");
+                    return nullptr;
+                }
+            }
+            // (A-U1) names from input 0; every input its column count, types and is_ts; nullable when any input's column is
+            n->schema = n->in[0]->schema;
+            for (size_t k = 1; k < n->in.size(); ++k) {
+                const std::vector<Field> &sk = n->in[k]->schema;
+                if (sk.size() != n->schema.size()) {
+                    fail("Union: input " + std::to_string(k) + " has " + std::to_string(sk.size()) + " columns, input 0 has " + std::to_string(n->schema.size()));
+                    return nullptr;
+                }
+                for (size_t i = 0; i < sk.size(); ++i) {
+                    if (sk[i].type != n->schema[i].type || sk[i].is_ts != n->schema[i].is_ts) {
+                        fail("Union: input " + std::to_string(k) + " gives " + type_name(sk[i]) + " for column " + std::to_string(i) + " ('" + sk[i].name + "'), input 0 gives " +
+                             type_name(n->schema[i]) + " ('" + n->schema[i].name + "'): the inputs of a union have one schema");
+                        return nullptr;
+                    }
+                    n->schema[i].nullable = n->schema[i].nullable || sk[i].nullable;
+                }
+            }
+            const JValue *sc = j->get("schema");
+            const JValue *sf = sc ? sc->get("fields") : nullptr;
+            if (sf && sf->kind == JValue::Arr) {
+                std::vector<Field> given;
+                if (!fields_of(sc, &given)) return nullptr;
+                if (given.size() != n->schema.size()) {
+                    fail("Union: the node's schema (" + std::to_string(given.size()) + " columns) is not its inputs' (" + std::to_string(n->schema.size()) + " columns)");
+                    return nullptr;
+                }
+                for (size_t i = 0; i < given.size(); ++i)
+                    if (given[i].type != n->schema[i].type || given[i].is_ts != n->schema[i].is_ts) {
+                        fail("Union: the node's schema says " + std::string(type_name(given[i])) + " for column " + std::to_string(i) + " ('" + given[i].name +
+                             "'), the inputs give " + type_name(n->schema[i]) + ": a union returns its inputs' columns unchanged");
+                        return nullptr;
+                    }
+            }
         } else if (t == "sort_exec") {
             n->kind = NKind::Sort;
             auto in = node(j->get("input"), depth + 1);
@@ -1355,6 +1412,9 @@ inline void mark_required(Plan *p, Node *n, const std::vector<char> &req) {
             mark_required(p, n->in[0].get(), r);
             break;
         }
+        case NKind::Union:   // output column c is column c of every input
+            for (auto &c : n->in) mark_required(p, c.get(), req);
+            break;
     }
 }
 
@@ -1452,6 +1512,9 @@ inline void mark_null_droppable(Plan *p, const Node *n, const std::vector<char> 
         case NKind::Window: // ... and so does every row's number
             mark_null_droppable(p, n->in[0].get(), std::vector<char>(n->in[0]->schema.size(), 0));
             break;
+        case NKind::Union:  // by position: a row dropped below is the row dropped above
+            for (auto &c : n->in) mark_null_droppable(p, c.get(), droppable);
+            break;
     }
 }
 
@@ -1475,6 +1538,27 @@ inline void mark_co_partitioned(Plan *p, const Node *n, bool under) {
     for (auto &c : n->in) mark_co_partitioned(p, c.get(), under);
 }
 
+// (union.hpp A-U7) leaves with identical field lists are one relation scanned more than once; fed as ONE source, every scan but the first reads the
+// fed leaf (Exec::resolve_leaf), which must then hold every column any of them reads: the OR of their `needed` masks.  A row that one of them could
+// drop for a NULL is still a row of the others: the AND of their null_droppable marks.
+inline void share_leaf_masks(Plan *p) {
+    auto same = [](const Leaf &a, const Leaf &b) {
+        if (a.schema.size() != b.schema.size()) return false;
+        for (size_t c = 0; c < a.schema.size(); ++c)
+            if (a.schema[c].name != b.schema[c].name || a.schema[c].type != b.schema[c].type || a.schema[c].is_ts != b.schema[c].is_ts) return false;
+        return true;
+    };
+    for (size_t a = 0; a < p->leaves.size(); ++a)
+        for (size_t b = a + 1; b < p->leaves.size(); ++b) {
+            Leaf &x = p->leaves[a], &y = p->leaves[b];
+            if (!same(x, y) || x.needed.size() != y.needed.size() || x.null_droppable.size() != y.null_droppable.size()) continue;
+            for (size_t c = 0; c < x.needed.size(); ++c) {
+                x.needed[c] = y.needed[c] = x.needed[c] | y.needed[c];
+                x.null_droppable[c] = y.null_droppable[c] = x.null_droppable[c] & y.null_droppable[c];
+            }
+        }
+}
+
 inline bool build_plan(const JValue *root, Plan *plan) {
     Builder b{plan, {}};
     plan->root = b.node(root);
@@ -1485,6 +1569,7 @@ inline bool build_plan(const JValue *root, Plan *plan) {
     mark_required(plan, plan->root.get(), std::vector<char>(plan->root->schema.size(), 1));
     mark_null_droppable(plan, plan->root.get(), std::vector<char>(plan->root->schema.size(), 0));
     mark_co_partitioned(plan, plan->root.get(), false);
+    if (plan->has_union) share_leaf_masks(plan);
     return true;
 }
 

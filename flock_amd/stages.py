@@ -10,7 +10,8 @@ from the root;
     inputs become the two plans of the stage below -- and the walk stops there (stage.rs:335-336);
   * `sort_exec`: like a final aggregate;
   * everything else: descend.  (`cross_join_exec` has no `input`: the walk ends there as it does at a leaf, and the cross join stays in one
-    stage with both of its inputs -- stage.rs knows no such node.)
+    stage with both of its inputs -- stage.rs knows no such node.  `union_exec` has no `input` either, only `inputs`: the walk ends there too, no
+    cut is made at a union, and the union stays in one stage with all of its inputs.)
 A stage plan whose root is `coalesce_batches_exec <- repartition_exec Hash` is a shuffling stage
 (`ExecutionContext::is_shuffling`, flock/src/runtime/context.rs:328-337): the function runs `execute_partitioned` and sends
 partition j to member j of the next function group (flock-function/src/aws/actor.rs:60-66,425-543).
@@ -69,6 +70,10 @@ def node_schema(n: dict) -> dict:
         if "schema" in n:
             return copy.deepcopy(n["schema"])
         return {"fields": node_schema(n["left"])["fields"] + node_schema(n["right"])["fields"], "metadata": {}}
+    if kind == "union_exec":        # (no cut here either: its `schema`, else input 0's -- the names a union takes, union.hpp A-U1)
+        if "schema" in n:
+            return copy.deepcopy(n["schema"])
+        return node_schema(n["inputs"][0])
     if "input" in n:
         return node_schema(n["input"])
     raise ValueError(f"no schema for plan node {kind!r}")
@@ -79,12 +84,20 @@ def _empty_memory(schema: dict) -> dict:
     return {"execution_plan": "memory_exec", "schema": schema, "projection": None}
 
 
+def _children(n: dict) -> List[dict]:
+    """The inputs of a plan node, in order: `input`, `left`, `right`, and a union_exec's `inputs`."""
+    kids = [n[k] for k in ("input", "left", "right") if isinstance(n.get(k), dict)]
+    if isinstance(n.get("inputs"), list):
+        kids += [c for c in n["inputs"] if isinstance(c, dict)]
+    return kids
+
+
 def leaves_bfs(plan: dict) -> List[dict]:
     """memory_exec leaves in the breadth-first order feed_data_sources visits them (context.rs:262-300)."""
     out, queue = [], [plan]
     while queue:
         n = queue.pop(0)
-        kids = [n[k] for k in ("input", "left", "right") if isinstance(n.get(k), dict)]
+        kids = _children(n)
         if n.get("execution_plan") == "memory_exec":
             out.append(n)
         queue.extend(kids)
@@ -92,7 +105,9 @@ def leaves_bfs(plan: dict) -> List[dict]:
 
 
 def build_query_dag(plan: dict) -> List[Stage]:
-    """stage.rs:269-367 on the JSON tree.  Returns stages leaves-first; the last one is the plan's root stage."""
+    """stage.rs:269-367 on the JSON tree.  Returns stages leaves-first; the last one is the plan's root stage.
+    No cut is made at a `union_exec` (or a `cross_join_exec`): it has no `input`, so the walk ends there as at a leaf, and whatever lies below
+    it -- repartitions and aggregates inside its branches included -- stays in the stage that holds it."""
     root = copy.deepcopy(plan)
     stages_top_down: List[tuple] = []     # (plan, marker leaf objects in it that the NEXT entries feed)
     node = root
@@ -184,6 +199,8 @@ def split_at_repartitions(plan: dict) -> List[Stage]:
     def cut(n: dict, is_root: bool) -> dict:
         """Returns `n` with every shuffling sub-tree below it replaced by a marker leaf."""
         n = dict(n)
+        if isinstance(n.get("inputs"), list):   # union_exec: every branch on its own, in input order (never the root's own repartition)
+            n["inputs"] = [cut({"input": c}, False)["input"] if isinstance(c, dict) else c for c in n["inputs"]]
         for key in ("input", "left", "right"):
             child = n.get(key)
             if not isinstance(child, dict):

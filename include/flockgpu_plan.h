@@ -88,7 +88,9 @@ typedef struct flockgpu_plan flockgpu_plan;
  * eight accumulators, AVG taking two -- gives exactly one row in every mode, also over no rows; with GROUP BY up to sixteen accumulators per node), hash_join_exec (Inner; Semi / Anti: the left input's rows that have / lack a partner, left schema), repartition_exec, coalesce_batches_exec / coalesce_partitions_exec / merge_exec (transparent), sort_exec,
  * global_limit_exec / local_limit_exec, window_agg_exec (ROW_NUMBER()), cross_join_exec (`left`, `right`: the left input's columns followed by the right
  * input's, L x R rows, pair (left row i, right row j) at output row i * R + j however the inputs were fed; a result of 2^31 rows or more, or an output
- * Utf8 column of 2^31 bytes or more, fails the execute with FLOCKGPU_ERR_UNSUPPORTED before anything is allocated or launched).
+ * Utf8 column of 2^31 bytes or more, fails the execute with FLOCKGPU_ERR_UNSUPPORTED before anything is allocated or launched), union_exec (`inputs`, a
+ * list of 1 to 64 plans of one schema -- input 0's names: UNION ALL, the rows of input 0 in their order, then input 1's, and so on, NULLs verbatim; the
+ * same limits of 2^31 rows and Utf8 bytes as the cross join's).
  * Expressions (`physical_expr` tags): column, literal, cast_expr, try_cast_expr, binary_expr (Eq NotEq Lt LtEq Gt GtEq And Or Plus Minus
  * Multiply Divide Modulo), not_expr, is_null_expr, is_not_null_expr, negative_expr, in_list_expr, case_expr -- over Int32 / Int64 / UInt64 /
  * Float64 / Timestamp(Millisecond) values (Utf8: =, <>, IN, IS NULL against literals).  A computed value may also be TEXT: a Utf8 literal, a Utf8
