@@ -24,7 +24,7 @@ struct UMod32 {
     uint32_t add = 0;    // the 33-bit multiplier case
 };
 
-inline UMod32 umod32_make(uint32_t d) {
+constexpr UMod32 umod32_make(uint32_t d) {   // (constexpr: a divisor known at compile time -- numtext.hpp's powers of ten -- folds into the code)
     UMod32 m;
     m.d = d ? d : 1;
     uint32_t k = 31;
@@ -47,16 +47,14 @@ inline UMod32 umod32_make(uint32_t d) {
     return m;
 }
 
-FLOCKGPU_HD uint32_t umod32_apply(uint32_t n, const UMod32 &m) {
-    uint32_t q;
-    if (m.magic == 0) {
-        q = n >> m.shift;
-    } else {
-        const uint32_t hi = (uint32_t)(((uint64_t)n * m.magic) >> 32);
-        q = m.add ? ((((n - hi) >> 1) + hi) >> m.shift) : (hi >> m.shift);
-    }
-    return n - q * m.d;
+// floor(n / d)
+FLOCKGPU_HD uint32_t udiv32_apply(uint32_t n, const UMod32 &m) {
+    if (m.magic == 0) return n >> m.shift;
+    const uint32_t hi = (uint32_t)(((uint64_t)n * m.magic) >> 32);
+    return m.add ? ((((n - hi) >> 1) + hi) >> m.shift) : (hi >> m.shift);
 }
+
+FLOCKGPU_HD uint32_t umod32_apply(uint32_t n, const UMod32 &m) { return n - udiv32_apply(n, m) * m.d; }
 
 // Truncated remainder of a signed 32-bit value by m (|m| = mm.d): the sign of the dividend, as Rust's / Arrow's `%`.
 FLOCKGPU_HD int32_t smod32_apply(int32_t x, const UMod32 &mm) {

@@ -727,7 +727,15 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
         case EKind::LitS: os << "'" << e->s << "'"; return;
         case EKind::LitB: os << (e->i ? "TRUE" : "FALSE"); return;
         case EKind::LitNull: os << "NULL"; return;
-        case EKind::Cast: pred_text(e->l.get(), schema, os); return;   // (the value, not its conversion)
+        case EKind::Cast:
+            if (e->num_text) {   // a number made text (numtext.hpp): CAST(price AS Utf8)
+                os << (e->try_cast ? "TRY_CAST(" : "CAST(");
+                pred_text(e->l.get(), schema, os);
+                os << " AS Utf8)";
+                return;
+            }
+            pred_text(e->l.get(), schema, os);   // (the value, not its conversion)
+            return;
         case EKind::Neg: os << "-"; pred_text(e->l.get(), schema, os); return;
         case EKind::Not: os << "NOT ("; pred_text(e->l.get(), schema, os); os << ")"; return;
         case EKind::IsNull: pred_text(e->l.get(), schema, os); os << " IS NULL"; return;
@@ -1135,6 +1143,8 @@ struct Exec {
     int64_t now_ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
     int fn_cols = 0;   // length columns written so far by this execute (octet_length / char_length: a buffer each, named by this count)
     int slice_bufs = 0;   // ... and the (begin, end) pairs of text slice calls (textslice.hpp)
+    int cast_bufs = 0;    // ... and the Utf8 columns of numbers cast to text (numtext.hpp)
+    std::map<std::string, DevColumn> cast_cols;   // the casts of the projection at hand by their text: identical casts are computed once (exec_project clears it)
 
     // A relation the SQL scans twice (q5 and q7 read `bid` in both join inputs, q5_plan.fmt:6,13) has two MemoryExec leaves
     // but arrives as ONE source, which feed_data_sources hands to the first matching leaf (context.rs:273-300) -- the
@@ -2067,9 +2077,14 @@ struct Exec {
         switch (e->kind) {
             case EKind::LitS: return source(tt.add_literal(e->s));
             case EKind::LitNull: return null();
-            case EKind::Cast:
+            case EKind::Cast: {
                 if (e->cast_to != ColType::UTF8) return val_unsupported("CASE branches of different types");
-                return text_compile(e->l.get(), in, b, tt, may_null);
+                if (!e->num_text) return text_compile(e->l.get(), in, b, tt, may_null);
+                DevColumn col;   // a number or timestamp made text (numtext.hpp): a column source
+                FG_TRY(cast_column(e, in, &col));
+                if (col.all_null) return null();
+                return source(tt.add_column(col));
+            }
             case EKind::Col: {
                 const TCol &c = in.cols[(size_t)e->col];
                 if (c.c.type != ColType::UTF8) return val_unsupported("CASE branches of different types");
@@ -2081,7 +2096,7 @@ struct Exec {
                 if (!fn_is_slice(e->fn)) return val_unsupported("CASE branches of different types");
                 std::vector<const Expr *> chain;
                 const Expr *c = e;
-                while (c->kind == EKind::Func || c->kind == EKind::Cast) {
+                while (c->kind == EKind::Func || (c->kind == EKind::Cast && !c->num_text)) {
                     if (c->kind == EKind::Func) {
                         if (!fn_is_slice(c->fn) || c->list.empty()) return val_unsupported("a text slice of something that is not a Utf8 column");
                         chain.push_back(c);
@@ -2090,8 +2105,14 @@ struct Exec {
                         c = c->l.get();
                     }
                 }
-                if (c->kind != EKind::Col || in.cols[(size_t)c->col].c.type != ColType::UTF8) return val_unsupported("a text slice of something that is not a Utf8 column");
-                const TCol &col = in.cols[(size_t)c->col];
+                TCol col;
+                if (c->kind == EKind::Cast) {   // the column under the slice is a number cast to Utf8 (numtext.hpp)
+                    FG_TRY(cast_column(c, in, &col.c));
+                    col.present = true;
+                } else {
+                    if (c->kind != EKind::Col || in.cols[(size_t)c->col].c.type != ColType::UTF8) return val_unsupported("a text slice of something that is not a Utf8 column");
+                    col = in.cols[(size_t)c->col];
+                }
                 if (col.c.all_null) return null();
                 if (!col.present || !col.c.offsets) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
                 // (the key names the column by its position in `in`: identical calls of one expression are one source)
@@ -2140,6 +2161,49 @@ struct Exec {
             default: return val_unsupported("CASE branches of different types");
         }
     }
+    // CAST(x AS Utf8) of a number or timestamp (numtext.hpp) as a Utf8 column: x is a column of `in`, or an expression the general evaluator computes
+    // into a temporary column first.  Identical casts of one projection are one column.
+    int cast_column(const Expr *e, const Table &in, DevColumn *out) {
+        const std::string key = expr_text(e, std::vector<std::string>());   // (columns by their position in `in`)
+        auto hit = cast_cols.find(key);
+        if (hit != cast_cols.end()) {
+            *out = hit->second;
+            return FLOCKGPU_OK;
+        }
+        const Node *root = pl->ir.root.get();
+        const int slot = cast_bufs++;
+        const Expr *x = e->l.get();
+        DevColumn src;
+        if (x->kind == EKind::Col) {
+            const TCol &c = in.cols[(size_t)x->col];
+            if (!c.c.all_null && !c.present) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
+            src = c.c;
+        } else {
+            ValBuilder vb;
+            int vt = -1;
+            bool may_null = false;
+            FG_TRY(val_compile(x, in, vb, -1, &vt, &may_null));
+            if (vt < 0 || vt > 2) return val_unsupported("CAST to Utf8 of a computed value that is not an integer or a Timestamp(ms)");
+            void *vals = nullptr;
+            uint8_t *vv = nullptr;
+            FG_TRY(arena_get(ctx, node_key(pl, root, "castval", slot).c_str(), ((size_t)std::max<int64_t>(in.rows, 0) + 2) * 8, &vals));
+            if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, root, "castvalv", slot).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 16, &vv));
+            FG_TRY(valprog_to_column(ctx, node_key(pl, root, "castprog", slot).c_str(), vb.p, in.rows, (ColType)vt, vals, vv));
+            src.type = (ColType)vt;
+            src.is_ts = expr_is_ts(x);
+            src.values = vals;
+            src.valid = vv;
+        }
+        if (src.all_null) {
+            *out = DevColumn{};
+            out->type = ColType::UTF8;
+            out->all_null = true;
+        } else {
+            FG_TRY(num_to_text(ctx, node_key(pl, root, "numtext", slot).c_str(), src, in.rows, e->try_cast, e->try_cast ? "try_cast_expr" : "cast_expr", out));
+        }
+        cast_cols[key] = *out;
+        return FLOCKGPU_OK;
+    }
     // Column i of projection `n` as text: the selector through the evaluator (none for a bare literal or column), then the length and emit passes
     int project_text(const Node *n, size_t i, const Table &in, TCol *o) {
         const Expr *e = n->proj[i].first.get();
@@ -2153,7 +2217,15 @@ struct Exec {
         const bool bare = vb.p.n_ops == 1;   // one push: a literal, a column, a NULL
         if (bare && tt.s.k == 1 && tt.s.src[0].offsets && !tt.s.src[0].begin) {   // CAST(column AS Utf8): the column itself (a bare slice is one text_select)
             const Expr *c = e;
-            while (c->kind == EKind::Cast) c = c->l.get();
+            while (c->kind == EKind::Cast && !c->num_text) c = c->l.get();
+            if (c->kind == EKind::Cast) {   // a bare cast of a number: the column numtext.hip wrote
+                DevColumn col;
+                FG_TRY(cast_column(c, in, &col));
+                *o = dev_col(ColType::UTF8, col.values, col.offsets, col.bytes);
+                o->c.valid = col.valid;
+                o->c.nullable = true;
+                return FLOCKGPU_OK;
+            }
             *o = in.cols[(size_t)c->col];
             o->c.nullable = true;
             return FLOCKGPU_OK;
@@ -2393,6 +2465,8 @@ struct Exec {
     int exec_project(const Node *n, Table *t) {
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
+        cast_cols.clear();   // (the casts of numbers to Utf8 of THIS projection's input, numtext.hpp)
+        for (size_t c = 0; c < in.cols.size() && c < n->in[0]->schema.size(); ++c) in.cols[c].c.is_ts = n->in[0]->schema[c].is_ts;   // (such a cast reads it)
         t->rows = in.rows;
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->proj.size(); ++i) {

@@ -22,6 +22,8 @@
 // (textsel.hpp A-T1..A-T5) -- as a projected column and, through computed_column, as a GROUP BY / ORDER BY key or a COUNT / COUNT(DISTINCT) argument.
 // The text slice functions split_part / left / right / ltrim / rtrim / btrim of a Utf8 column (textslice.hpp A-SL1..A-SL8) are text-valued expressions
 // too: `split_part(url, '/', 4)`, `btrim(split_part(description, ',', 1))`.  Every other text-producing function stays refused.
+// CAST(x AS Utf8) / TRY_CAST(x AS Utf8) of an Int32 / Int64 / UInt64 / Timestamp(ms) column or numeric expression (numtext.hpp A-NT1..A-NT7) is text-valued
+// as well and counts as a Utf8 column wherever one is taken: `left(CAST(b_date_time AS Utf8), 10)` is NEXMark q10's date.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -63,6 +65,7 @@ struct Expr {
     bool big_unsigned = false;                 // LitI: `i` is the bit pattern of a UInt64 above INT64_MAX
     bool cast_ts = false;                      // Cast: the target is Timestamp(Millisecond) (Int64 storage)
     bool try_cast = false;                     // Cast: try_cast_expr (a value that does not fit becomes NULL instead of failing the call)
+    bool num_text = false;                     // Cast to Utf8 of something that is not text: the number / timestamp is FORMATTED (numtext.hpp); false: Utf8 to Utf8, nothing happens
     std::string lit_kind;                      // literals: the ScalarValue variant ("Int32", "Float64", ...; empty: a bare JSON value)
     Fn fn = Fn::Abs;                           // Func: the function (`s`: its canonical name; `i`: the cal::Unit of date_trunc / date_part, else -1; `list`: the value
                                                // arguments -- one, none for now(); the unit literal is folded into `i`)
@@ -75,20 +78,56 @@ inline bool fn_is_slice(Fn f) { return f >= Fn::SplitPart; }
 inline SliceFn slice_fn_of(Fn f) { return (SliceFn)((int)f - (int)Fn::SplitPart); }
 // A slice call as text, the way explain prints it: split_part(url, '/', 4), btrim(split_part(description, ',', 1)), ltrim(name).  Identical calls
 // give identical text: the key under which one source table holds a slice once.  (`e` a slice Func; a cast in front of the value argument is not printed.)
+// (A value argument that is a cast of a number to Utf8 -- numtext.hpp -- prints as CAST(price AS Utf8): expr_text below.)
+inline std::string expr_text(const Expr *e, const std::vector<std::string> &col_names);
 inline std::string slice_text(const Expr *e, const std::vector<std::string> &col_names) {
     const Expr *v = e->list[0].get();
-    while (v->kind == EKind::Cast) v = v->l.get();
+    while (v->kind == EKind::Cast && !v->num_text) v = v->l.get();
     std::string t = e->s + "(";
-    if (v->kind == EKind::Func) t += slice_text(v, col_names);
+    if (v->kind == EKind::Cast) t += expr_text(v, col_names);
+    else if (v->kind == EKind::Func) t += slice_text(v, col_names);
     else if (v->kind == EKind::Col && v->col >= 0 && (size_t)v->col < col_names.size()) t += col_names[(size_t)v->col];
     else t += "#" + std::to_string(v->col);
     if (e->slice_has_arg) t += ", '" + e->slice_arg + "'";
     if (e->fn == Fn::SplitPart || e->fn == Fn::Left || e->fn == Fn::Right) t += ", " + std::to_string(e->slice_n);
     return t + ")";
 }
-// how deep slice calls nest in `e` (a column: 0)
+// An expression as text, structure for structure: identical expressions give identical text -- the key under which a source table holds the cast of a
+// number to Utf8 once -- and explain prints it (CAST(price * 2 AS Utf8)).
+inline std::string expr_text(const Expr *e, const std::vector<std::string> &col_names) {
+    if (!e) return "?";
+    auto list = [&](const char *sep) {
+        std::string t;
+        for (size_t i = 0; i < e->list.size(); ++i) t += (i ? sep : "") + expr_text(e->list[i].get(), col_names);
+        return t;
+    };
+    static const char *types[] = {"Int32", "Int64", "UInt64", "Float64", "Utf8"};
+    switch (e->kind) {
+        case EKind::Col: return e->col >= 0 && (size_t)e->col < col_names.size() ? col_names[(size_t)e->col] : "#" + std::to_string(e->col);
+        case EKind::LitI: return e->big_unsigned ? std::to_string((uint64_t)e->i) : std::to_string(e->i);
+        case EKind::LitF: { std::ostringstream os; os << e->f; return os.str(); }
+        case EKind::LitS: return "'" + e->s + "'";
+        case EKind::LitB: return e->i ? "TRUE" : "FALSE";
+        case EKind::LitNull: return "NULL";
+        case EKind::Cast:
+            return std::string(e->try_cast ? "TRY_CAST(" : "CAST(") + expr_text(e->l.get(), col_names) + " AS " + (e->cast_ts ? "Timestamp(ms)" : types[(int)e->cast_to <= 4 ? (int)e->cast_to : 4]) + ")";
+        case EKind::Neg: return "-(" + expr_text(e->l.get(), col_names) + ")";
+        case EKind::Not: return "NOT (" + expr_text(e->l.get(), col_names) + ")";
+        case EKind::IsNull: return "(" + expr_text(e->l.get(), col_names) + ") IS NULL";
+        case EKind::IsNotNull: return "(" + expr_text(e->l.get(), col_names) + ") IS NOT NULL";
+        case EKind::InList: return "(" + expr_text(e->l.get(), col_names) + (e->negated ? ") NOT IN (" : ") IN (") + list(", ") + ")";
+        case EKind::Bin: return "(" + expr_text(e->l.get(), col_names) + " " + e->s + " " + expr_text(e->r.get(), col_names) + ")";
+        case EKind::Func:
+            if (fn_is_slice(e->fn)) return slice_text(e, col_names);
+            return e->s + "(" + (e->i >= 0 ? std::to_string(e->i) + ", " : std::string()) + list(", ") + ")";
+        case EKind::Case:
+            return "CASE " + (e->l ? expr_text(e->l.get(), col_names) + " " : std::string()) + "[" + list("; ") + "]" + (e->r ? " ELSE " + expr_text(e->r.get(), col_names) : std::string()) + " END";
+    }
+    return "?";
+}
+// how deep slice calls nest in `e` (a column, or a number cast to Utf8: 0)
 inline int slice_depth(const Expr *e) {
-    while (e->kind == EKind::Cast) e = e->l.get();
+    while (e->kind == EKind::Cast && !e->num_text) e = e->l.get();
     return e->kind == EKind::Func && fn_is_slice(e->fn) ? 1 + slice_depth(e->list[0].get()) : 0;
 }
 // the result is a Timestamp(Millisecond): CAST(x AS Timestamp), date_trunc, now()
@@ -434,7 +473,11 @@ struct Builder {
             if (!parse_type(e->get("cast_type"), &x->cast_to, &ts)) { fail("cast to an unsupported type"); return nullptr; }
             x->cast_ts = ts;
             x->l = expr(e->get("expr"), schema);
-            return x->l ? std::move(x) : nullptr;
+            if (!x->l) return nullptr;
+            // to Utf8 from anything but text (a NULL literal takes the type): the value is formatted (numtext.hpp)
+            const int from = expr_static_type(x->l.get(), schema);   // (-1: untyped NULLs alone, or an untyped integer literal)
+            x->num_text = x->cast_to == ColType::UTF8 && !ts && from != 4 && (from != -1 || x->l->kind == EKind::LitI);
+            return x;
         }
         if (t == "binary_expr") {
             x->kind = EKind::Bin;
@@ -575,9 +618,13 @@ struct Builder {
                 return refuse(who + " with " + std::to_string(av.size()) + " arguments: it takes " +
                               (split ? "(string, delimiter, n)" : count ? "(string, n)" : "(string) or (string, characters)"));
             // the value: a Utf8 column or a slice function of one
-            const Expr *v = no_utf8_cast(av[0].get());
+            // ... and a number or timestamp cast to Utf8 counts as such a column (numtext.hpp A-NT7)
+            const Expr *v = av[0].get();
+            while (v->kind == EKind::Cast && v->cast_to == ColType::UTF8 && !v->num_text) v = v->l.get();
             const bool inner = v->kind == EKind::Func && fn_is_slice(v->fn);
-            if (!inner && !(v->kind == EKind::Col && schema[(size_t)v->col].type == ColType::UTF8)) {
+            if (v->kind == EKind::Cast && v->num_text) {
+                if (!check_num_text(v, schema)) return nullptr;
+            } else if (!inner && !(v->kind == EKind::Col && schema[(size_t)v->col].type == ColType::UTF8)) {
                 const char *what = v->kind == EKind::LitS || v->kind == EKind::LitNull ? "a literal" : v->kind == EKind::Case ? "a CASE" : v->kind == EKind::Col ? "a column that is not Utf8" : "a computed value";
                 return refuse(who + ": the value argument is " + what + ", it takes a Utf8 column or a slice function (split_part, left, right, ltrim, rtrim, btrim) of one");
             }
@@ -668,6 +715,18 @@ struct Builder {
         return true;
     }
 
+    // CAST(x AS Utf8) of something that is not text (numtext.hpp A-NT1 / A-NT6): x is an Int32 / Int64 / UInt64 / Timestamp(ms) column or expression
+    bool check_num_text(const Expr *e, const std::vector<Field> &schema) {
+        const std::string who = e->try_cast ? "try_cast_expr: " : "cast_expr: ";
+        const Expr *x = e->l.get();
+        if (x->kind == EKind::LitI || x->kind == EKind::LitF || x->kind == EKind::LitB)
+            return fail(who + "CAST of a literal to Utf8 (a literal operand: write the text itself)");
+        const int from = expr_static_type(x, schema);
+        if (from == 3) return fail(who + "CAST of a Float64 value to Utf8 (Rust's shortest round-trip form has no counterpart on the device)");
+        if (from == 5) return fail(who + "CAST of a Boolean value to Utf8 (no Boolean columns at this boundary)");
+        if (from < 0 || from > 2) return fail(who + "CAST to Utf8 of an operand without one numeric type");
+        return true;
+    }
     // A text-valued expression (textsel.hpp A-T1) in a value position: its sources -- distinct literals and columns -- are collected for the A-T5
     // limits; a branch of another type is refused.
     bool text_sources(const Expr *e, const std::vector<Field> &schema, std::set<std::string> *lits, std::set<int> *cols, std::set<std::string> *slices) {
@@ -687,8 +746,13 @@ struct Builder {
                 return true;
             case EKind::Cast: {
                 if (e->cast_to != ColType::UTF8) return fail("CASE branches of different types");
-                const int from = expr_static_type(e->l.get(), schema);
-                if (from != 4 && from != -1) return fail("CAST between other than numeric types inside a computed expression");
+                if (e->num_text) {   // a number or timestamp made text (numtext.hpp): one column source, identical casts once
+                    if (!check_num_text(e, schema)) return false;
+                    std::vector<std::string> names;
+                    for (auto &f : schema) names.push_back(f.name);
+                    slices->insert(expr_text(e, names));
+                    return true;
+                }
                 return text_sources(e->l.get(), schema, lits, cols, slices);
             }
             case EKind::Case:

@@ -19,7 +19,7 @@
 // Dialect and semantics (DataFusion ~6 CaseExpr / Literal; like valprog.hpp's A-V / A-F lists ASSUMPTIONS, not reference-held vectors -- checked
 // against tests/text_expr_ref.py and, there, against pyarrow.compute.case_when):
 //   A-T1 a text-valued expression is a Utf8 literal ({"Utf8": null}: a NULL of type Utf8), a Utf8 column (a cast_expr to Utf8 may sit in front),
-//        or a case_expr whose THEN / ELSE branches are text-valued or untyped NULL literals (nested CASE counts).  Its static type is Utf8; leading
+//        a cast_expr / try_cast_expr to Utf8 of an integer or Timestamp(ms) value (A-T7), or a case_expr whose THEN / ELSE branches are text-valued or untyped NULL literals (nested CASE counts).  Its static type is Utf8; leading
 //        NULL branches do not hide it.  A CASE that mixes text and numeric branches is refused ("CASE branches of different types");
 //   A-T2 CASE picks the first WHEN that is TRUE (NULL and FALSE are not), else ELSE, else NULL; `CASE WHEN cond` and `CASE base WHEN value` are
 //        both taken; conditions, base and value are what the general evaluator takes (numeric, Timestamp, scalar functions, IS NULL, IN, Kleene
@@ -34,6 +34,9 @@
 //        the published total before any byte is written.
 //   A-T6 the slice functions split_part / left / right / ltrim / rtrim / btrim of a Utf8 column (textslice.hpp A-SL1..A-SL8) are text-valued
 //        expressions too: one slice expression is one source, identical ones count once.
+//   A-T7 CAST(x AS Utf8) / TRY_CAST(x AS Utf8) of an Int32 / Int64 / UInt64 / Timestamp(ms) column or numeric expression (numtext.hpp A-NT1..A-NT7) is a
+//        text-valued expression too.  The cast is computed into an ordinary Utf8 column first (numtext.hip) and enters the table as a COLUMN source:
+//        one source, identical casts once; a bare projected cast is that column itself.  A Float64, Boolean or literal operand is refused by name.
 //   Still refused, as before: a Utf8 column or literal inside a condition or under an operator, LIKE inside a computed expression, the other
 //   text-producing scalar functions (substr, lower, upper, trim, concat, ...), Boolean projections, hash partitioning on a computed expression,
 //   MIN / MAX of text.
@@ -42,6 +45,7 @@
 #include <string>
 #include <vector>
 
+#include "numtext.hpp"
 #include "relops.hpp"
 
 namespace flockgpu {
@@ -115,5 +119,10 @@ struct TextTable {
 // whose chosen column holds a NULL there is NULL.  No source at all: every row NULL.  Offsets, bytes and validity live in the ctx arena under
 // `name`.  One host wait (the byte total); none for a bare literal or an empty result.
 int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &srcs, const int32_t *sel, const uint8_t *sel_valid, int64_t rows, DevColumn *out);
+
+// CAST(`in` AS Utf8) (numtext.hip; numtext.hpp A-NT1..A-NT7): `in` an Int32 / Int64 / UInt64 column, a Timestamp(ms) one when in.is_ts.  A NULL row gives
+// a NULL; a timestamp outside the years 0000..9999 gives a NULL when `try_cast`, else the call fails naming `who` (the expression's tag).  Offsets, bytes
+// and validity live in the ctx arena under `name`.  One host wait (the byte total, and with it the flag word).
+int num_to_text(flockgpu_ctx *ctx, const char *name, const DevColumn &in, int64_t rows, bool try_cast, const char *who, DevColumn *out);
 
 }  // namespace flockgpu

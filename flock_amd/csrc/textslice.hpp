@@ -30,7 +30,8 @@
 // A-F list -- ASSUMPTIONS, checked against tests/text_slice_ref.py and, there, against pyarrow.compute):
 //   A-SL1 scalar_function_expr named split_part, left, right, ltrim, rtrim or btrim (case-insensitive); return_type, where present, is Utf8.  The
 //         value argument is a Utf8 column or another slice function of one (a cast_expr to Utf8 may sit in front of either), nested at most
-//         kSliceMaxDepth deep; every other argument is a literal (a cast to the literal's own type may sit in front of it).  Refused by name at create /
+//         kSliceMaxDepth deep -- and a cast_expr / try_cast_expr to Utf8 of an integer or Timestamp(ms) value (numtext.hpp A-NT1..A-NT7) counts as such a
+//         column: left(CAST(b_date_time AS Utf8), 10) is NEXMark q10's date; every other argument is a literal (a cast to the literal's own type may sit in front of it).  Refused by name at create /
 //         explain: a column or computed n / delim / chars, a NULL literal argument, a literal, CASE or other text expression as the value argument,
 //         a wrong argument count, deeper nesting, and the limits of A-SL2 / A-SL5;
 //   A-SL2 split_part(s, delim, n): field n (1-based) of s cut at every non-overlapping, leftmost occurrence of delim ('aaa' cut at 'aa': 'a' is field

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/plans/*.json: the physical plans of the five NEXMark target queries (and q7, q13) in the
 serde_json dialect of the reference's DataFusion fork, bids_above_average.json (a cross join against a global aggregate), and
-q22_url_dirs.json / person_email_domains.json (text slice functions as projected columns and as a GROUP BY key).
+q22_url_dirs.json / person_email_domains.json (text slice functions as projected columns and as a GROUP BY key), and q10_date_time_text.json (NEXMark
+q10's two formatted columns: slices of the bid time cast to Utf8).
 
 The fork's serialiser cannot be run here (no Rust toolchain), so the plans are AUTHORED from
   * the grammar of the checked-in fixtures flock/src/tests/data/plan/{simple_select,aggregate,join}.json
@@ -494,9 +495,20 @@ def person_email_domains():
     return proj(final, [(col("domain", 0), "domain"), (col("COUNT(UInt8(1))", 1), "COUNT(UInt8(1))")], fin)
 
 
+def q10_date_time_text():
+    """NEXMark q10 `SELECT auction, bidder, price, b_date_time, DATE_FORMAT(b_date_time, 'yyyy-MM-dd'), DATE_FORMAT(b_date_time, 'HH:mm') FROM bid`.
+    This dialect has no DATE_FORMAT: the two columns are slices of CAST(b_date_time AS Utf8) = 'YYYY-MM-DD HH:MM:SS[.mmm]' (numtext.hpp) --
+    left(.., 10) is the date, right(left(.., 16), 5) the hour and minute.  One projection over the scan."""
+    out = BID + [field("date", "Utf8", True), field("time", "Utf8", True)]
+    text = lambda: cast(col("b_date_time", 3), "Utf8")
+    date = scalar_fn("left", [text(), lit("Int64", 10)], "Utf8")
+    time = scalar_fn("right", [scalar_fn("left", [text(), lit("Int64", 16)], "Utf8"), lit("Int64", 5)], "Utf8")
+    return proj(rr(memory(BID, [0, 1, 2, 3], "bid")), [(col(f["name"], i), f["name"]) for i, f in enumerate(BID)] + [(date, "date"), (time, "time")], out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    for name, fn in (("q22_url_dirs", q22_url_dirs), ("person_email_domains", person_email_domains)):
+    for name, fn in (("q22_url_dirs", q22_url_dirs), ("person_email_domains", person_email_domains), ("q10_date_time_text", q10_date_time_text)):
         with open(os.path.join(OUT, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1, sort_keys=True)
             f.write("\n")
