@@ -30,8 +30,8 @@
 //         -- a projected column, a branch of a text CASE (one of the sixteen sources, identical casts once), the value argument of a slice function
 //         (textslice.hpp A-SL1), a GROUP BY / ORDER BY / DISTINCT key, the argument of COUNT / COUNT(DISTINCT).  Its bytes do not depend on batching
 //         or grid shape;
-//   Kept as before: a cast from Utf8 to a number, text inside a condition or under an operator (CAST(i AS Utf8) = '5'), LIKE / char_length /
-//   octet_length over a cast.
+//   Kept as before: text inside a condition or under an operator (CAST(i AS Utf8) = '5'), LIKE / char_length / octet_length over a cast.  (The way
+//   back, a cast from Utf8 to a number or a timestamp, is textnum.hpp.)
 #pragma once
 #include <cstdint>
 

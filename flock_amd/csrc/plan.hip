@@ -264,7 +264,7 @@ Peeled peel(const Node *n) {
     }
 }
 const Expr *uncast(const Expr *e) {
-    while (e && e->kind == EKind::Cast && (e->cast_to == ColType::I64 || e->cast_to == ColType::F64)) e = e->l.get();
+    while (e && e->kind == EKind::Cast && !e->text_num && (e->cast_to == ColType::I64 || e->cast_to == ColType::F64)) e = e->l.get();   // (a parse of text is no such cast)
     return e;
 }
 bool is_bin(const Expr *e, const char *op) { return e && e->kind == EKind::Bin && e->s == op; }
@@ -716,6 +716,15 @@ bool holds_func(const Expr *e) {
         if (holds_func(x.get())) return true;
     return false;
 }
+// ... or a cast of text to a number (textnum.hpp): `Filter(CAST(extra AS Int64) > 100)`
+bool holds_text_num(const Expr *e) {
+    if (!e) return false;
+    if (e->kind == EKind::Cast && e->text_num) return true;
+    if (holds_text_num(e->l.get()) || holds_text_num(e->r.get())) return true;
+    for (auto &x : e->list)
+        if (holds_text_num(x.get())) return true;
+    return false;
+}
 void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstream &os) {
     if (!e) { os << "?"; return; }
     static const std::pair<const char *, const char *> ops[] = {{"Eq", "="}, {"NotEq", "<>"}, {"Lt", "<"}, {"LtEq", "<="}, {"Gt", ">"}, {"GtEq", ">="}, {"And", "AND"}, {"Or", "OR"},
@@ -728,6 +737,13 @@ void pred_text(const Expr *e, const std::vector<Field> &schema, std::ostringstre
         case EKind::LitB: os << (e->i ? "TRUE" : "FALSE"); return;
         case EKind::LitNull: os << "NULL"; return;
         case EKind::Cast:
+            if (e->text_num) {   // text made a number (textnum.hpp): CAST(left(credit_card, 4) AS Int32)
+                static const char *types[] = {"Int32", "Int64", "UInt64", "Float64"};
+                os << (e->try_cast ? "TRY_CAST(" : "CAST(");
+                pred_text(e->l.get(), schema, os);
+                os << " AS " << (e->cast_ts ? "Timestamp(ms)" : types[(int)e->cast_to & 3]) << ")";
+                return;
+            }
             if (e->num_text) {   // a number made text (numtext.hpp): CAST(price AS Utf8)
                 os << (e->try_cast ? "TRY_CAST(" : "CAST(");
                 pred_text(e->l.get(), schema, os);
@@ -793,7 +809,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
     if (n->kind == NKind::Scan) os << "(" << pl->ir.leaves[(size_t)n->leaf].relation << ")";
     if (n->kind == NKind::Limit) os << "(" << n->limit << ")";
     if (n->kind == NKind::Union) os << "(" << n->in.size() << " inputs)";
-    if (n->kind == NKind::Filter && (holds_like(n->pred.get()) || holds_func(n->pred.get()))) {
+    if (n->kind == NKind::Filter && (holds_like(n->pred.get()) || holds_func(n->pred.get()) || holds_text_num(n->pred.get()))) {
         os << "(";
         pred_text(n->pred.get(), n->schema, os);
         os << ")";
@@ -802,7 +818,7 @@ void describe(const flockgpu_plan *pl, const Node *n, int depth, std::ostringstr
         bool any = false;
         for (size_t i = 0; i < n->proj.size(); ++i) {
             const bool text = n->proj[i].first->kind != EKind::Col && i < n->schema.size() && n->schema[i].type == ColType::UTF8;   // 'bid', CASE ... (textsel.hpp)
-            if (!holds_func(n->proj[i].first.get()) && !text) continue;
+            if (!holds_func(n->proj[i].first.get()) && !text && !holds_text_num(n->proj[i].first.get())) continue;
             os << (any ? ", " : "(") << n->proj[i].second << " = ";
             pred_text(n->proj[i].first.get(), n->in[0]->schema, os);
             any = true;
@@ -1145,6 +1161,13 @@ struct Exec {
     int slice_bufs = 0;   // ... and the (begin, end) pairs of text slice calls (textslice.hpp)
     int cast_bufs = 0;    // ... and the Utf8 columns of numbers cast to text (numtext.hpp)
     std::map<std::string, DevColumn> cast_cols;   // the casts of the projection at hand by their text: identical casts are computed once (exec_project clears it)
+    int parse_bufs = 0;   // ... and the numeric columns of text cast to numbers (textnum.hpp)
+    std::map<std::string, DevColumn> parse_cols;   // the parses of the node at hand by their text: identical casts are parsed once (cleared with cast_cols)
+    struct ParseFlag {
+        const uint32_t *h_fail;   // pinned: the parse kernel stores a 1 where a value does not parse (textnum.hip)
+        std::string what;
+    };
+    std::vector<ParseFlag> parse_pending;   // the cast_expr parses launched since the last wait of the evaluator
 
     // A relation the SQL scans twice (q5 and q7 read `bid` in both join inputs, q5_plan.fmt:6,13) has two MemoryExec leaves
     // but arrives as ONE source, which feed_data_sources hands to the first matching leaf (context.rs:273-300) -- the
@@ -1926,6 +1949,14 @@ struct Exec {
             case EKind::LitS:
                 return val_unsupported("a Utf8 literal inside a computed expression");
             case EKind::Cast: {
+                if (e->text_num) {   // text parsed to a number (textnum.hpp): a kernel of its own writes the column, the program reads it, its validity bytes with it
+                    DevColumn d;
+                    FG_TRY(parse_column(e, in, &d));
+                    *vt = (int)e->cast_to;
+                    *may_null = true;
+                    if (d.all_null) return b.push(ValOpKind::Null, (ValType)*vt, 0) ? FLOCKGPU_OK : val_full();
+                    return b.push(ValOpKind::Col, (ValType)*vt, 0, b.add_col(d)) ? FLOCKGPU_OK : val_full();
+                }
                 int from = -1;
                 FG_TRY(val_compile(e->l.get(), in, b, -1, &from, may_null));
                 if (from > 3 || (int)e->cast_to > 3) return val_unsupported("CAST between other than numeric types inside a computed expression");
@@ -2161,6 +2192,82 @@ struct Exec {
             default: return val_unsupported("CASE branches of different types");
         }
     }
+    // The casts of the node whose expressions are compiled next: `in` is its input table (a cast's key names columns by their position in it)
+    void begin_casts(Table *in, const std::vector<Field> &schema) {
+        cast_cols.clear();
+        parse_cols.clear();
+        for (size_t c = 0; c < in->cols.size() && c < schema.size(); ++c) in->cols[c].c.is_ts = schema[c].is_ts;   // (a cast of a timestamp to Utf8 reads it)
+    }
+    // After a wait of the evaluator on the stream: the failure words of the parse kernels queued in front of it (textnum.hpp A-TN3)
+    int parse_check() {
+        std::vector<ParseFlag> pending;
+        pending.swap(parse_pending);
+        for (auto &f : pending)
+            if (__atomic_load_n(f.h_fail, __ATOMIC_ACQUIRE)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: %s", f.what.c_str());
+        return FLOCKGPU_OK;
+    }
+    // CAST(x AS Int32 / Int64 / UInt64 / Timestamp(ms)) of text (textnum.hpp) as a numeric column: x is a Utf8 column of `in` (read in place), a chain of
+    // slice functions over one (the parse reads the slices' (begin, end) pairs), or any other text-valued expression, materialised first the way a
+    // projected text column is.  Identical casts of one node are one column.
+    int parse_column(const Expr *e, const Table &in, DevColumn *out) {
+        const std::string key = expr_text(e, std::vector<std::string>());   // (columns by their position in `in`)
+        auto hit = parse_cols.find(key);
+        if (hit != parse_cols.end()) {
+            *out = hit->second;
+            return FLOCKGPU_OK;
+        }
+        const Node *root = pl->ir.root.get();
+        const int slot = parse_bufs++;
+        const TextNumKind kind = e->cast_ts ? TextNumKind::TS : e->cast_to == ColType::I32 ? TextNumKind::I32 : e->cast_to == ColType::U64 ? TextNumKind::U64 : TextNumKind::I64;
+        // the operand: down the slice calls (and the casts of text to Utf8, which change nothing) to a column
+        std::vector<const Expr *> chain;
+        const Expr *c = e->l.get();
+        while ((c->kind == EKind::Func && fn_is_slice(c->fn) && !c->list.empty()) || (c->kind == EKind::Cast && c->cast_to == ColType::UTF8 && !c->num_text)) {
+            if (c->kind == EKind::Func) {
+                chain.push_back(c);
+                c = c->list[0].get();
+            } else {
+                c = c->l.get();
+            }
+        }
+        DevColumn col;
+        const int32_t *sb = nullptr, *se = nullptr;
+        if (c->kind == EKind::Col && in.cols[(size_t)c->col].c.type == ColType::UTF8) {
+            const TCol &tc = in.cols[(size_t)c->col];
+            if (!tc.c.all_null && (!tc.present || !tc.c.offsets)) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: expression column was not materialised");
+            col = tc.c;
+            if (!col.all_null)
+                for (size_t k = chain.size(); k-- > 0;) {   // innermost first, one launch each (text_compile's chain)
+                    const Expr *f = chain[k];
+                    SliceSpec spec;
+                    spec.fn = slice_fn_of(f->fn);
+                    spec.n = (int32_t)f->slice_n;
+                    spec.arg = f->slice_arg;
+                    int32_t *ob = nullptr, *oe = nullptr;
+                    FG_TRY(text_slice(ctx, node_key(pl, root, "slice", slice_bufs++).c_str(), col, in.rows, spec, sb, se, &ob, &oe));
+                    sb = ob;
+                    se = oe;
+                }
+        } else {   // a text CASE, a number cast to Utf8, a slice of those: the column a projection of it would give
+            TCol t;
+            FG_TRY(text_value(e->l.get(), root, "tn", slot, in, &t));
+            col = t.c;
+        }
+        if (col.all_null) {   // (every row NULL: nothing is launched)
+            *out = DevColumn{};
+            out->type = e->cast_to;
+            out->is_ts = e->cast_ts;
+            out->all_null = true;
+        } else {
+            const uint32_t *h_fail = nullptr;
+            FG_TRY(text_to_num(ctx, node_key(pl, root, "textnum", slot).c_str(), col, in.rows, kind, e->try_cast, sb, se, out, &h_fail));
+            static const char *types[] = {"Int32", "Int64", "UInt64", "Timestamp(ms)"};
+            if (!e->try_cast && in.rows > 0)
+                parse_pending.push_back({h_fail, std::string("cast_expr: a Utf8 value that is no ") + types[(int)kind] + " (CAST of Utf8 to " + types[(int)kind] + "; try_cast_expr gives NULL there)"});
+        }
+        parse_cols[key] = *out;
+        return FLOCKGPU_OK;
+    }
     // CAST(x AS Utf8) of a number or timestamp (numtext.hpp) as a Utf8 column: x is a column of `in`, or an expression the general evaluator computes
     // into a temporary column first.  Identical casts of one projection are one column.
     int cast_column(const Expr *e, const Table &in, DevColumn *out) {
@@ -2189,6 +2296,7 @@ struct Exec {
             FG_TRY(arena_get(ctx, node_key(pl, root, "castval", slot).c_str(), ((size_t)std::max<int64_t>(in.rows, 0) + 2) * 8, &vals));
             if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, root, "castvalv", slot).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 16, &vv));
             FG_TRY(valprog_to_column(ctx, node_key(pl, root, "castprog", slot).c_str(), vb.p, in.rows, (ColType)vt, vals, vv));
+            FG_TRY(parse_check());
             src.type = (ColType)vt;
             src.is_ts = expr_is_ts(x);
             src.values = vals;
@@ -2205,8 +2313,10 @@ struct Exec {
         return FLOCKGPU_OK;
     }
     // Column i of projection `n` as text: the selector through the evaluator (none for a bare literal or column), then the length and emit passes
-    int project_text(const Node *n, size_t i, const Table &in, TCol *o) {
-        const Expr *e = n->proj[i].first.get();
+    int project_text(const Node *n, size_t i, const Table &in, TCol *o) { return text_value(n->proj[i].first.get(), n, "", (int)i, in, o); }
+    // ... of any text-valued expression `e` over `in`; the buffers are named after node `n`, `pre` and `i`
+    int text_value(const Expr *e, const Node *n, const char *pre, int i, const Table &in, TCol *o) {
+        const std::string k_val = std::string(pre) + "val", k_valv = std::string(pre) + "valv", k_prog = std::string(pre) + "vprog", k_text = std::string(pre) + "text";
         ValBuilder vb;
         TextTable tt;
         bool may_null = false;
@@ -2233,14 +2343,15 @@ struct Exec {
         if (!bare) {
             void *vals = nullptr;
             uint8_t *vv = nullptr;
-            FG_TRY(arena_get(ctx, node_key(pl, n, "val", (int)i).c_str(), ((size_t)rows + 2) * 8, &vals));
-            if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, "valv", (int)i).c_str(), (size_t)rows + 16, &vv));
-            FG_TRY(valprog_to_column(ctx, node_key(pl, n, "vprog", (int)i).c_str(), vb.p, in.rows, ColType::I32, vals, vv));
+            FG_TRY(arena_get(ctx, node_key(pl, n, k_val.c_str(), i).c_str(), ((size_t)rows + 2) * 8, &vals));
+            if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, k_valv.c_str(), i).c_str(), (size_t)rows + 16, &vv));
+            FG_TRY(valprog_to_column(ctx, node_key(pl, n, k_prog.c_str(), i).c_str(), vb.p, in.rows, ColType::I32, vals, vv));
+            FG_TRY(parse_check());
             sel = static_cast<const int32_t *>(vals);
             sel_valid = vv;
         }
         DevColumn out;
-        FG_TRY(text_select(ctx, node_key(pl, n, "text", (int)i).c_str(), tt.s, sel, sel_valid, in.rows, &out));
+        FG_TRY(text_select(ctx, node_key(pl, n, k_text.c_str(), i).c_str(), tt.s, sel, sel_valid, in.rows, &out));
         *o = dev_col(ColType::UTF8, out.values, out.offsets, out.bytes);
         o->c.valid = out.valid;
         o->c.nullable = true;
@@ -2252,6 +2363,7 @@ struct Exec {
     // which writes the same flag words + wave counts
     int compile_filter(const Node *n, Table *in, PredBuilder &b, ValBuilder &vb, bool *general) {
         FG_TRY(exec(n->in[0].get(), in));
+        begin_casts(in, n->in[0]->schema);
         words_node = n;
         words_used = 0;
         col_rows = in->rows;
@@ -2271,7 +2383,10 @@ struct Exec {
         ValBuilder vb;
         bool general = false;
         FG_TRY(compile_filter(n, in, b, vb, &general));
-        if (general) return valprog_to_rows(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, rows, n_out);
+        if (general) {
+            FG_TRY(valprog_to_rows(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, rows, n_out));
+            return parse_check();
+        }
         return pred_to_rows(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, rows, n_out);
     }
     // The filter's predicate pass alone: flag words and wave counts over its INPUT table (pred.hpp pred_to_flags), for an ungrouped aggregate that
@@ -2281,7 +2396,10 @@ struct Exec {
         ValBuilder vb;
         bool general = false;
         FG_TRY(compile_filter(n, in, b, vb, &general));
-        if (general) return valprog_to_flags(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, flags, counts, tiles);
+        if (general) {
+            FG_TRY(valprog_to_flags(ctx, node_key(pl, n, "vprog").c_str(), vb.p, in->rows, flags, counts, tiles));
+            return parse_check();
+        }
         return pred_to_flags(ctx, node_key(pl, n, "sel").c_str(), b.p, in->rows, flags, counts, tiles);
     }
 
@@ -2465,8 +2583,7 @@ struct Exec {
     int exec_project(const Node *n, Table *t) {
         Table in;
         FG_TRY(exec(n->in[0].get(), &in));
-        cast_cols.clear();   // (the casts of numbers to Utf8 of THIS projection's input, numtext.hpp)
-        for (size_t c = 0; c < in.cols.size() && c < n->in[0]->schema.size(); ++c) in.cols[c].c.is_ts = n->in[0]->schema[c].is_ts;   // (such a cast reads it)
+        begin_casts(&in, n->in[0]->schema);   // (the casts of THIS projection's input: numbers to Utf8, numtext.hpp; text to numbers, textnum.hpp)
         t->rows = in.rows;
         t->cols.assign(n->schema.size(), TCol{});
         for (size_t i = 0; i < n->proj.size(); ++i) {
@@ -2500,6 +2617,7 @@ struct Exec {
                 FG_TRY(arena_get(ctx, node_key(pl, n, "val", (int)i).c_str(), ((size_t)std::max<int64_t>(in.rows, 0) + 2) * 8, &vals));
                 if (may_null) FG_TRY(arena_get_t(ctx, node_key(pl, n, "valv", (int)i).c_str(), (size_t)std::max<int64_t>(in.rows, 0) + 16, &vv));
                 FG_TRY(valprog_to_column(ctx, node_key(pl, n, "vprog", (int)i).c_str(), vb.p, in.rows, n->schema[i].type, vals, vv));
+                FG_TRY(parse_check());
                 o = dev_col(n->schema[i].type, vals, nullptr, 0, n->schema[i].is_ts);
                 o.c.valid = vv;
                 o.c.nullable = true;

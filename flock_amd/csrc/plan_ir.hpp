@@ -24,6 +24,8 @@
 // too: `split_part(url, '/', 4)`, `btrim(split_part(description, ',', 1))`.  Every other text-producing function stays refused.
 // CAST(x AS Utf8) / TRY_CAST(x AS Utf8) of an Int32 / Int64 / UInt64 / Timestamp(ms) column or numeric expression (numtext.hpp A-NT1..A-NT7) is text-valued
 // as well and counts as a Utf8 column wherever one is taken: `left(CAST(b_date_time AS Utf8), 10)` is NEXMark q10's date.
+// CAST(s AS Int32 / Int64 / UInt64 / Timestamp(ms)) / TRY_CAST of a text-valued expression (textnum.hpp A-TN1..A-TN6) is the way back: a numeric value of
+// the general evaluator, `CAST(left(credit_card, 4) AS Int32)`.  Float64, Boolean, another Timestamp unit and a literal operand are refused by name.
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -66,6 +68,7 @@ struct Expr {
     bool cast_ts = false;                      // Cast: the target is Timestamp(Millisecond) (Int64 storage)
     bool try_cast = false;                     // Cast: try_cast_expr (a value that does not fit becomes NULL instead of failing the call)
     bool num_text = false;                     // Cast to Utf8 of something that is not text: the number / timestamp is FORMATTED (numtext.hpp); false: Utf8 to Utf8, nothing happens
+    bool text_num = false;                     // Cast of a text-valued expression to Int32 / Int64 / UInt64 / Timestamp(ms): the text is PARSED (textnum.hpp)
     std::string lit_kind;                      // literals: the ScalarValue variant ("Int32", "Float64", ...; empty: a bare JSON value)
     Fn fn = Fn::Abs;                           // Func: the function (`s`: its canonical name; `i`: the cal::Unit of date_trunc / date_part, else -1; `list`: the value
                                                // arguments -- one, none for now(); the unit literal is folded into `i`)
@@ -470,10 +473,33 @@ struct Builder {
             x->kind = EKind::Cast;
             x->try_cast = t == "try_cast_expr";
             bool ts = false;
-            if (!parse_type(e->get("cast_type"), &x->cast_to, &ts)) { fail("cast to an unsupported type"); return nullptr; }
+            if (!parse_type(e->get("cast_type"), &x->cast_to, &ts)) {
+                // of text, by name (textnum.hpp A-TN5); everything else as before
+                const std::string before = err;
+                const JValue *ct = e->get("cast_type");
+                auto op = expr(e->get("expr"), schema);
+                const bool text = op && err == before && expr_static_type(op.get(), schema) == 4;
+                err = before;
+                if (text && ct && ct->kind == JValue::Str && ct->str == "Boolean") fail(t + ": CAST of a Utf8 value to Boolean (no Boolean columns at this boundary)");
+                else if (text && ct && ct->kind == JValue::Obj && ct->obj.size() == 1 && ct->obj[0].first == "Timestamp")
+                    fail(t + ": CAST of a Utf8 value to a Timestamp of another unit than Millisecond (the text is parsed to Timestamp(Millisecond, None) alone)");
+                else fail("cast to an unsupported type");
+                return nullptr;
+            }
             x->cast_ts = ts;
             x->l = expr(e->get("expr"), schema);
             if (!x->l) return nullptr;
+            if ((int)x->cast_to <= 3 && expr_static_type(x->l.get(), schema) == 4) {   // text to a number or a timestamp: the value is parsed (textnum.hpp)
+                const Expr *v = x->l.get();
+                while (v->kind == EKind::Cast && v->cast_to == ColType::UTF8 && !v->num_text) v = v->l.get();
+                if (v->kind == EKind::LitS || v->kind == EKind::LitNull) { fail(t + ": CAST of a Utf8 literal to a number (a literal operand: write the number itself)"); return nullptr; }
+                if (x->cast_to == ColType::F64) {
+                    fail(t + ": CAST of a Utf8 value to Float64 (no correctly rounded decimal-to-double conversion on the device)");
+                    return nullptr;
+                }
+                if (v->kind != EKind::Col && (!check_case_types(v, schema) || !check_text(v, schema))) return nullptr;   // a text-valued expression within textsel.hpp's limits
+                x->text_num = true;
+            }
             // to Utf8 from anything but text (a NULL literal takes the type): the value is formatted (numtext.hpp)
             const int from = expr_static_type(x->l.get(), schema);   // (-1: untyped NULLs alone, or an untyped integer literal)
             x->num_text = x->cast_to == ColType::UTF8 && !ts && from != 4 && (from != -1 || x->l->kind == EKind::LitI);

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "numtext.hpp"
+#include "textnum.hpp"
 #include "relops.hpp"
 
 namespace flockgpu {
@@ -124,5 +125,13 @@ int text_select(flockgpu_ctx *ctx, const char *name, const TextSources &srcs, co
 // a NULL; a timestamp outside the years 0000..9999 gives a NULL when `try_cast`, else the call fails naming `who` (the expression's tag).  Offsets, bytes
 // and validity live in the ctx arena under `name`.  One host wait (the byte total, and with it the flag word).
 int num_to_text(flockgpu_ctx *ctx, const char *name, const DevColumn &in, int64_t rows, bool try_cast, const char *who, DevColumn *out);
+
+// CAST(`col` AS Int32 / Int64 / UInt64 / Timestamp(ms)) of a Utf8 column (textnum.hip; textnum.hpp A-TN1..A-TN6), or -- `range_begin` / `range_end` given --
+// of the per-row byte ranges of a text slice of it (textslice.hpp).  `out`: a nullable column of the target type, values and validity bytes in the ctx
+// arena under `name`; a NULL row gives a NULL, a value that does not parse a NULL as well and -- unless `try_cast` -- a 1 in *h_fail, a word of pinned
+// host memory the kernel stores to.  Launches only: the caller reads *h_fail after its next wait on the stream (the evaluator's, for its own failure
+// word).  Zero rows launch nothing.
+int text_to_num(flockgpu_ctx *ctx, const char *name, const DevColumn &col, int64_t rows, TextNumKind kind, bool try_cast, const int32_t *range_begin, const int32_t *range_end,
+                DevColumn *out, const uint32_t **h_fail);
 
 }  // namespace flockgpu

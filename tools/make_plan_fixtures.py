@@ -2,7 +2,7 @@
 """Writes tests/golden/plans/*.json: the physical plans of the five NEXMark target queries (and q7, q13) in the
 serde_json dialect of the reference's DataFusion fork, bids_above_average.json (a cross join against a global aggregate), and
 q22_url_dirs.json / person_email_domains.json (text slice functions as projected columns and as a GROUP BY key), and q10_date_time_text.json (NEXMark
-q10's two formatted columns: slices of the bid time cast to Utf8).
+q10's two formatted columns: slices of the bid time cast to Utf8), and person_card_prefix.json (a text slice cast to Int32 as a GROUP BY key).
 
 The fork's serialiser cannot be run here (no Rust toolchain), so the plans are AUTHORED from
   * the grammar of the checked-in fixtures flock/src/tests/data/plan/{simple_select,aggregate,join}.json
@@ -506,9 +506,23 @@ def q10_date_time_text():
     return proj(rr(memory(BID, [0, 1, 2, 3], "bid")), [(col(f["name"], i), f["name"]) for i, f in enumerate(BID)] + [(date, "date"), (time, "time")], out)
 
 
+def person_card_prefix():
+    """`SELECT CAST(left(credit_card, 4) AS Int32) AS prefix, COUNT(*) FROM person GROUP BY 1`: the two-phase aggregate whose key is a text slice parsed
+    to a number (textnum.hpp)."""
+    inp = [field("credit_card", "Utf8")]
+    key = cast(scalar_fn("left", [col("credit_card", 0), lit("Int64", 4)], "Utf8"), "Int32")
+    part = [field("prefix", "Int32", True), field("COUNT(UInt8(1))[count]", "UInt64", True)]
+    fin = [field("prefix", "Int32", True), field("COUNT(UInt8(1))", "UInt64", True)]
+    cnt = [{"aggregate_expr": "count", "name": "COUNT(UInt8(1))", "data_type": "UInt64", "nullable": True, "expr": lit("UInt8", 1)}]
+    partial = agg(rr(memory(PERSON, [3], "person")), "Partial", [(key, "prefix")], cnt, inp, part)
+    final = agg(coalesce(hashp(partial, [col("prefix", 0)])), "FinalPartitioned", [(col("prefix", 0), "prefix")], cnt, inp, fin)
+    return proj(final, [(col("prefix", 0), "prefix"), (col("COUNT(UInt8(1))", 1), "COUNT(UInt8(1))")], fin)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    for name, fn in (("q22_url_dirs", q22_url_dirs), ("person_email_domains", person_email_domains), ("q10_date_time_text", q10_date_time_text)):
+    for name, fn in (("q22_url_dirs", q22_url_dirs), ("person_email_domains", person_email_domains), ("q10_date_time_text", q10_date_time_text),
+                     ("person_card_prefix", person_card_prefix)):
         with open(os.path.join(OUT, name + ".json"), "w") as f:
             json.dump(fn(), f, indent=1, sort_keys=True)
             f.write("\n")
