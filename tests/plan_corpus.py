@@ -6,9 +6,13 @@ both zeros in one column; Float64 literals are multiples of 1 / 4 or divisors wh
 arguments are integers below 2^31 in magnitude, so every sum stays inside 64 bits and inside Float64's 53, and AVG is one correctly rounded division --
 except in `group_wide`, whose column `w` (SUM only, Int64 near 2^62) wraps on purpose.  Integer arithmetic wraps as generic_ops.eval_typed says.
 Zero divisors, INT_MIN / -1 and casts that do not fit are kept out (divisor literals are never 0 or -1, Float64 values fit Int32) except in `errors`.
+The text casts are exact by nature (digits in, digits out); under cast_expr every timestamp lies in the years 0000 to 9999 and every text parses
+(text_numbers(valid=True) keeps only what parse_text_ref.parse_one takes); what does not stands under try_cast_expr alone -- except in `errors_text`;
+SUM / MIN / MAX over parsed values take texts of magnitude below 2^31 (`parse_text` case 4), the rule of the other sums.
 
-Order.  `ordered` is True only when the root is a sort or a limit over a sort; such a sort carries the row-unique column `id` (or a GROUP BY's key tuple)
-as its last key.  Everything else is compared as a multiset; no limit sits over an unsorted input.
+Order.  `ordered` is True only when the root is a sort or a limit over a sort, or a union over scans, filters and projections (ordered_union: the
+rows of input 0 in their order, then input 1's; a filter keeps its input's order).  Such a sort carries the row-unique column `id` (or a GROUP BY's
+key tuple, or every column of its input) as its last key.  Everything else is compared as a multiset; no limit sits over an unsorted input.
 
 Shapes.  Row counts come from SIZES (the flag tile and kDenseTile 8192, the sort tile 4096) plus one case of 20 011 and one of 32 769 rows per stratum
 (case 4 of seed 0 / seed 1); join build sides from both sides of kTinyBuild = 4096.  Every stratum is DIRECTED by the case number i: case i takes the
@@ -16,7 +20,8 @@ i-th way through the node it is about (the docstring of each recipe says which),
 
 Columns of a table with prefix `p`: p_k Int32 and p_l Int64 (keys in the case's style), p_g Int32 (a small dense key), p_u UInt64 (either side of 2^63),
 p_t Timestamp(ms) (either side of 1970), p_f Float64, p_s / p_s2 Utf8, p_v Int64 and p_i Int32 (values below 2^20 / of any size), p_id Int64 (the row's
-number, never NULL).  Every other column is NULL with a share drawn from NULL_SHARES."""
+number, never NULL).  Every other column is NULL with a share drawn from NULL_SHARES.  The strata of the text casts put directed values into these
+columns (number_pools) and add the Utf8 columns of PARSE_COLS (parse_table)."""
 import collections
 import random
 
@@ -33,7 +38,7 @@ WORDS = ["", "7", "07", "a", "ab", "abc", "prefix_8", "prefix_8x", "sixteen_byte
          "z" * 40, "w" * 70, "w" * 69 + "v", "été", "€", "\U0001F600", "aé€\U0001F600", "a/b/c", " pad ", "a//b", "xx/é/yy"]
 CASES_PER_SEED = 6
 STRATA = ["filter_project", "text", "group_narrow", "group_composite", "group_wide", "distinct_count", "global_agg", "join_inner", "join_semi_anti",
-          "sort_limit", "window", "cross", "mixed", "errors"]
+          "sort_limit", "window", "cross", "mixed", "errors", "union", "cast_text", "parse_text", "errors_text"]
 
 # The kernels every (stratum, seed) must run, by name as profile_read() gives them; `sort_emit_kernel` is a template with an instance per digit
 # width whose profile name may carry the width: names are matched by PREFIX.
@@ -56,6 +61,10 @@ MUST_RUN = {
     "cross": ("cross_repeat_kernel", "cross_tile_kernel"),
     "mixed": (),
     "errors": (),
+    "union": ("union_fixed_kernel", "union_valid_kernel", "union_bytes_kernel", "union_offsets_kernel"),
+    "cast_text": ("numtext_len_kernel", "numtext_emit_kernel"),
+    "parse_text": ("textnum_parse_kernel",),
+    "errors_text": (),
 }
 
 
@@ -951,9 +960,348 @@ def r_errors(seed, i, rnd, r):
     return _finish(node, [t], r, rnd, False, "n=%d at=%d" % (n, at))
 
 
+# ------------------------------------------------------------------ UNION ALL and the text casts (their own generators: the recipes above stay as they were)
+def union(inputs):
+    """UNION ALL of Nodes whose columns agree in type by position; the names are input 0's"""
+    first = inputs[0]
+    assert all([t for _, t in x.cols] == [t for _, t in first.cols] for x in inputs), [x.cols for x in inputs]
+    return Node({"execution_plan": "union_exec", "inputs": [x.plan for x in inputs], "schema": schema(first.cols)}, first.cols)
+
+
+def ordered_union(plan):
+    """a union at the root over scans, filters and projections (unions of such included) has a defined row order: A-U2, and a filter keeps its
+    input's order"""
+    def plain(node):
+        kind = node.get("execution_plan")
+        if kind == "memory_exec":
+            return True
+        if kind == "union_exec":
+            return all(plain(x) for x in node["inputs"])
+        return kind in ("filter_exec", "projection_exec", "coalesce_batches_exec") and plain(node["input"])
+    return plan.get("execution_plan") == "union_exec" and all(plain(x) for x in plan["inputs"])
+
+
+UNION_ROWS = [0, 1, 3, 5, 7, 4097]
+
+
+def _renamed(inp, names):
+    return proj(inp, [(inp.c(old), new, t) for (old, t), new in zip(inp.cols, names)])
+
+
+def _id_mod(node, name, m, j):
+    return binop(binop(node.c(name), "Modulo", lit("Int64", m)), "Eq", lit("Int64", j))
+
+
+def r_union(seed, i, rnd, r):
+    """case 0: two plain scans of two relations, every column, one relation without a NULL anywhere, row counts of UNION_ROWS (seams at every
+    misalignment); case 1: two filters over ONE relation that read different columns of it; case 2: three to five inputs -- one empty, one all NULL,
+    one a union itself -- under a sort and a limit; case 3: 17 to 33 small inputs under a GROUP BY on (Int32, Utf8); case 4: a union as one side of an
+    Inner / Semi / Anti join; case 5: UNION DISTINCT (a key-only aggregate) over a projection with a literal and an id as text beside a join or an
+    aggregate.  Cases 0 and 1 are ordered: the root is a union over scans, filters and projections."""
+    a, b = scan(table_cols("a")), scan(table_cols("b"))
+    if i == 0:
+        na, nb = rnd.choice(UNION_ROWS), rnd.choice(UNION_ROWS)
+        plain = rnd.choice(["a", "b"])
+        every = {c: 0.0 for c, _ in COLS}
+        ta = make_table("a", na, r, rnd, nulls=every if plain == "a" else {"s": 0.3, "k": 0.02})
+        tb = make_table("b", nb, r, rnd, nulls=every if plain == "b" else {"s": 0.3, "k": 0.02})
+        return _finish(union([a, b]), [ta, tb], r, rnd, True, "rows=%d+%d no NULL in %s" % (na, nb, plain))
+    if i == 1:
+        n = size(seed, i, rnd, SIZES[1:])
+        ta = make_table("a", n, r, rnd, nulls={"k": 0.02, "i": 0.3, "s": 0.3, "s2": 0.0})
+        x = Exprs(a, "a", rnd)
+        one = proj(filt(a, x.simple(1)), [(a.c("a_id"), "id", "Int64"), (a.c("a_k"), "n", "Int32"), (a.c("a_s"), "w", "Utf8")])
+        src = keep(a, ["a_v", "a_i", "a_s2"])
+        two = filt(src, binop(src.c("a_i"), rnd.choice(["Lt", "GtEq"]), lit("Int32", rnd.choice([0, 2**30]))))
+        return _finish(union([one, two]), [ta], r, rnd, True, "n=%d one relation twice" % n)
+    if i == 2:
+        n = size(seed, i, rnd)
+        count = rnd.randint(3, 5)
+        names = ["k", "s", "u", "n"]
+        tables, parts = [], []
+        roles = ["empty", "null", "nested"] + ["plain"] * (count - 3)
+        rnd.shuffle(roles)
+        for j, role in enumerate(roles):
+            p = "abcdefg"[len(tables)]
+            rows = 0 if role == "empty" else n if j == 0 or role == "nested" else rnd.choice([1, 65, 700])
+            t = make_table(p, rows, r, rnd, nulls={"k": 1.0, "s": 1.0, "u": 1.0, "l": 1.0} if role == "null" else {"k": 0.02, "s": 0.3, "u": 0.0})
+            s = scan(table_cols(p))
+            node = _renamed(keep(s, [p + "_k", p + "_s", p + "_u", p + ("_l" if role == "null" else "_id")]), names)
+            if role == "nested":
+                q = "abcdefg"[len(tables) + 1]
+                t2 = make_table(q, rnd.choice([1, 7, 300]), r, rnd)
+                s2 = scan(table_cols(q))
+                other = _renamed(keep(s2, [q + "_g", q + "_s2", q + "_u", q + "_v"]), names)
+                swap = rnd.random() < 0.5
+                node = union([other, node] if swap else [node, other])
+                tables += [t2, t] if swap else [t, t2]                # (tables in leaf order)
+            else:
+                tables.append(t)
+            parts.append(node)
+        u = union(parts)
+        keys = [(c, rnd.random() < 0.5, rnd.random() < 0.5) for c in rnd.sample(names, 4)]      # every column is a key: only identical rows tie
+        node = limit(sort(u, keys), [5000, 50, 100_000, 1][seed % 4])
+        return _finish(node, tables, r, rnd, True, "n=%d inputs=%s" % (n, roles))
+    if i == 3:
+        n = size(seed, i, rnd, [65, 700, 4097])
+        count, m = rnd.randint(17, 33), rnd.choice([3, 7])
+        ta = make_table("a", n, r, rnd, style="dense", card=rnd.choice([7, 300]), nulls={"s2": 0.3, "v": 0.02}, key_nulls=0.02)
+        tb = make_table("b", rnd.choice([1, 65, 300]), r, rnd, style="dense", card=7, key_nulls=0.3)
+        parts = []
+        for j in range(count):
+            if j % 8 == 5:
+                parts.append(keep(b, ["b_k", "b_s2", "b_v", "b_id"]))                # a plain input among the row lists
+            else:
+                src = keep(a, ["a_k", "a_s2", "a_v", "a_id"])
+                parts.append(filt(src, _id_mod(src, "a_id", m, j % m)))
+        node = aggregate(union(parts), ["a_k", "a_s2"], [("count", None), ("sum", "a_v"), ("max", "a_id")])
+        return _finish(node, [ta, tb], r, rnd, False, "n=%d inputs=%d modulus=%d" % (n, count, m))
+    if i == 4:
+        n = size(seed, i, rnd, [700, 4097, 8193])
+        nb = rnd.choice(BUILD_SIZES)
+        jt = ["Inner", "Semi", "Anti", "Inner"][seed % 4]
+        ta = make_table("a", n, r, rnd, style="dense", card=nb, key_nulls=0.02, nulls={"s2": 0.3})
+        tb = make_table("b", rnd.choice([1, 300, 4097]), r, rnd, style="dense", card=nb, key_nulls=0.3)
+        tc = make_table("c", nb, r, rnd, key_nulls=0.0)
+        tc["c_k"] = with_nulls([int(v) - nb // 4 for v in r.permutation(nb)], rnd.choice([0.0, 0.02]), r)
+        first = keep(a, ["a_k", "a_id", "a_s2", "a_v"])
+        u = union([filt(first, _id_mod(first, "a_id", 2, 0)), keep(b, ["b_k", "b_id", "b_s2", "b_v"]), filt(first, _id_mod(first, "a_id", 2, 1))])
+        build = keep(scan(table_cols("c")), ["c_k", "c_s", "c_id"])
+        if jt == "Inner":
+            node, tables = join("Inner", build, u, [("c_k", "a_k")]), [tc, ta, tb]
+        else:
+            node, tables = join(jt, u, build, [("a_k", "c_k")]), [ta, tb, tc]
+        if rnd.random() < 0.4:
+            node = aggregate(node, ["a_s2"], [("count", None), ("sum", "a_v")])
+        return _finish(node, tables, r, rnd, False, "n=%d build=%d %s" % (n, nb, jt))
+    n = size(seed, i, rnd, SIZES[1:])
+    ta = make_table("a", n, r, rnd, groups=37, nulls={"g": 0.02})
+    tb = make_table("b", rnd.choice([65, 700, 4097]), r, rnd, style="dense", card=50, key_nulls=0.02, nulls={"s2": 0.3})
+    one = proj(a, [(lit("Utf8", rnd.choice(["bid", "", "sixteen_bytes_pfx"])), "kind", "Utf8"), (cast(a.c("a_g"), "Utf8"), "who", "Utf8")])
+    tables = [ta, tb]
+    if rnd.random() < 0.5:
+        two = aggregate(b, ["b_s2", "b_s"], [])
+    else:
+        tc = make_table("c", 300, r, rnd)
+        tc["c_k"] = [int(v) - 5 for v in r.permutation(300)]
+        j = join("Inner", keep(scan(table_cols("c")), ["c_k", "c_s2"]), keep(b, ["b_k", "b_s"]), [("c_k", "b_k")])
+        two = keep(j, ["c_s2", "b_s"])
+        tables = [ta, tc, tb]
+    node = aggregate(union([one, two]), ["kind", "who"], [])
+    return _finish(node, tables, r, rnd, False, "n=%d second=%s" % (n, two.plan["execution_plan"]))
+
+
+TS_MIN = -62167219200000                     # 0000-01-01 00:00:00.000
+TS_MAX = 253402300799999                     # 9999-12-31 23:59:59.999
+_DAY = 86_400_000
+
+
+def number_pools():
+    """the directed values of the cast to text: integers of every digit count from 1 to 20 with both ends of every type and UInt64 at and above
+    2^63; timestamps either side of 1970 with and without a millisecond part, the first and last millisecond of the years 0000 and 9999"""
+    i32 = [0, -2**31, 2**31 - 1] + [s * (10**d + e) for d in range(10) for s in (1, -1) for e in (0, -1)]
+    i64 = [-2**63, 2**63 - 1] + [s * (10**d + e) for d in range(19) for s in (1, -1) for e in (0, -1)]
+    u64 = [0, 2**63 - 1, 2**63, 2**63 + 1, 2**64 - 1, 10**19, 10**19 - 1] + [10**d + e for d in range(20) for e in (0, -1)]
+    ts = [0, 1, -1, 999, 1000, -1000, -999, -1001, 86_399_999, -86_400_000, 1_436_951_287_123, 1_436_951_287_000, -1_436_951_287_123, -1_436_951_287_000,
+          TS_MIN, TS_MIN + 1, TS_MIN + 366 * _DAY - 1, TS_MIN + 366 * _DAY, TS_MAX, TS_MAX - 999, TS_MAX + 1 - 365 * _DAY, TS_MAX - 365 * _DAY]
+    return {"i": [v for v in i32 if -2**31 <= v < 2**31], "l": i64, "u": [v for v in u64 if v >= 0], "t": ts}
+
+
+def pooled(pool, n, r, share):
+    """n values: the pool in order first (as far as n reaches), then draws from it; NULL with `share`"""
+    vals = [pool[k] if k < len(pool) else pool[int(x)] for k, x in enumerate(r.integers(0, len(pool), n))]
+    return with_nulls(vals, share, r)
+
+
+def r_cast_text(seed, i, rnd, r):
+    """CAST(number | timestamp AS Utf8).  case 0: projected casts of the Int32, Int64, UInt64 and Timestamp columns over number_pools(); case 1:
+    try_cast_expr of timestamps, some outside the years 0000 to 9999 (NULL); case 2: the cast of a computed expression, as a branch of a text CASE
+    and under left / right / split_part / trims; case 3: as a GROUP BY key and as the argument of COUNT and COUNT(DISTINCT); case 4: as an ORDER BY
+    key with a_id as the last key; case 5: beside a Utf8 column in a union branch and under a filter, below a join"""
+    n = size(seed, i, rnd, [700, 1025, 4097, 8193] if i < 2 else [65, 700, 4097, 8193] if i < 4 else SIZES)      # (cases 0 and 1: every value of a pool)
+    a = scan(table_cols("a"))
+    t = make_table("a", n, r, rnd, style="dense", card=300, groups=37, nulls={"g": 0.02, "k": 0.02, "v": 0.02, "f": 0.02, "s": 0.3, "s2": 0.02})
+    pools = number_pools()
+    share = rnd.choice([0.02, 0.3])
+    if i in (0, 1):
+        for c in "ilut":
+            t["a_" + c] = pooled(pools[c] + ([TS_MAX + 1, TS_MIN - 1, 2**62, -2**63, 2**63 - 1] if (c == "t" and i == 1) else []), n, r, share)
+    x = Exprs(a, "a", rnd)
+    tables, ordered = [t], False
+    if i == 0:
+        node = proj(a, [(x.c("id"), "a_id", "Int64")] + [(cast(x.c(c), "Utf8"), "x" + c, "Utf8") for c in "ilut"])
+    elif i == 1:
+        node = proj(a, [(x.c("id"), "a_id", "Int64"), (cast(x.c("t"), "Utf8", safe=True), "xt", "Utf8"), (cast(x.c("u"), "Utf8", safe=True), "xu", "Utf8")])
+    elif i == 2:
+        day = fn("left", "Utf8", cast(x.c("t"), "Utf8"), lit("Int64", 10))
+        es = [cast(x.nl(x.int64(2), "v"), "Utf8"), cast(x.nl(x.int32(2), "i"), "Utf8"), cast(x.ts(1), "Utf8"),
+              case_([(x.plain_boolean(), cast(x.c("l"), "Utf8")), (x.plain_boolean(), x.c("s2"))], rnd.choice([None, lit("Utf8", "none"), cast(x.c("g"), "Utf8")])),
+              day, fn("right", "Utf8", fn("left", "Utf8", cast(x.c("t"), "Utf8"), lit("Int64", 16)), lit("Int64", 5)),
+              fn("split_part", "Utf8", cast(x.c("t"), "Utf8"), lit("Utf8", rnd.choice(["-", ":", " "])), lit("Int64", rnd.randint(1, 3))),
+              fn(rnd.choice(["ltrim", "btrim"]), "Utf8", cast(x.c("i"), "Utf8"), lit("Utf8", "-1")), fn("rtrim", "Utf8", cast(x.c("v"), "Utf8"), lit("Utf8", "0"))]
+        picked = es[:3] + rnd.sample(es[3:], 3)
+        node = proj(a, [(x.c("id"), "a_id", "Int64")] + [(e, "x%d" % k, "Utf8") for k, e in enumerate(picked)])
+    elif i == 3:
+        key = rnd.choice(["g", "k", "t"])
+        if key == "t":
+            t["a_t"] = [None if v is None else v // 3_600_000 * 3_600_000 for v in t["a_t"]]
+        below = proj(a, [(cast(x.c(key), "Utf8"), "x0", "Utf8"), (cast(x.c("k"), "Utf8"), "x1", "Utf8"), (x.c("v"), "a_v", "Int64")])
+        node = aggregate(below, ["x0"], [("count", "x1"), ("dc", "x1"), ("count", None), ("sum", "a_v")])
+    elif i == 4:
+        key = rnd.choice(["v", "g", "t", "u"])
+        below = proj(a, [(x.c("id"), "a_id", "Int64"), (cast(x.c(key), "Utf8"), "x0", "Utf8")])
+        node = sort(below, [("x0", rnd.random() < 0.5, rnd.random() < 0.5), ("a_id", False, False)])
+        ordered = True
+    else:
+        b = scan(table_cols("b"))
+        tb = make_table("b", rnd.choice([1, 300, 4097]), r, rnd, style="dense", card=300, key_nulls=0.02)
+        nc = rnd.choice([300, 4097])
+        tc = make_table("c", nc, r, rnd)
+        tc["c_k"] = [int(v) - 100 for v in r.permutation(nc)]
+        one = proj(a, [(x.c("k"), "k", "Int32"), (cast(x.c("id"), "Utf8"), "who", "Utf8"), (x.c("s"), "w", "Utf8")])
+        below = proj(b, [(b.c("b_k"), "b_k", "Int32"), (cast(b.c("b_l"), "Utf8"), "xl", "Utf8"), (b.c("b_s2"), "b_s2", "Utf8")])
+        two = filt(below, binop(below.c("b_k"), "GtEq", lit("Int32", rnd.choice([-50, 0, 40]))))
+        node = join("Inner", keep(scan(table_cols("c")), ["c_k", "c_s"]), union([one, two]), [("c_k", "k")])
+        tables = [tc, t, tb]
+    return _finish(node, tables, r, rnd, ordered, "n=%d" % n)
+
+
+def text_numbers(target, n, rnd, valid=True, bound=None):
+    """n texts for a cast to `target` ('Int32' | 'Int64' | 'UInt64' | 'Timestamp'), deterministic in `rnd` (a random.Random), built on
+    parse_text_ref's own generators.  valid: every value parses -- zeros in front beyond 24 bytes, a leading '+', '-0' for the signed types and both
+    limits among them; otherwise parse_text_ref.EDGES first, then values and their mutations.  bound: integers of magnitude below it only."""
+    import parse_text_ref as ptref
+    make = ptref._ts_text if target == "Timestamp" else ptref._int_text
+    out = []
+    if not valid:
+        out = list(ptref.EDGES)[:n]
+    elif target != "Timestamp" and bound is None:
+        lo, hi = ptref.LIMITS[target]
+        out = [str(lo), str(hi), "0" * 30 + "7", "+5", "+" + str(hi), "0", "007"] + (["-0", "-" + "0" * 25 + "12", "-000"] if lo < 0 else ["0" * 24 + str(hi)])
+        out = out[:n]
+    while len(out) < n:
+        if bound is not None:
+            v = rnd.randrange(-bound + 1, bound)
+            s = rnd.choice(["%d", "%d", "%d", "%+d", "%05d", "%030d"]) % v
+        else:
+            s = make(rnd)
+        if not valid and rnd.random() < 0.5:
+            s = ptref._mutate(rnd, s)
+        if valid and ptref.parse_one(s, target) is None:
+            continue
+        out.append(s)
+    return out
+
+
+PARSE_COLS = [("a_n", "Utf8"), ("a_m", "Utf8"), ("a_p", "Utf8"), ("a_d", "Utf8"), ("a_q", "Utf8")]
+
+
+def parse_table(n, r, rnd, valid=True, bound=None):
+    """table_cols('a') and PARSE_COLS: a_n / a_m / a_p texts for Int32 / Int64 / UInt64, a_d for Timestamp, a_q `key=<Int32>/<Int64>` for the slices"""
+    t = make_table("a", n, r, rnd, groups=5, nulls={"g": 0.02, "k": 0.02, "i": 0.02, "f": 0.02, "t": 0.02, "l": 0.02, "u": 0.02})
+    share = rnd.choice([0.0, 0.02, 0.3])
+    for name, target in (("a_n", "Int32"), ("a_m", "Int64"), ("a_p", "UInt64"), ("a_d", "Timestamp")):
+        t[name] = with_nulls(text_numbers(target, n, rnd, valid, bound if target != "Timestamp" else None), share, r)
+    first, second = text_numbers("Int32", n, rnd, True, bound), text_numbers("Int64", n, rnd, True, bound)
+    t["a_q"] = with_nulls(["%s=%s/%s" % (WORDS[k % 7], p, q) for k, (p, q) in enumerate(zip(first, second))], share, r)
+    return scan(table_cols("a") + PARSE_COLS), t
+
+
+_PARSE_TARGETS = [("a_n", "Int32"), ("a_m", "Int64"), ("a_p", "UInt64"), ("a_d", "ts")]
+
+
+def r_parse_text(seed, i, rnd, r):
+    """CAST(text AS Int32 / Int64 / UInt64 / Timestamp).  case 0: cast_expr of columns of valid values to each integer target; case 1:
+    try_cast_expr over the edge table and mutated values, to all four targets; case 2: the cast of split_part / left chains (the parse reads (begin,
+    end) pairs in place); case 3: the cast of a text CASE and of a number cast to Utf8 (the materialised route); case 4: the cast in a filter predicate
+    and as the argument of SUM, MIN and MAX, magnitudes below 2^31; case 5: through a projection, as a join key against an Int64 id (Inner and Semi)
+    and as a GROUP BY or ORDER BY key"""
+    n = size(seed, i, rnd, [700, 1025, 4097, 8193] if i == 1 else [65, 700, 1025, 4097, 8193] if i < 4 else SIZES[2:])      # (case 1: the whole edge table)
+    a, t = parse_table(n, r, rnd, valid=i != 1, bound=2**31 if i == 4 else None)
+    c = a.c
+    tables, ordered = [t], False
+    ident = (c("a_id"), "a_id", "Int64")
+    if i == 0:
+        node = proj(a, [ident] + [(cast(c(name), ty), "v" + name[-1], ty) for name, ty in _PARSE_TARGETS[:3]] + [(cast(c("a_n"), "Int64"), "wide", "Int64")])
+    elif i == 1:
+        node = proj(a, [ident] + [(cast(c(name), ty, safe=True), "v%d%s" % (k, name[-1]), ty) for k, (_, ty) in enumerate(_PARSE_TARGETS) for name in ("a_n", "a_d")])
+    elif i == 2:
+        tail = fn("split_part", "Utf8", c("a_q"), lit("Utf8", "/"), lit("Int64", 2))
+        mid = fn("split_part", "Utf8", fn("split_part", "Utf8", c("a_q"), lit("Utf8", "="), lit("Int64", 2)), lit("Utf8", "/"), lit("Int64", 1))
+        node = proj(a, [ident, (cast(tail, "Int64"), "tail", "Int64"), (cast(mid, "Int32"), "mid", "Int32"),
+                        (cast(fn("left", "Utf8", c("a_d"), lit("Int64", 10)), "ts"), "day", "ts"),
+                        (cast(fn("right", "Utf8", tail, lit("Int64", rnd.choice([1, 3, 30]))), "UInt64", safe=True), "last", "UInt64"),
+                        (cast(fn("left", "Utf8", c("a_m"), lit("Int64", rnd.choice([1, 2, 9]))), "Int32", safe=True), "head", "Int32")])
+    elif i == 3:
+        x = Exprs(a, "a", rnd)
+        label = case_([(x.plain_boolean(), c("a_n")), (x.plain_boolean(), lit("Utf8", rnd.choice(["77", "+0", "none"])))], rnd.choice([None, c("a_m"), cast(c("a_k"), "Utf8")]))
+        node = proj(a, [ident, (cast(fn("left", "Utf8", cast(c("a_t"), "Utf8"), lit("Int64", 10)), "ts"), "day", "ts"),
+                        (cast(cast(c("a_t"), "Utf8"), "ts"), "again", "ts"), (cast(label, "Int64", safe=True), "label", "Int64"),
+                        (cast(cast(c("a_l"), "Utf8"), "Int64"), "l", "Int64"), (cast(cast(c("a_u"), "Utf8"), "Int64", safe=True), "u", "Int64"),
+                        (cast(cast(c("a_u"), "Utf8"), "UInt64"), "uu", "UInt64")])
+    elif i == 4:
+        e = cast(c("a_m"), "Int64")
+        inp = filt(a, binop(e, rnd.choice(["Gt", "LtEq"]), lit("Int64", rnd.choice([100, 0, -2**20]))))
+        keys = rnd.choice([[], ["a_g"]])
+        node = aggregate(inp, keys, [("sum", (e, "Int64")), ("min", (cast(c("a_n"), "Int32"), "Int32")), ("max", (e, "Int64")), ("count", None)])
+    else:
+        nc = rnd.choice([300, 4097])
+        t["a_n"] = with_nulls(text_numbers("Int64", n, rnd, True, nc + 50), rnd.choice([0.0, 0.02]), r)
+        tc = make_table("c", nc, r, rnd)
+        jt = "Inner" if seed % 2 == 0 else "Semi"
+        below = proj(a, [(cast(c("a_n"), "Int64"), "key", "Int64"), ident, (c("a_s2"), "a_s2", "Utf8")])
+        right = keep(scan(table_cols("c")), ["c_id", "c_s"])
+        if jt == "Inner":
+            node, tables = join("Inner", right, below, [("c_id", "key")]), [tc, t]
+        else:
+            node, tables = join("Semi", below, right, [("key", "c_id")]), [t, tc]
+        if rnd.random() < 0.5:
+            node = aggregate(node, ["key"], [("count", None)])
+        else:
+            node = sort(node, [("key", rnd.random() < 0.5, rnd.random() < 0.5), ("a_id", False, False)])
+            ordered = True
+    return _finish(node, tables, r, rnd, ordered, "n=%d" % n)
+
+
+def r_errors_text(seed, i, rnd, r):
+    """r_errors for the text casts, exactly ONE failing row at 0, n - 1, a random position or either side of a workgroup (1024) or tile (8192)
+    boundary: 0 a Timestamp one millisecond outside the years 0000 to 9999 to Utf8, 1 '2147483648' to Int32, 2 a trailing blank to Int64, 3 '-0'
+    to UInt64, 4 '2015-02-29' to Timestamp, 5 a bad text under a filter's predicate"""
+    n = size(seed, i, rnd, [1, 65, 700, 1025, 8192, 8193])
+    a, t = parse_table(n, r, rnd)
+    at = rnd.choice([0, n - 1, rnd.randrange(n)] + ([1023, 1024] if n > 1024 else []) + ([8191, 8192] if n > 8192 else []))
+    c = a.c
+    if i == 0:
+        t["a_t"][at] = rnd.choice([TS_MAX + 1, TS_MIN - 1])
+        e, ty = cast(c("a_t"), "Utf8"), "Utf8"
+    elif i == 1:
+        t["a_n"][at] = "2147483648"
+        e, ty = cast(c("a_n"), "Int32"), "Int32"
+    elif i == 2:
+        t["a_m"][at] = (t["a_m"][at] or "5") + " "
+        e, ty = cast(c("a_m"), "Int64"), "Int64"
+    elif i == 3:
+        t["a_p"][at] = "-0"
+        e, ty = cast(c("a_p"), "UInt64"), "UInt64"
+    elif i == 4:
+        t["a_d"][at] = "2015-02-29"
+        e, ty = cast(c("a_d"), "ts"), "ts"
+    else:
+        t["a_m"][at] = rnd.choice(["", "1e3", "5a", "--5", "9223372036854775808"])
+        e, ty = cast(c("a_m"), "Int64"), "Int64"
+    if i == 5:
+        node = filt(a, binop(e, "Gt", lit("Int64", 0)))
+    else:
+        node = proj(a, [(c("a_id"), "a_id", "Int64"), (e, "e", ty)])
+    return _finish(node, [t], r, rnd, False, "n=%d at=%d" % (n, at))
+
+
+ERROR_STRATA = ("errors", "errors_text")
+
 _RECIPES = {"filter_project": r_filter_project, "text": r_text, "group_narrow": r_group_narrow, "group_composite": r_group_composite, "group_wide": r_group_wide,
             "distinct_count": r_distinct_count, "global_agg": r_global_agg, "join_inner": r_join_inner, "join_semi_anti": r_join_semi_anti,
-            "sort_limit": r_sort_limit, "window": r_window, "cross": r_cross, "mixed": r_mixed, "errors": r_errors}
+            "sort_limit": r_sort_limit, "window": r_window, "cross": r_cross, "mixed": r_mixed, "errors": r_errors,
+            "union": r_union, "cast_text": r_cast_text, "parse_text": r_parse_text, "errors_text": r_errors_text}
 
 
 def case(stratum, seed, i):

@@ -4,7 +4,8 @@ Python values -- int, float, str, None for NULL -- row at a time.  It is the ref
 What it is made of: oracle.generic_ops (the typed expression rules: wrap-around, checked casts, the failing divisions; the stable multi-key sort; the
 inner join's build / probe; limit), scalar_fn_ref (every scalar function), text_slice_ref (the slice functions), test_plan_like.reference_like (LIKE),
 wide_group_ref.finish (COUNT / SUM / MIN / MAX / AVG of one group: SUM wraps in 64 bits, AVG is one division), count_distinct_ref (distinct counts),
-semi_anti_ref (Semi / Anti), cross_join_ref (the pair order).  The tree walk, the typing of expressions that carry a function, and the window frame are
+semi_anti_ref (Semi / Anti), cross_join_ref (the pair order), union_ref (UNION ALL), cast_text_ref (integers and timestamps as text), parse_text_ref (text as
+integers and timestamps).  The tree walk, the typing of expressions that carry a function, and the window frame are
 restated here; test_plan_differential.py pins the result to the reference's transcribed vectors and to every one of those modules on its own table.
 
 Where the parts disagree: generic_ops.hash_aggregate_exec adds SUM without wrapping and AVG as a running Float64 sum, wide_group_ref wraps SUM in 64 bits
@@ -18,11 +19,14 @@ import datetime as _dtm
 import functools
 import re
 
+import cast_text_ref as ctref
 import count_distinct_ref as dref
 import cross_join_ref as xref
+import parse_text_ref as ptref
 import scalar_fn_ref as sref
 import semi_anti_ref as saref
 import text_slice_ref as tsl
+import union_ref as uref
 import wide_group_ref as wref
 from oracle import generic_ops as g
 from oracle.generic_ops import ExprError
@@ -56,6 +60,15 @@ QUIRKS = {
     "date_trunc_towards_zero_before_1970": "filter_project",
     "week_starts_sunday": "filter_project",
     "cross_pair_order_swapped": "cross",                   # pair (i, j) at output row j * L + i
+    "union_inputs_reversed": "union",                      # the last input's rows come first
+    "union_is_distinct": "union",                          # the union drops duplicate rows (UNION, not UNION ALL)
+    "ts_text_always_prints_millis": "cast_text",           # a whole second prints its `.000`
+    "ts_text_truncates_towards_zero_before_1970": "cast_text",   # -1 prints as 1970-01-01 00:00:00.001
+    "uint64_text_as_signed": "cast_text",                  # a UInt64 at or above 2^63 prints as the Int64 of its bits
+    "parse_refuses_leading_plus": "parse_text",            # `+5` does not parse (pyarrow's rule)
+    "parse_trims_blanks": "parse_text",                    # blanks around a value are skipped
+    "parse_minus_zero_is_uint64_zero": "parse_text",       # `-0` is the UInt64 0
+    "try_cast_bad_text_is_zero": "parse_text",             # try_cast_expr of a text that does not parse gives 0, not NULL
 }
 
 _NEUTRAL = ("coalesce_batches_exec", "repartition_exec", "coalesce_partitions_exec", "merge_exec")
@@ -63,6 +76,8 @@ _ARITH = ("Plus", "Minus", "Multiply", "Divide", "Modulo")
 _CMP = ("Eq", "NotEq", "Lt", "LtEq", "Gt", "GtEq")
 _INT = g._INT_RANGE
 _UNIT_MS = {"second": 1000, "minute": 60_000, "hour": 3_600_000, "day": 86_400_000}
+_NUM_AS_TEXT = ("Int32", "Int64", "UInt64")              # and Timestamp(ms): the operands of a cast to Utf8
+_MINUS_ZERO = re.compile(r"-0+")
 
 
 class Rel:
@@ -203,6 +218,41 @@ class _Interp:
                 return sref._ms(d - _dtm.timedelta(days=(d.weekday() + 1) % 7))
         return sref.call(name, args)
 
+    def num_text(self, v, src, safe):
+        """CAST(v AS Utf8) of one non-NULL integer or Timestamp(ms): cast_text_ref.int_text / ts_text"""
+        q = self.q
+        if not _is_ts(src):
+            if src == "UInt64" and v >= 2**63 and "uint64_text_as_signed" in q:
+                v -= 2**64
+            return ctref.int_text([v])[0]
+        try:
+            if "ts_text_truncates_towards_zero_before_1970" in q and v < 0 and v % 1000:
+                whole = ctref.ts_text([(v // 1000 + 1) * 1000], safe)[0]
+                return whole if whole is None else "%s.%03d" % (whole, -v % 1000)
+            text = ctref.ts_text([v], safe)[0]
+        except ctref.CastRangeError as err:
+            raise ExprError(str(err))
+        if text is not None and "ts_text_always_prints_millis" in q and v % 1000 == 0:
+            text += ".000"
+        return text
+
+    def text_num(self, s, target, safe):
+        """CAST(s AS target) of one non-NULL text: parse_text_ref.parse_one"""
+        q = self.q
+        if "parse_trims_blanks" in q:
+            s = s.strip(" ")
+        v = ptref.parse_one(s, target)
+        if "parse_refuses_leading_plus" in q and s.startswith("+"):
+            v = None
+        if "parse_minus_zero_is_uint64_zero" in q and target == "UInt64" and _MINUS_ZERO.fullmatch(s):
+            v = 0
+        if v is None:
+            if not safe:
+                raise ExprError("%r is no %s" % (s, target))
+            if "try_cast_bad_text_is_zero" in q:
+                return 0
+        return v
+
     def ev(self, e, row, types, want=None):
         """generic_ops.eval_typed, with scalar functions, LIKE, text values and the quirks.  Every branch of eval_typed is kept in its words."""
         q = self.q
@@ -217,10 +267,19 @@ class _Interp:
         if t in ("cast_expr", "try_cast_expr"):
             v = self.ev(e["expr"], row, types)
             ty = g._type_name(e["cast_type"])
+            src = full_type(e["expr"], types)
+            literal = e["expr"]["physical_expr"] == "literal"
             if ty == "Utf8":
-                if _st(e["expr"], types) != "Utf8":
-                    raise NotImplementedError("a cast of a number to Utf8")
-                return v
+                if src == "Utf8":
+                    return v
+                if literal or not (src == TS or src in _NUM_AS_TEXT):
+                    raise NotImplementedError("a cast of %s to Utf8" % ("a literal" if literal else src))
+                return None if v is None else self.num_text(v, src, t == "try_cast_expr")
+            if src == "Utf8":
+                target = "Timestamp" if e["cast_type"] == TS else e["cast_type"]
+                if literal or target not in ptref.TARGETS:
+                    raise NotImplementedError("a cast of %s to %s" % ("a text literal" if literal else "text", e["cast_type"]))
+                return None if v is None else self.text_num(v, target, t == "try_cast_expr")
             if ty not in _INT and ty != "Float64":
                 raise NotImplementedError("cast to " + str(ty))
             return None if v is None else g._cast(v, ty, t == "try_cast_expr")
@@ -405,6 +464,21 @@ class _Interp:
             rows = xref.cross_rows(l.rows(), r.rows())
         cols = list(zip(*rows)) if rows else [()] * (len(l.names) + len(r.names))
         return Rel(l.names + r.names, l.types + r.types, cols)
+
+    def n_union_exec(self, node):
+        rels = [self.run(x) for x in node["inputs"]]
+        if not rels:
+            raise NotImplementedError("a union_exec without inputs")
+        for k, r in enumerate(rels[1:], 1):
+            if r.types != rels[0].types:
+                raise NotImplementedError("union_exec: input %d gives %s, input 0 gives %s" % (k, r.types, rels[0].types))
+        if "union_inputs_reversed" in self.q:
+            rels = rels[::-1]
+        rows = uref.union_rows([r.rows() for r in rels])
+        if "union_is_distinct" in self.q:
+            rows = list(dict.fromkeys(rows))
+        first = rels[-1 if "union_inputs_reversed" in self.q else 0]
+        return Rel(first.names, first.types, list(zip(*rows)) if rows else [()] * len(first.names))
 
     def n_hash_join_exec(self, node):
         jt = node.get("join_type")
@@ -657,7 +731,7 @@ class _Interp:
 
 
 def leaf_schemas(plan):
-    """the field lists of the plan's leaves in leaf order -- depth first, `input` / `left` before `right` --, leaves of one schema once: they are ONE
+    """the field lists of the plan's leaves in leaf order -- depth first, `input` / `left` before `right`, a union's `inputs` in their order --, leaves of one schema once: they are ONE
     relation (the library matches sources to leaves by their column names)"""
     out, seen = [], set()
 
@@ -670,6 +744,8 @@ def leaf_schemas(plan):
         for k in ("input", "left", "right"):
             if isinstance(node.get(k), dict):
                 walk(node[k])
+        for x in node.get("inputs") or ():
+            walk(x)
     walk(plan)
     return out
 

@@ -1,6 +1,7 @@
 """Random plans over the generic operators against a CPU interpreter: tests/plan_corpus.py draws plans inside the claimed dialect, tests/plan_interp.py
 evaluates them row at a time, the GPU tests run them through ExecutionContext + collect -- whole and cut into batches -- and compare EXACTLY: schema
-names and Arrow types, rows as a sequence under a sort and as a multiset otherwise, Float64 by its bits, Timestamp as Int64, Utf8 as bytes.
+names and Arrow types, rows as a sequence under a sort (or a root union over scans, filters and projections) and as a multiset otherwise, Float64 by
+its bits, Timestamp as Int64, Utf8 as bytes.
 
 The CPU tests hold the interpreter to what is already pinned (the reference's transcribed vectors, every *_ref module on its own table), every case
 of the corpus to `explain` (no refusal) and to the interpreter (no NotImplementedError), and every quirk of plan_interp.QUIRKS to at least one case of
@@ -187,6 +188,108 @@ def test_interpreter_equals_the_like_reference_and_the_window_reference():
     assert [row[len(entries) - 1] for row in rows] == [1 + i - max(j for j in range(i + 1) if j == 0 or p[j] != p[j - 1]) for i in range(n)]
 
 
+def test_interpreter_equals_union_ref():
+    import test_plan_union as U
+    import union_ref as ref
+    shape = (5, 0, 7, 3, 4)                                                                      # an empty input; NULLs in the odd inputs
+    tabs = U._tables(shape, 3, True)
+    scans = [U._scan(U._sfx(U.COLS, k)) for k in range(len(shape))]
+    want = ref.union_rows([ref.rows_of(t, [c for c, _ in U._sfx(U.COLS, k)]) for k, t in enumerate(tabs)])
+    assert any(v is None for r in want for v in r) and len(want) == sum(shape)
+    for plan in (U._union(scans), U._union([scans[0], U._union([scans[1], U._union(scans[2:4])]), scans[4]])):      # flat, and unions under unions
+        names, types, rows = run_plan(plan, tabs)
+        assert names == U.NAMES and types == [U._dt(t) for _, t in U.COLS] and _norm(rows) == _norm(want)
+    # one relation under two branches is ONE table (A-U7); a filter keeps its input's order
+    bid = U._bids(3000, 20)
+    names, _, rows = run_plan(json.load(open(os.path.join(PLANS, "bids_two_ranges.json"))), [bid])
+    high = [a for a, p in zip(bid["auction"], bid["price"]) if p > 9_000_000]
+    late = [b for b, t in zip(bid["bidder"], bid["b_date_time"]) if t > 1_436_918_400_000 + 50_000]
+    assert names == ["id"] and [r[0] for r in rows] == ref.union_table([{"id": high}, {"bidder": late}])["id"] and high and not late
+    for quirk in ("union_inputs_reversed", "union_is_distinct"):
+        assert run_plan(U._union([scans[0], scans[0], scans[3]]), [tabs[0], tabs[3]], frozenset([quirk]))[2] != run_plan(U._union([scans[0], scans[0], scans[3]]), [tabs[0], tabs[3]])[2]
+
+
+def test_interpreter_equals_cast_text_ref():
+    import cast_text_ref as ref
+    import test_plan_cast_text as K
+    t = K.shared_table(300)
+    q10 = [K.left(ref.cast_utf8(K.c("t")), 10), K.right(K.left(ref.cast_utf8(K.c("t")), 16), 5)]
+    label = K.case([(K.mod("k", 3, 0), ref.cast_utf8(K.c("l"))), (K.mod("k", 3, 1), K.c("s"))], K.lit_utf8("none"))
+    exprs = [ref.cast_utf8(K.c(n)) for n in "ilut"] + [ref.cast_utf8(K.c("w"), try_cast=True), ref.cast_utf8(K.binary(K.c("i"), "Multiply", K.lit("Int32", 2)))] + q10 + [label]
+    _, types, rows = run_plan(K.projection([(e, "x%d" % k) for k, e in enumerate(exprs)]), [t])
+    assert set(types) == {"Utf8"}
+    for k, e in enumerate(exprs):
+        assert [r[k] for r in rows] == ref.eval_text(e, t, K.TYPES), k
+    assert any(r[4] is None and w is not None for r, w in zip(rows, t["w"]))                      # try_cast_expr beyond the years: NULL
+    beyond = K.projection([(ref.cast_utf8(K.c("w")), "x")])                                      # cast_expr of the same column fails the call
+    with pytest.raises(ref.CastRangeError):
+        ref.eval_text(ref.cast_utf8(K.c("w")), t, K.TYPES)
+    with pytest.raises(g.ExprError):
+        run_plan(beyond, [t])
+
+
+def test_interpreter_equals_parse_text_ref():
+    import parse_text_ref as ref
+    import test_plan_parse_text as P
+    vals = ref.corpus()
+    t = {"k": list(range(len(vals))), "s": [None if k % 50 == 7 else v for k, v in enumerate(vals)], "d": [None] * len(vals), "i": [0] * len(vals)}
+    targets = [(ty, ref.TS if ty == "Timestamp" else ty) for ty in ref.TARGETS]
+    plan = P.projection([(ref.cast_to(P.c("s"), ty, try_cast=True), "x" + ty, full) for ty, full in targets])
+    _, types, rows = run_plan(plan, [t])
+    assert types == [full for _, full in targets]
+    for k, (ty, _) in enumerate(targets):
+        want = ref.parse(t["s"], ty, try_cast=True)
+        assert [r[k] for r in rows] == want and 100 < sum(v is not None for v in want) < len(vals) - 100, ty
+        with pytest.raises(ref.ParseError):
+            ref.parse(t["s"], ty)
+        with pytest.raises(g.ExprError):                                                         # cast_expr: one value that does not parse fails the call
+            run_plan(P.projection([(ref.cast_to(P.c("s"), ty), "x", targets[k][1])]), [t])
+        good = dict(t, s=[v if w is not None else None for v, w in zip(t["s"], want)])
+        assert [r[0] for r in run_plan(P.projection([(ref.cast_to(P.c("s"), ty), "x", targets[k][1])]), [good])[2]] == ref.parse(good["s"], ty) == want
+
+
+def _relation(fields, n, **cols):
+    """a table for a fixture's leaf: the named columns, every other field NULL"""
+    return {f["name"]: list(cols.get(f["name"], [None] * n)) for f in fields}
+
+
+def test_interpreter_gives_what_the_three_fixtures_tests_expect():
+    import cast_text_ref as cref
+    import test_plan_union as U
+    r = np.random.default_rng(5)
+    # person_activity.json as tests/test_plan_union.py expects it: a count per (person, kind)
+    plan = json.load(open(os.path.join(PLANS, "person_activity.json")))
+    fa, fb = pi.leaf_schemas(plan)
+    na, nb = 700, 1300
+    seller = [int(x) for x in r.integers(0, 40, na)]
+    bid = U._bids(nb, 6)
+    bid["bidder"] = [b % 60 for b in bid["bidder"]]
+    names, _, rows = run_plan(plan, [_relation(fa, na, a_date_time=[1_436_918_400_000 + 11 * k for k in range(na)], seller=seller), _relation(fb, nb, **bid)])
+    want = {}
+    for p, kind in [(s, "auction") for s in seller] + [(b, "bid") for b in bid["bidder"]]:
+        want[(p, kind)] = want.get((p, kind), 0) + 1
+    assert names == ["person", "kind", "COUNT(UInt8(1))"] and sorted(rows) == sorted((p, k, n) for (p, k), n in want.items()) and len(want) == 100
+    # q10_date_time_text.json as tests/test_plan_cast_text.py expects it: the date and the time of day out of the timestamp's text
+    plan = json.load(open(os.path.join(PLANS, "q10_date_time_text.json")))
+    n = 2000
+    ms = [1_699_920_000_000 + int(d) * 86_400_000 + int(x) for d, x in zip(r.integers(0, 3, n), r.integers(-2000, 2001, n))]      # within two seconds of a midnight
+    bid = {"auction": list(range(n)), "bidder": [j % 13 for j in range(n)], "price": [(j * 37) % 10_000 for j in range(n)], "b_date_time": ms}
+    names, _, rows = run_plan(plan, [bid])
+    text = cref.ts_text(ms)
+    assert names == ["auction", "bidder", "price", "b_date_time", "date", "time"]
+    assert rows == [(bid["auction"][j], bid["bidder"][j], bid["price"][j], ms[j], text[j][:10], text[j][11:16]) for j in range(n)]
+    assert {"23:59", "00:00"} <= {row[5] for row in rows} and {len(s) for s in text} == {19, 23}
+    # person_card_prefix.json as tests/test_plan_parse_text.py expects it: a count per four-digit prefix
+    plan = json.load(open(os.path.join(PLANS, "person_card_prefix.json")))
+    n = 3000
+    cards = ["%04d %04d %04d %04d" % ((j * j) % 50 * 199, j % 10_000, 0, j % 3) for j in range(n)]
+    names, types, rows = run_plan(plan, [_relation(pi.leaf_schemas(plan)[0], n, credit_card=cards)])
+    want = {}
+    for s in cards:
+        want[int(s[:4])] = want.get(int(s[:4]), 0) + 1
+    assert names == ["prefix", "COUNT(UInt8(1))"] and types[0] == "Int32" and sorted(rows) == sorted(want.items()) and len(want) > 20
+
+
 # ------------------------------------------------------------------ CPU 2: every case explains and evaluates
 def _leaf(node):
     while node["execution_plan"] != "memory_exec":
@@ -195,13 +298,14 @@ def _leaf(node):
 
 
 def test_the_corpus_has_its_floors():
-    assert len(pc.STRATA) >= 14 and len(SEEDS) >= 4 and pc.CASES_PER_SEED >= 6 and set(pc.MUST_RUN) == set(pc.STRATA) == set(pc._RECIPES)
+    assert len(pc.STRATA) >= 18 and len(SEEDS) >= 4 and pc.CASES_PER_SEED >= 6 and set(pc.MUST_RUN) == set(pc.STRATA) == set(pc._RECIPES)
     assert set(pi.QUIRKS.values()) <= set(pc.STRATA)
     for s in pc.STRATA:
         sizes = [max(len(next(iter(t.values()))) for t in _case(s, seed, i).tables) for seed in SEEDS for i in range(pc.CASES_PER_SEED)]
         assert sizes.count(20_011) == 1 and sizes.count(32_769) == 1 and max(sizes) == 32_769, (s, sizes)
     # the edges the recipes promise: four PARTITION BY and four ORDER BY columns in every seed; an empty right side under Semi and under Anti; a join
-    # build key on every row and on half of them; a leaf with a projection of its own; a filter over an aggregate
+    # build key on every row and on half of them; a leaf with a projection of its own; a filter over an aggregate; a union of more than 16 inputs, of
+    # one relation twice, of an input without validity beside one with it; a parse through a slice and through a materialised text
     empty = set()
     for seed in SEEDS:
         w = _case("window", seed, 3).plan
@@ -214,23 +318,85 @@ def test_the_corpus_has_its_floors():
         assert any(len(f["projection"]) < len(f["schema"]["fields"]) for i in range(pc.CASES_PER_SEED)
                    for f in [_leaf(_case("sort_limit", seed, i).plan)]), seed
         assert _case("group_narrow", seed, 3).plan["input"]["execution_plan"] == "filter_exec"
+        assert any(len(u["inputs"]) > 16 for u in _nodes(_case("union", seed, 3).plan, "union_exec")), seed
+        c = _case("union", seed, 1)
+        assert c.plan["execution_plan"] == "union_exec" and len(c.tables) == 1 and len(pi.leaf_schemas(c.plan)) == 1, seed
+        assert len(_nodes(c.plan, "memory_exec")) == 2 and c.ordered
+        c = _case("union", seed, 0)
+        plain = [all(v is not None for col in t.values() for v in col) for t in c.tables]
+        assert c.plan["execution_plan"] == "union_exec" and sorted(plain) == [False, True] and c.ordered, (seed, plain)
+        assert {len(next(iter(t.values()))) for t in c.tables} <= set(pc.UNION_ROWS)
+        roles = [[_text_kind(e["expr"]) for e in _exprs(_case("parse_text", seed, i).plan) if _parses_text(e)] for i in (2, 3)]
+        assert "slice" in roles[0] and "materialised" in roles[1], (seed, roles)
     assert empty == {"Semi", "Anti"}
+    # every directed value of the casts to text, and every entry of parse_text_ref's edge table, stands non-NULL in some seed
+    for c, pool in pc.number_pools().items():
+        assert set(pool) <= {v for seed in SEEDS for v in _case("cast_text", seed, 0).tables[0]["a_" + c]}, c
+    assert {len(str(v).lstrip("-")) for v in pc.number_pools()["u"]} == set(range(1, 21))
+    import parse_text_ref as ptref
+    for name in ("a_n", "a_d"):
+        assert set(ptref.EDGES) <= {v for seed in SEEDS for v in _case("parse_text", seed, 1).tables[0][name]}, name
     notes = " ".join(_case(s, seed, 2).note for s in ("join_inner", "join_semi_anti") for seed in SEEDS)
     assert "(hot)" in notes and "(constant)" in notes and "(repeat)" in notes
 
 
+def _nodes(plan, kind):
+    """every node of `kind` in the plan, depth first"""
+    out = [plan] if plan.get("execution_plan") == kind else []
+    for k in ("input", "left", "right"):
+        if isinstance(plan.get(k), dict):
+            out += _nodes(plan[k], kind)
+    for x in plan.get("inputs") or ():
+        out += _nodes(x, kind)
+    return out
+
+
+def _exprs(x):
+    """every expression object anywhere in a plan"""
+    if isinstance(x, dict):
+        if "physical_expr" in x:
+            yield x
+        for v in x.values():
+            yield from _exprs(v)
+    elif isinstance(x, list):
+        for v in x:
+            yield from _exprs(v)
+
+
+def _parses_text(e):
+    return e["physical_expr"] in ("cast_expr", "try_cast_expr") and e["cast_type"] != "Utf8" and _text_kind(e["expr"]) is not None
+
+
+def _text_kind(e):
+    """'column' | 'slice' (a chain of slice functions over a column: read in place) | 'materialised' (a text CASE, a number cast to Utf8, a slice of
+    those) | None for what is no text"""
+    t = e["physical_expr"]
+    if t == "column":
+        return "column" if e["name"] in dict(pc.PARSE_COLS) or e["name"].endswith(("_s", "_s2")) else None
+    if t == "scalar_function_expr" and e["name"] in pi.tsl.SLICE_FNS:
+        below = _text_kind(e["args"][0])
+        return "slice" if below in ("column", "slice") else below
+    if t == "case_expr":
+        return "materialised" if any(_text_kind(th) for _, th in e["when_then_expr"]) else None
+    if t in ("cast_expr", "try_cast_expr") and e["cast_type"] == "Utf8":
+        return "materialised"
+    return None
+
+
 @pytest.mark.parametrize("stratum", pc.STRATA)
 def test_every_case_explains_and_evaluates(stratum):
-    """zero refusals from flockgpu_plan_explain, no NotImplementedError from the interpreter; an `errors` case raises ExprError and nothing else does;
-    the schema explain derives for the root is the interpreter's"""
+    """zero refusals from flockgpu_plan_explain, no NotImplementedError from the interpreter; a case of an error stratum raises ExprError and nothing
+    else does; `ordered` exactly where the root fixes the row order (a sort, a limit over one, a union over scans, filters and projections); the
+    schema explain derives for the root is the interpreter's"""
     from flock_amd.runtime import explain
     for seed in SEEDS:
         for i in range(pc.CASES_PER_SEED):
             c = _case(stratum, seed, i)
             text = explain(c.plan)                                # raises FlockGpuError on a refusal
             want = _want(stratum, seed, i)
-            assert isinstance(want, g.ExprError) == (stratum == "errors"), (stratum, seed, i, c.note, want if isinstance(want, Exception) else "")
-            assert c.ordered == (c.plan["execution_plan"] == "sort_exec" or (c.plan["execution_plan"] == "global_limit_exec" and c.plan["input"]["execution_plan"] == "sort_exec"))
+            assert isinstance(want, g.ExprError) == (stratum in pc.ERROR_STRATA), (stratum, seed, i, c.note, want if isinstance(want, Exception) else "")
+            assert c.ordered == (c.plan["execution_plan"] == "sort_exec" or (c.plan["execution_plan"] == "global_limit_exec" and c.plan["input"]["execution_plan"] == "sort_exec")
+                                 or pc.ordered_union(c.plan))
             for cut, t in zip(c.batch_cuts, c.tables):
                 n = len(next(iter(t.values())))
                 assert cut[0] == 0 and cut[-1] == n and cut == sorted(cut) and any(a == b for a, b in zip(cut, cut[1:])), (stratum, seed, i, cut)
@@ -254,7 +420,11 @@ def test_some_case_of_its_stratum_detects_the_quirk(quirk):
             if len(next(iter(c.tables[0].values()))) > 9000:
                 continue                                          # (the small cases are enough, and quicker)
             names, types, rows = _want(stratum, seed, i)
-            qn, qt, qrows = run_plan(c.plan, c.tables, frozenset([quirk]))
+            try:
+                qn, qt, qrows = run_plan(c.plan, c.tables, frozenset([quirk]))
+            except g.ExprError:
+                return                                            # the wrong rule fails a call that the true rule completes
+
             a, b = _norm(rows), _norm(qrows)
             if (a != b) if c.ordered else (_multiset(a) != _multiset(b)):
                 return
@@ -264,8 +434,8 @@ def test_some_case_of_its_stratum_detects_the_quirk(quirk):
 def test_an_unknown_quirk_and_a_node_outside_the_dialect_are_named():
     with pytest.raises(ValueError, match="no_such_quirk"):
         run_plan(_case("cross", 0, 1).plan, _case("cross", 0, 1).tables, frozenset(["no_such_quirk"]))
-    with pytest.raises(NotImplementedError, match="union_exec"):
-        run_plan({"execution_plan": "union_exec", "inputs": []}, [])
+    with pytest.raises(NotImplementedError, match="sort_preserving_merge_exec"):
+        run_plan({"execution_plan": "sort_preserving_merge_exec", "input": _case("cross", 0, 1).plan}, _case("cross", 0, 1).tables)
     a = pc.scan([("x", "Int32")])
     with pytest.raises(NotImplementedError, match="Left"):
         run_plan(dict(pc.join("Inner", a, pc.scan([("y", "Int32")]), [("x", "y")]).plan, join_type="Left"), [{"x": [1]}, {"y": [1]}])
@@ -360,7 +530,7 @@ def _compare(gpu, key, ran_all):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", SEEDS)
-@pytest.mark.parametrize("stratum", [s for s in pc.STRATA if s != "errors"])
+@pytest.mark.parametrize("stratum", [s for s in pc.STRATA if s not in pc.ERROR_STRATA])
 def test_gpu_equals_the_interpreter(gpu, stratum, seed):
     ran = set()
     for i in range(pc.CASES_PER_SEED):
@@ -372,11 +542,12 @@ def test_gpu_equals_the_interpreter(gpu, stratum, seed):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", SEEDS)
-def test_gpu_fails_the_call_on_the_one_bad_row_and_is_correct_afterwards(gpu, seed):
+@pytest.mark.parametrize("stratum", pc.ERROR_STRATA)
+def test_gpu_fails_the_call_on_the_one_bad_row_and_is_correct_afterwards(gpu, stratum, seed):
     from flock_amd import FlockGpuError, _ffi
     ran = set()
     for i in range(pc.CASES_PER_SEED):
-        key = ("errors", seed, i)
+        key = (stratum, seed, i)
         c = _case(*key)
         assert isinstance(_want(*key), g.ExprError)
         for cuts in ([None], c.batch_cuts):
