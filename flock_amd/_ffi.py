@@ -236,6 +236,7 @@ SYMBOLS = {
                                        C.POINTER(Windows), _i64, C.POINTER(C.c_char_p), _i, C.POINTER(Q3Result)]),
     "flockgpu_q8_join_exchange": (_i, [_vp, _vp, C.POINTER(PersonCols), C.POINTER(Windows), C.POINTER(AuctionCols),
                                        C.POINTER(Windows), C.POINTER(Q8Result)]),
+    "flockgpu_plan_exchange_retain": (_i, [_vp, _vp, _i, C.c_uint32, C.POINTER(C.c_int64)]),
     "flockgpu_host_alloc": (_i, [C.c_size_t, C.POINTER(_vp)]),
     "flockgpu_host_free": (_i, [_vp]),
     "flockgpu_host_register": (_i, [_vp, C.c_size_t]),
@@ -260,6 +261,7 @@ SYMBOLS = {
     "flockgpu_ctx_wait": (_i, [_vp]),
 }
 PLAN_GENERIC_ONLY = 1
+EXCHANGE_NO_ROWS = 1
 
 _lib = None
 

@@ -25,6 +25,7 @@
 #include <thread>
 
 #include "../../include/flockgpu_comm.h"
+#include "comm_table.hpp"
 #include "relops.hpp"
 
 using namespace flockgpu;
@@ -923,6 +924,342 @@ int check_single_panes(flockgpu_ctx *ctx, const flockgpu_windows *w, const char 
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------ the table exchange (comm_table.hpp)
+namespace flockgpu {
+
+void exchange_phase_begin(flockgpu_comm *c) { phase_begin(c); }
+void exchange_phase_mark(flockgpu_ctx *ctx, flockgpu_comm *c, const char *name) { phase_mark(ctx, c, name); }
+void exchange_phase_finish(flockgpu_ctx *ctx, flockgpu_comm *c) { phase_finish(ctx, c); }
+
+int exchange_table_check(flockgpu_ctx *ctx, const flockgpu_comm *c, const char *what) {
+    FG_TRY(check_comm(ctx, c, what));
+    if (c->dead) return fail(ctx, FLOCKGPU_ERR_PEER, "%s: the communicator is dead (an earlier collective failed)", what);
+    return FLOCKGPU_OK;
+}
+
+// RepartitionExec Hash([key], n_ranks) -- or the gather under CoalescePartitionsExec -- for the result of ANY stage plan.  One window, so
+// the received layout (source-major runs) is already the result: nothing is regrouped, the received buffers are the retained columns.
+// exchange_relation's failure protocol, in two messages of the counts exchange:
+//   A  {status, fingerprint}: a rank whose execute failed (entry_rc) or whose schema / placement differs is known to EVERY rank before a
+//      message whose length depends on the schema is read;
+//   B  {status, rows, validity mask, bytes per Utf8 column} per destination + the totals for every destination: the receiver-side limits
+//      and which columns travel with validity bytes are decided alike on every rank before a data byte moves.
+// After that only the transport or the device can fail: that rank takes its communicator down (kill_comm).
+int exchange_table(flockgpu_ctx *ctx, flockgpu_comm *c, int entry_rc, const XTableArgs &a, XTableResult *out) {
+    const int n = c->n, me = c->rank;
+    const std::string &name = a.name;
+    const size_t nc = a.cols.size();
+    *out = XTableResult{};
+    if (c->dead) return entry_rc != FLOCKGPU_OK ? entry_rc : fail(ctx, FLOCKGPU_ERR_PEER, "exchange: the communicator is dead (an earlier collective failed)");
+    int rc = entry_rc;
+    if (rc == FLOCKGPU_OK && c->inject == 1) {
+        c->inject = 0;
+        rc = fail(ctx, FLOCKGPU_ERR_CAPACITY, "exchange of '%s': injected failure on rank %d (test hook)", name.c_str(), me);
+    }
+    if (n == 1) {   // one destination: send order is input order, the caller's table is the result
+        out->passthrough = rc == FLOCKGPU_OK;
+        return rc;
+    }
+    std::string first_error = ctx->last_error;
+    // slot 0 of every per-destination part of a message is the sender's status
+    auto agree = [&](const std::vector<int64_t> &send, int mm, std::vector<int64_t> &recv, const char *when) -> int {
+        const int rc2 = exchange_counts(ctx, c, send.data(), mm, recv.data());
+        if (rc2 != FLOCKGPU_OK) {   // the transport failed under this rank
+            kill_comm(c);
+            if (rc != FLOCKGPU_OK) ctx->last_error = first_error;
+            return rc != FLOCKGPU_OK ? rc : rc2;
+        }
+        if (rc != FLOCKGPU_OK) {   // the peers have been told
+            ctx->last_error = first_error;
+            return rc;
+        }
+        for (int s = 0; s < n; ++s)
+            if (recv[(size_t)s * mm] != 0)
+                return fail(ctx, FLOCKGPU_ERR_PEER, "exchange of '%s': rank %d failed with status %lld %s", name.c_str(), s, (long long)recv[(size_t)s * mm], when);
+        return FLOCKGPU_OK;
+    };
+
+    // ---- A: status + fingerprint
+    phase_mark(ctx, c, "counts");
+    {
+        const int mA = 2;
+        std::vector<int64_t> send((size_t)n * mA), recv((size_t)n * mA, 0);
+        for (int d = 0; d < n; ++d) {
+            send[(size_t)d * mA] = rc;
+            send[(size_t)d * mA + 1] = (int64_t)a.fingerprint;
+        }
+        FG_TRY(agree(send, mA, recv, "before the repartition"));
+        for (int s = 0; s < n; ++s)
+            if (recv[(size_t)s * mA + 1] != (int64_t)a.fingerprint)
+                return fail(ctx, FLOCKGPU_ERR_INVALID, "exchange of '%s': rank %d runs a plan with another root schema or another placement (schema fingerprint %016llx, here %016llx)",
+                            name.c_str(), s, (unsigned long long)recv[(size_t)s * mA + 1], (unsigned long long)a.fingerprint);
+    }
+
+    // ---- send order
+    struct Sent {
+        const void *values = nullptr;
+        const uint8_t *valid = nullptr;
+        flockgpu_utf8 u{};
+        std::vector<int64_t> run_bytes;   // Utf8: bytes per destination
+    };
+    std::vector<Sent> sent(nc);
+    std::vector<size_t> ucols;   // every Utf8 column, schema order (the message's layout); all-NULL ones carry no bytes
+    for (size_t i = 0; i < nc; ++i)
+        if (a.cols[i].type == ColType::UTF8) {
+            ucols.push_back(i);
+            sent[i].run_bytes.assign((size_t)n, 0);
+        }
+    const int nu = (int)ucols.size();
+    const int64_t n_send = a.rows;
+    std::vector<int64_t> run_start((size_t)n + 1, 0);
+    auto width_of = [&](size_t i) { return (int64_t)col_width(a.cols[i].type); };
+    auto zeros = [&](const std::string &key, size_t bytes, void **p) -> int {
+        FG_TRY(arena_get(ctx, key.c_str(), bytes + 16, p));
+        FG_HIP(ctx, hipMemsetAsync(*p, 0, bytes + 16, ctx->stream));
+        return FLOCKGPU_OK;
+    };
+    auto prepare = [&]() -> int {
+        if (a.gather_rank >= 0 ? (a.sel != nullptr) : (n_send > 0 && !a.keys)) return fail(ctx, FLOCKGPU_ERR_INVALID, "exchange: bad placement arguments");
+        for (size_t i = 0; i < nc; ++i) {   // an all-NULL column (MAX over nothing): zeros in the validity bytes, values unspecified
+            if (!a.cols[i].all_null) continue;
+            void *v = nullptr, *z = nullptr;
+            FG_TRY(zeros(name + ".nullv" + std::to_string(i), (size_t)n_send, &v));
+            sent[i].valid = static_cast<const uint8_t *>(v);
+            if (a.cols[i].type == ColType::UTF8) {
+                FG_TRY(zeros(name + ".nullo" + std::to_string(i), ((size_t)n_send + 1) * 4, &z));
+                sent[i].u = flockgpu_utf8{static_cast<const int32_t *>(z), nullptr};
+            } else {
+                FG_TRY(zeros(name + ".nullx" + std::to_string(i), (size_t)n_send * width_of(i), &z));
+                sent[i].values = z;
+            }
+        }
+        if (a.gather_rank >= 0) {   // one destination: a plain copy -- the columns are their own send buffers
+            for (int d = a.gather_rank + 1; d <= n; ++d) run_start[(size_t)d] = n_send;
+            for (size_t i = 0; i < nc; ++i) {
+                const DevColumn &col = a.cols[i];
+                if (col.all_null) continue;
+                sent[i].valid = col.valid;
+                if (col.type == ColType::UTF8) {
+                    sent[i].u = flockgpu_utf8{col.offsets, static_cast<const uint8_t *>(col.values)};
+                    sent[i].run_bytes[(size_t)a.gather_rank] = n_send > 0 ? col.bytes : 0;
+                } else {
+                    sent[i].values = col.values;
+                }
+            }
+            return FLOCKGPU_OK;
+        }
+        if (n_send == 0) return FLOCKGPU_OK;
+        // fixed-width values ride in the partition's emit pass, kTablePayload columns per launch
+        std::vector<TablePayload> pay(1);
+        auto ride = [&](const void *src, int width, const std::string &key, const void **dst) -> int {
+            void *p = nullptr;
+            FG_TRY(arena_get(ctx, key.c_str(), (size_t)n_send * width + 16, &p));
+            if (pay.back().n == kTablePayload) pay.emplace_back();
+            TablePayload &pl = pay.back();
+            pl.src[pl.n] = src;
+            pl.dst[pl.n] = p;
+            pl.width[pl.n++] = width;
+            *dst = p;
+            return FLOCKGPU_OK;
+        };
+        std::vector<size_t> utake, vtake;   // Utf8 columns and validity bytes are taken at the row list the emit pass writes
+        for (size_t i = 0; i < nc; ++i) {
+            const DevColumn &col = a.cols[i];
+            if (col.all_null) continue;
+            if (col.valid) vtake.push_back(i);
+            if (col.type == ColType::UTF8) utake.push_back(i);
+            else FG_TRY(ride(col.values, (int)width_of(i), name + ".send" + std::to_string(i), &sent[i].values));
+        }
+        for (size_t p = 0; p < pay.size(); ++p) {
+            pay[p].sel = a.sel;
+            pay[p].skip_rows = p > 0 || (utake.empty() && vtake.empty());
+        }
+        const int32_t *part_rows = nullptr;
+        const int64_t *d_group_off = nullptr, *pw = nullptr;
+        FG_TRY(partition_table_async(ctx, (name + ".part").c_str(), a.keys, n_send, n, pay.data(), (int)pay.size(), &part_rows, &d_group_off, &pw));
+        // validity bytes: a take of their own (as 1-byte payload of the emit pass they cost more than this at 2, 4 and 8 destinations:
+        // profiles/plan_exchange/README.md); the row list is already composed with a filter's selection
+        for (size_t i : vtake) {
+            uint8_t *v = nullptr;
+            FG_TRY(arena_get_t(ctx, (name + ".sendv" + std::to_string(i)).c_str(), (size_t)n_send + 16, &v));
+            FG_TRY(gather_u8(ctx, a.cols[i].valid, part_rows, n_send, v));
+            sent[i].valid = v;
+        }
+        // Utf8 columns: the multi-column take in send order, four at a time; the runs' bytes come from the take's own scan
+        std::vector<Utf8MultiGather> takes((utake.size() + 3) / 4);
+        std::vector<std::vector<unsigned long long *>> h_rb(takes.size());
+        for (size_t g = 0; g < takes.size(); ++g) {
+            const int k = (int)std::min<size_t>(4, utake.size() - 4 * g);
+            flockgpu_utf8 srcs[4];
+            unsigned long long *d_rb[4] = {};
+            for (int j = 0; j < k; ++j) {
+                const DevColumn &col = a.cols[utake[4 * g + (size_t)j]];
+                srcs[j] = flockgpu_utf8{col.offsets, static_cast<const uint8_t *>(col.values)};
+            }
+            FG_TRY(gather_utf8_multi_begin(ctx, (name + ".sendu" + std::to_string(g)).c_str(), srcs, k, part_rows, n_send, &takes[g]));
+            h_rb[g].assign((size_t)k, nullptr);
+            for (int j = 0; j < k; ++j) {
+                const std::string key = name + ".sendu" + std::to_string(g) + ".run_bytes" + std::to_string(j);
+                FG_TRY(arena_get_t(ctx, key.c_str(), (size_t)n + 1, &d_rb[j]));
+                FG_TRY(pinned_get_t(ctx, key.c_str(), (size_t)n + 1, &h_rb[g][(size_t)j]));
+            }
+            FG_TRY(gather_utf8_multi_run_bytes(ctx, takes[g], d_group_off, n, d_rb));
+            for (int j = 0; j < k; ++j)
+                FG_HIP(ctx, hipMemcpyAsync(h_rb[g][(size_t)j], d_rb[j], sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        FG_HIP(ctx, hipStreamSynchronize(ctx->stream));   // ONE wait: the group offsets, the Utf8 totals and the runs' bytes
+        for (size_t g = 0; g < takes.size(); ++g) {
+            flockgpu_utf8 outs[4];
+            int64_t nb[4];
+            FG_TRY(gather_utf8_multi_finish(ctx, takes[g], outs, nb));
+            for (int j = 0; j < takes[g].k; ++j) {
+                Sent &s = sent[utake[4 * g + (size_t)j]];
+                s.u = outs[j];
+                for (int d = 0; d < n; ++d) s.run_bytes[(size_t)d] = (int64_t)h_rb[g][(size_t)j][d];
+            }
+        }
+        for (int d = 0; d <= n; ++d) run_start[(size_t)d] = pw[d];
+        if (run_start[(size_t)n] != n_send) return fail(ctx, FLOCKGPU_ERR_HIP, "exchange: the partition pass covered %lld of %lld rows", (long long)run_start[(size_t)n], (long long)n_send);
+        return FLOCKGPU_OK;
+    };
+    phase_mark(ctx, c, "partition+take");
+    rc = prepare();
+    first_error = ctx->last_error;
+
+    // ---- B: rows, validity, Utf8 bytes -- and the totals for every destination
+    phase_mark(ctx, c, "counts");
+    const int n_mask = (int)((nc + 31) / 32);
+    const int m = 2 + n_mask + nu, tot = n * (1 + nu), mm = m + tot;
+    std::vector<int64_t> send_counts((size_t)n * mm, 0), recv_counts((size_t)n * mm, 0);
+    if (rc == FLOCKGPU_OK) {
+        std::vector<int64_t> totals((size_t)tot, 0), mask((size_t)n_mask, 0);
+        for (size_t i = 0; i < nc; ++i)
+            if (a.cols[i].valid || a.cols[i].all_null) mask[i / 32] |= int64_t(1) << (i % 32);
+        for (int d = 0; d < n; ++d) {
+            int64_t *part = &send_counts[(size_t)d * mm];
+            part[1] = totals[(size_t)d * (1 + nu)] = run_start[(size_t)d + 1] - run_start[(size_t)d];
+            std::copy(mask.begin(), mask.end(), part + 2);
+            for (int u = 0; u < nu; ++u) part[2 + n_mask + u] = totals[(size_t)d * (1 + nu) + 1 + u] = sent[ucols[(size_t)u]].run_bytes[(size_t)d];
+        }
+        for (int d = 0; d < n; ++d) std::copy(totals.begin(), totals.end(), send_counts.begin() + (size_t)d * mm + m);
+    }
+    for (int d = 0; d < n; ++d) send_counts[(size_t)d * mm] = rc;
+    FG_TRY(agree(send_counts, mm, recv_counts, "in its partition pass"));
+    for (int d = 0; d < n; ++d) {   // the same verdict on every rank: what rank d is going to receive
+        int64_t r = 0;
+        for (int s = 0; s < n; ++s) r += recv_counts[(size_t)s * mm + m + (size_t)d * (1 + nu)];
+        bool over = r >= (int64_t(1) << 31);
+        if (over && d == me) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "exchange of '%s': this rank would receive %lld rows (limit 2^31 per rank and call)", name.c_str(), (long long)r);
+        for (int u = 0; u < nu && !over; ++u) {
+            int64_t by = 0;
+            for (int s = 0; s < n; ++s) by += recv_counts[(size_t)s * mm + m + (size_t)d * (1 + nu) + 1 + u];
+            over = by >= (int64_t(1) << 31);
+            if (over && d == me)
+                return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "exchange of '%s': Utf8 column %zu received by this rank would hold %lld bytes (Arrow int32 offsets)", name.c_str(), ucols[(size_t)u], (long long)by);
+        }
+        if (over) return fail(ctx, FLOCKGPU_ERR_PEER, "exchange of '%s': rank %d would receive more than 2^31 rows or Utf8 bytes", name.c_str(), d);
+    }
+    std::vector<char> with_valid(nc, 0);   // a received column carries validity when any rank's column does
+    for (size_t i = 0; i < nc; ++i)
+        for (int s = 0; s < n; ++s) with_valid[i] = with_valid[i] || ((recv_counts[(size_t)s * mm + 2 + i / 32] >> (i % 32)) & 1);
+
+    // ---- one all-to-all per column buffer; source-major runs are the result's order
+    phase_mark(ctx, c, "all_to_all");
+    auto move = [&]() -> int {
+        if (c->inject == 2) {
+            c->inject = 0;
+            return fail(ctx, FLOCKGPU_ERR_HIP, "exchange of '%s': injected transport failure on rank %d (test hook)", name.c_str(), me);
+        }
+        std::vector<int64_t> recv_rows_off((size_t)n + 1, 0);
+        for (int s = 0; s < n; ++s) recv_rows_off[(size_t)s + 1] = recv_rows_off[(size_t)s] + recv_counts[(size_t)s * mm + 1];
+        const int64_t n_recv = recv_rows_off[(size_t)n];
+        int64_t *d_run_start = nullptr, *d_rro = nullptr;
+        if (nu) {
+            FG_TRY(upload(ctx, name + ".run_start", run_start.data(), (size_t)n + 1, &d_run_start));
+            FG_TRY(upload(ctx, name + ".rrows", recv_rows_off.data(), (size_t)n + 1, &d_rro));
+        }
+        out->rows = n_recv;
+        out->cols.assign(nc, DevColumn{});
+        std::vector<int64_t> so((size_t)n + 1), ro((size_t)n + 1);
+        auto offsets_of = [&](int64_t width) {
+            for (int p = 0; p <= n; ++p) {
+                so[(size_t)p] = run_start[(size_t)p] * width;
+                ro[(size_t)p] = recv_rows_off[(size_t)p] * width;
+            }
+        };
+        int u = 0;
+        for (size_t i = 0; i < nc; ++i) {
+            DevColumn &o = out->cols[i];
+            o.type = a.cols[i].type;
+            o.is_ts = a.cols[i].is_ts;
+            o.nullable = a.cols[i].nullable || with_valid[i];
+            const std::string key = name + ".recv" + std::to_string(i);
+            if (with_valid[i]) {
+                const uint8_t *src = sent[i].valid;
+                if (!src) {   // this rank's column has no NULLs: ones
+                    void *ones = nullptr;
+                    FG_TRY(arena_get(ctx, (name + ".ones" + std::to_string(i)).c_str(), (size_t)n_send + 16, &ones));
+                    FG_HIP(ctx, hipMemsetAsync(ones, 1, (size_t)n_send + 16, ctx->stream));
+                    src = static_cast<const uint8_t *>(ones);
+                }
+                uint8_t *v = nullptr;
+                FG_TRY(arena_get_t(ctx, (key + ".valid").c_str(), (size_t)n_recv + 16, &v));
+                offsets_of(1);
+                FG_TRY(all_to_all(ctx, c, src, so.data(), v, ro.data()));
+                o.valid = v;
+            }
+            if (o.type != ColType::UTF8) {
+                void *vals = nullptr;
+                FG_TRY(arena_get(ctx, key.c_str(), (size_t)n_recv * width_of(i) + 16, &vals));
+                offsets_of(width_of(i));
+                FG_TRY(all_to_all(ctx, c, sent[i].values, so.data(), vals, ro.data()));
+                o.values = vals;
+                continue;
+            }
+            // Utf8: the rows' END offsets travel relative to the start of their run, the bytes as they are
+            std::vector<int64_t> send_delta((size_t)n), recv_delta((size_t)n), sb((size_t)n + 1, 0), rb((size_t)n + 1, 0);
+            for (int p = 0; p < n; ++p) {
+                sb[(size_t)p + 1] = sb[(size_t)p] + sent[i].run_bytes[(size_t)p];
+                rb[(size_t)p + 1] = rb[(size_t)p] + recv_counts[(size_t)p * mm + 2 + n_mask + u];
+                send_delta[(size_t)p] = -sb[(size_t)p];
+                recv_delta[(size_t)p] = rb[(size_t)p];
+            }
+            ++u;
+            int64_t *d_sd = nullptr, *d_rd = nullptr;
+            FG_TRY(upload(ctx, key + ".sdelta", send_delta.data(), (size_t)n, &d_sd));
+            FG_TRY(upload(ctx, key + ".rdelta", recv_delta.data(), (size_t)n, &d_rd));
+            int32_t *ends_send = nullptr, *off_recv = nullptr;
+            uint8_t *bytes_recv = nullptr;
+            FG_TRY(arena_get_t(ctx, (key + ".ends").c_str(), (size_t)n_send + 4, &ends_send));
+            FG_TRY(arena_get_t(ctx, (key + ".off").c_str(), (size_t)n_recv + 4, &off_recv));
+            FG_TRY(arena_get_t(ctx, key.c_str(), (size_t)rb[(size_t)n] + 16, &bytes_recv));
+            if (n_send > 0) {
+                hipLaunchKernelGGL(run_rebase_kernel, dim3(grid_for(ctx, n_send)), dim3(kBlock), 0, ctx->stream, sent[i].u.offsets + 1, n_send, d_run_start, d_sd, n, ends_send);
+                FG_TRY(check_launch(ctx, "run_rebase_kernel"));
+            }
+            offsets_of(4);
+            FG_HIP(ctx, hipMemsetAsync(off_recv, 0, 4, ctx->stream));
+            FG_TRY(all_to_all(ctx, c, ends_send, so.data(), off_recv + 1, ro.data()));
+            FG_TRY(all_to_all(ctx, c, sent[i].u.data, sb.data(), bytes_recv, rb.data()));
+            if (n_recv > 0) {
+                hipLaunchKernelGGL(run_rebase_kernel, dim3(grid_for(ctx, n_recv)), dim3(kBlock), 0, ctx->stream, off_recv + 1, n_recv, d_rro, d_rd, n, off_recv + 1);
+                FG_TRY(check_launch(ctx, "run_rebase_kernel"));
+            }
+            o.values = bytes_recv;
+            o.offsets = off_recv;
+            o.bytes = rb[(size_t)n];
+        }
+        return FLOCKGPU_OK;
+    };
+    rc = move();
+    // the consumer's kernels follow on this stream: the received bytes must have ARRIVED -- or the peers be known gone -- before they start
+    if (rc == FLOCKGPU_OK && c->is_rccl) rc = comm_stream_wait(ctx, c, "all-to-all");
+    if (rc != FLOCKGPU_OK) kill_comm(c);   // past the agreement: the peers are already moving data
+    return rc;
+}
+
+}  // namespace flockgpu
 
 extern "C" {
 

@@ -158,6 +158,23 @@ int partition_by_key_async(flockgpu_ctx *ctx, const int32_t *keys, int64_t rows,
                            const int32_t **d_rows, const int64_t **d_group_off, const int64_t **h_group_off, int64_t *n_out,
                            const PartPayload *payload = nullptr, const char *cache_name = nullptr);
 
+// The same pass for a whole TABLE (the generic plan exchange, comm.hip exchange_table): one window [0, rows), 32-bit keys already folded, and an
+// emit pass of its own that carries up to kTablePayload columns of 4 or 8 bytes per launch in send order (validity bytes are taken with gather_u8).  `sel` (may be
+// null): relation row r is row sel[r] of the payload columns -- a filter's row list directly below the repartition, composed here instead
+// of by a take of its own; the row numbers written (*d_rows) are in the payload columns' row space, too.  More than kTablePayload columns: several
+// payloads, one emit launch each over the same destination bytes and tile bases.  n_parts >= 2.
+constexpr int kTablePayload = 8;
+struct TablePayload {
+    int32_t n = 0;
+    const void *src[kTablePayload] = {};
+    void *dst[kTablePayload] = {};       // `rows` entries each, caller-owned
+    int32_t width[kTablePayload] = {};   // 4 | 8
+    const int32_t *sel = nullptr;
+    bool skip_rows = false;              // this launch writes no row numbers
+};
+int partition_table_async(flockgpu_ctx *ctx, const char *name, const int32_t *keys, int64_t rows, int32_t n_parts, const TablePayload *payloads, int n_payloads,
+                          const int32_t **d_rows, const int64_t **d_group_off, const int64_t **h_group_off);
+
 // q3's stage 0 for the in-library exchange (q3.hip; planner.rs:152-171: FilterExec category = lit / state = a OR b OR ... BEFORE the
 // hash repartition): the rows each filter keeps, in input order, with the windows' new row offsets.  Synchronises once for both.
 struct Q3Stage0 {

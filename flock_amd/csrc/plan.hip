@@ -20,6 +20,7 @@
 
 #include "../../include/flockgpu_plan.h"
 #include "plan_ir.hpp"
+#include "comm_table.hpp"
 #include "cross.hpp"
 #include "union.hpp"
 #include "pred.hpp"
@@ -4890,16 +4891,9 @@ int flockgpu_plan_feed_shared(flockgpu_plan *plan, int input, const flockgpu_pla
     return FLOCKGPU_OK;   // same stream as the donor's copies: ordered behind them without a wait
 }
 
-int flockgpu_plan_execute_retain(flockgpu_plan *plan, int64_t *rows) {
-    if (!plan) return FLOCKGPU_ERR_INVALID;
+// The tail of execute_retain, shared with flockgpu_plan_exchange_retain's one-rank case: `t` becomes the plan's retained result.
+static int keep_result(flockgpu_plan *plan, Table &t, int64_t *rows) {
     flockgpu_ctx *ctx = plan->ctx;
-    FG_HIP(ctx, hipSetDevice(ctx->device));
-    plan->has_retained = false;
-    Exec ex{plan, ctx};
-    Table t;
-    // a root hash repartition is not computed: which partition a key lands in is unobservable once every partition is handed to
-    // the same consumer, and that is the only hand-over this call serves
-    FG_TRY(ex.exec(plan->ir.root.get(), &t));
     const Node *root = plan->ir.root.get();
     if (t.cols.size() != root->schema.size()) return fail(ctx, FLOCKGPU_ERR_HIP, "plan execute: %zu result columns for a schema of %zu", t.cols.size(), root->schema.size());
     for (size_t c = 0; c < t.cols.size(); ++c)
@@ -4951,6 +4945,156 @@ int flockgpu_plan_execute_retain(flockgpu_plan *plan, int64_t *rows) {
     plan->has_retained = true;
     if (rows) *rows = t.rows;
     return FLOCKGPU_OK;   // no host wait: the consumer's kernels follow on the same stream
+}
+
+int flockgpu_plan_execute_retain(flockgpu_plan *plan, int64_t *rows) {
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    FG_HIP(ctx, hipSetDevice(ctx->device));
+    plan->has_retained = false;
+    Exec ex{plan, ctx};
+    Table t;
+    // a root hash repartition is not computed: which partition a key lands in is unobservable once every partition is handed to
+    // the same consumer, and that is the only hand-over this call serves
+    FG_TRY(ex.exec(plan->ir.root.get(), &t));
+    return keep_result(plan, t, rows);
+}
+
+// The collective twin of execute_retain (include/flockgpu_comm.h): the result is hash-partitioned over the ranks of `comm` -- or gathered on
+// one of them -- by the library's own all-to-all (comm.hip exchange_table) and what this rank receives becomes the retained result.
+int flockgpu_plan_exchange_retain(flockgpu_plan *plan, flockgpu_comm *comm, int gather_rank, uint32_t flags, int64_t *rows) {
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    if (rows) *rows = 0;
+    // ---- returned at once, before any collective
+    FG_TRY(exchange_table_check(ctx, comm, "plan_exchange_retain"));
+    const int n = flockgpu_comm_size(comm);
+    if (flags & ~FLOCKGPU_EXCHANGE_NO_ROWS) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_exchange_retain: unknown flag bits 0x%x", flags & ~FLOCKGPU_EXCHANGE_NO_ROWS);
+    if (gather_rank < -1 || gather_rank >= n) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_exchange_retain: gather_rank %d with %d ranks", gather_rank, n);
+    if (plan->async_pending) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_exchange_retain: an asynchronous execute is in flight (flockgpu_plan_wait first)");
+    const Node *root = plan->ir.root.get();
+    if (gather_rank < 0) {
+        if (root->kind != NKind::Repartition || root->hash_cols.empty())
+            return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_exchange_retain: rows are placed by the root's hash keys, and the plan's root is no RepartitionExec Hash (pass a gather_rank)");
+        if (root->hash_diff)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_exchange_retain: a HashDiff root gives every distinct key a partition of its own; the ranks of a communicator are no such partitions");
+    }
+    FG_HIP(ctx, hipSetDevice(ctx->device));
+    plan->has_retained = false;
+    exchange_phase_begin(comm);
+    exchange_phase_mark(ctx, comm, "execute");
+    const bool no_rows = (flags & FLOCKGPU_EXCHANGE_NO_ROWS) != 0;
+    XTableArgs a;
+    {
+        char prefix[40];
+        snprintf(prefix, sizeof prefix, "plan%p.xchg", (const void *)plan);   // buffers named after the plan: keep_result's mine() rule holds for what arrives
+        a.name = prefix;
+    }
+    a.gather_rank = gather_rank;
+    {   // names, types and order of the root schema, and where the rows go
+        uint64_t h = 1469598103934665603ull;
+        auto mix = [&](const void *p, size_t len) {
+            for (size_t i = 0; i < len; ++i) h = (h ^ static_cast<const uint8_t *>(p)[i]) * 1099511628211ull;
+        };
+        for (const Field &f : root->schema) {
+            mix(f.name.data(), f.name.size() + 1);
+            const int32_t t[2] = {(int32_t)f.type, f.is_ts ? 1 : 0};
+            mix(t, sizeof t);
+        }
+        const int32_t place[2] = {gather_rank, gather_rank < 0 ? root->hash_cols[0] : -1};
+        mix(place, sizeof place);
+        a.fingerprint = h;
+    }
+    Exec ex{plan, ctx};
+    Table t, blank;   // blank: what a rank without rows announces -- the schema's columns, empty
+    blank.cols.assign(root->schema.size(), TCol{});
+    for (size_t c = 0; c < blank.cols.size(); ++c) {
+        blank.cols[c].c.type = root->schema[c].type;
+        blank.cols[c].c.is_ts = root->schema[c].is_ts;
+        blank.cols[c].c.nullable = root->schema[c].nullable;
+        blank.cols[c].present = true;
+    }
+    auto describe = [&](const Table &from, int64_t n_rows) -> int {
+        if (from.cols.size() != root->schema.size()) return fail(ctx, FLOCKGPU_ERR_HIP, "plan execute: %zu result columns for a schema of %zu", from.cols.size(), root->schema.size());
+        a.cols.clear();
+        for (size_t c = 0; c < from.cols.size(); ++c) {
+            if (!from.cols[c].present && !from.cols[c].c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: output column '%s' was not materialised", root->schema[c].name.c_str());
+            a.cols.push_back(from.cols[c].c);
+        }
+        a.rows = n_rows;
+        return FLOCKGPU_OK;
+    };
+    auto produce = [&]() -> int {
+        if (n == 1 || gather_rank >= 0) {   // a root hash repartition is skipped, as execute_retain skips it
+            FG_TRY(ex.exec(root, &t));
+            return describe(t, t.rows);
+        }
+        // run_plan's placement with the partition count replaced by the communicator's size; a filter directly below the repartition is
+        // composed with the send order (its row list goes into the emit pass), never materialised
+        const Node *below = root->in[0].get();
+        while (below->kind == NKind::Repartition) below = below->in[0].get();
+        const bool compose = below->kind == NKind::Filter && plan->fused[(size_t)below->id].kind == kNone && below->schema.size() == root->schema.size() &&
+                             root->in[0]->schema.size() == root->schema.size();
+        Table in;
+        int32_t *sel = nullptr;
+        int64_t n_sel = 0;
+        if (compose) FG_TRY(ex.filter_rows(below, &in, &sel, &n_sel));
+        else FG_TRY(ex.exec(root->in[0].get(), &in));
+        const int64_t n_rows = compose ? n_sel : in.rows;
+        FG_TRY(describe(in, n_rows));
+        TCol k = in.cols[(size_t)root->hash_cols[0]];
+        if (!k.present && !k.c.all_null) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan execute: key column was not materialised");
+        int64_t *keys = nullptr;
+        if (k.c.all_null) {   // every key NULL: one key
+            FG_TRY(arena_get_t(ctx, node_key(plan, root, "xk").c_str(), (size_t)n_rows + 2, &keys));
+            FG_HIP(ctx, hipMemsetAsync(keys, 0, sizeof(int64_t) * ((size_t)n_rows + 2), ctx->stream));
+        } else {
+            if (compose) FG_TRY(take_column(ctx, node_key(plan, root, "xkcol").c_str(), in.cols[(size_t)root->hash_cols[0]].c, sel, n_sel, &k.c));
+            if (k.c.type == ColType::UTF8) {
+                FG_TRY(arena_get_t(ctx, node_key(plan, root, "xk").c_str(), (size_t)n_rows + 2, &keys));
+                FG_TRY(hash_utf8_i64(ctx, k.c, n_rows, keys));
+            } else {
+                FG_TRY(ex.key_i64(root, k, n_rows, "xk", &keys));
+            }
+            if (k.c.valid) FG_TRY(replace_invalid_i64(ctx, keys, k.c.valid, n_rows, 0));   // (NULL keys: one key as far as placement goes)
+        }
+        int32_t *folded = nullptr;
+        FG_TRY(arena_get_t(ctx, node_key(plan, root, "xfold").c_str(), (size_t)n_rows + 4, &folded));
+        FG_TRY(fold_keys_i32(ctx, keys, n_rows, folded));
+        a.keys = folded;
+        a.sel = compose ? sel : nullptr;
+        return FLOCKGPU_OK;
+    };
+    int rc = FLOCKGPU_OK;
+    if (no_rows) rc = describe(blank, 0);
+    else rc = produce();
+    if (rc != FLOCKGPU_OK) {   // the failed rank still takes part: the empty table stands in
+        const std::string first_error = ctx->last_error;
+        (void)describe(blank, 0);
+        a.keys = nullptr;
+        a.sel = nullptr;
+        ctx->last_error = first_error;
+    }
+    XTableResult res;
+    rc = exchange_table(ctx, comm, rc, a, &res);
+    if (rc == FLOCKGPU_OK) {
+        if (res.passthrough) {
+            rc = keep_result(plan, no_rows ? blank : t, rows);
+        } else {
+            Table got;
+            got.rows = res.rows;
+            got.cols.assign(res.cols.size(), TCol{});
+            for (size_t c = 0; c < res.cols.size(); ++c) {
+                got.cols[c].c = res.cols[c];
+                got.cols[c].present = true;
+            }
+            plan->retained = got;
+            plan->has_retained = true;
+            if (rows) *rows = got.rows;
+        }
+    }
+    exchange_phase_finish(ctx, comm);
+    return rc;
 }
 
 int flockgpu_plan_feed_from(flockgpu_plan *plan, int input, const flockgpu_plan *producer) {

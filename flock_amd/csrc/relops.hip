@@ -2668,6 +2668,11 @@ int row_number_runs(flockgpu_ctx *ctx, const char *name, const DevColumn *cols, 
     return FLOCKGPU_OK;
 }
 
+int fold_keys_i32(flockgpu_ctx *ctx, const int64_t *keys, int64_t rows, int32_t *out) {
+    if (rows > 0) RELOPS_LAUNCH(ctx, "fold_key_kernel", fold_key_kernel, rows, keys, rows, out);
+    return FLOCKGPU_OK;
+}
+
 int partition_rows_key64(flockgpu_ctx *ctx, const char *name, const int64_t *keys, int64_t rows, int32_t n_parts, int32_t **out_rows,
                          std::vector<int64_t> *part_offsets) {
     const std::string base = name;

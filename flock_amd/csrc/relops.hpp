@@ -185,6 +185,8 @@ int semi_rows_from_ids(flockgpu_ctx *ctx, const char *name, const void *ids, boo
 // mix of flockgpu_partition_by_key.  part_offsets: host, n_parts + 1.
 int partition_rows_key64(flockgpu_ctx *ctx, const char *name, const int64_t *keys, int64_t rows, int32_t n_parts, int32_t **out_rows,
                          std::vector<int64_t> *part_offsets);
+// the fold alone: out[i] = low ^ high word of keys[i], the 32-bit key the partition pass mixes (the table exchange partitions by it, comm_table.hpp)
+int fold_keys_i32(flockgpu_ctx *ctx, const int64_t *keys, int64_t rows, int32_t *out);
 
 // ---- ORDER BY (SortExec; the reference's boundary goldens end in it, flock/src/runtime/context.rs:471,549, and the stage splitter
 // cuts at it, flock/src/distributed_plan/stage.rs:337): the permutation of [0, rows) that orders the rows by `keys`, first key most

@@ -284,6 +284,157 @@ __global__ __launch_bounds__(kBlock) void partition_emit_one_kernel(SegTiles st,
     }
 }
 
+// ---- the emit pass for whole tables (TablePayload): a generic result is mostly 8-byte values (COUNT / SUM states, timestamps, Int64 keys), which
+// PartPayload does not take.  (1-byte columns -- validity -- were carried here, too, and measured slower than gather_u8 at the row list: not kept.)  The write-out is a scatter by position, so what counts is how often the row list is walked
+// and how many loads a lane has in flight: a lane takes kTableRows list entries per step, resolves their source rows (one more load each under a
+// filter's row list), then issues EVERY column's load of every entry before the first store -- up to 16 independent loads per lane.  The column
+// count and the widths are kernel arguments: the branches on them are uniform.
+constexpr int kTableRows = 2;
+__device__ __forceinline__ uint64_t table_load(const void *__restrict__ src, int32_t width, int64_t r) {
+    if (width == 8) return static_cast<const uint64_t *>(src)[r];
+    return static_cast<const uint32_t *>(src)[r];
+}
+__device__ __forceinline__ void table_store(void *__restrict__ dst, int32_t width, uint64_t pos, uint64_t v) {
+    if (width == 8) static_cast<uint64_t *>(dst)[pos] = v;
+    else static_cast<uint32_t *>(dst)[pos] = (uint32_t)v;
+}
+// rows r[k] (relation rows, all inside the window) go to send positions pos[k]; on[k] = 0: no such entry
+__device__ __forceinline__ void table_move(const TablePayload &pl, int32_t *__restrict__ out_rows, const int64_t (&r)[kTableRows], const uint64_t (&pos)[kTableRows],
+                                           const bool (&on)[kTableRows]) {
+    int64_t sr[kTableRows];
+#pragma unroll
+    for (int k = 0; k < kTableRows; ++k) sr[k] = !on[k] ? 0 : pl.sel ? (int64_t)pl.sel[r[k]] : r[k];
+    uint64_t v[kTableRows][kTablePayload];
+#pragma unroll
+    for (int k = 0; k < kTableRows; ++k)
+#pragma unroll
+        for (int c = 0; c < kTablePayload; ++c) v[k][c] = (c < pl.n && on[k]) ? table_load(pl.src[c], pl.width[c], sr[k]) : 0ull;
+#pragma unroll
+    for (int k = 0; k < kTableRows; ++k) {
+        if (!on[k]) continue;
+        if (!pl.skip_rows) out_rows[pos[k]] = (int32_t)sr[k];
+#pragma unroll
+        for (int c = 0; c < kTablePayload; ++c)
+            if (c < pl.n) table_store(pl.dst[c], pl.width[c], pos[k], v[k][c]);
+    }
+}
+
+// partition_emit_loop_kernel's list build (up to kPartLoopMax destinations), the table write-out
+__global__ __launch_bounds__(kBlock) void partition_emit_table_loop_kernel(const uint32_t *__restrict__ dest, SegTiles st, uint32_t n_parts,
+                                                                           const uint32_t *__restrict__ counts, const uint64_t *__restrict__ tile_base,
+                                                                           int32_t *__restrict__ out_rows, TablePayload pl) {
+    __shared__ uint16_t s_list[kFlagTile];
+    const int32_t tile = (int32_t)blockIdx.x;
+    const TileRange tr = locate_tile(st, tile, kFlagTile);
+    uint32_t d[kFlagIters];
+#pragma unroll
+    for (int it = 0; it < kFlagIters; ++it) d[it] = __builtin_nontemporal_load(dest + (size_t)tile * (kFlagTile / 4) + (flag_rel0() >> 2) + it * 64);
+#pragma unroll 1
+    for (uint32_t part = 0; part < n_parts; ++part) {
+        const size_t slot = (size_t)part * st.n_tiles + tile;
+        const uint4 wc = *reinterpret_cast<const uint4 *>(counts + slot * kWavesPerBlock);
+        if (wc.x + wc.y + wc.z + wc.w == 0) continue;  // block-uniform
+        const uint32_t total = build_flag_list(flags_of(d, part), wc, s_list);
+        __syncthreads();
+        const uint64_t base = tile_base[slot];
+        for (uint32_t i0 = 0; i0 < total; i0 += kBlock * kTableRows) {
+            int64_t r[kTableRows];
+            uint64_t pos[kTableRows];
+            bool on[kTableRows];
+#pragma unroll
+            for (int k = 0; k < kTableRows; ++k) {
+                const uint32_t i = i0 + k * kBlock + threadIdx.x;
+                on[k] = i < total;
+                r[k] = tr.tile_begin + (on[k] ? s_list[i] : 0);
+                pos[k] = base + i;
+            }
+            table_move(pl, out_rows, r, pos, on);
+        }
+        __syncthreads();  // s_list is rewritten for the next destination
+    }
+}
+
+// partition_emit_kernel's one-pass list build (any number of destinations up to kMaxParts), the table write-out
+__global__ __launch_bounds__(kBlock) void partition_emit_table_kernel(const uint32_t *__restrict__ dest, SegTiles st, uint32_t n_parts,
+                                                                      const uint32_t *__restrict__ counts, const uint64_t *__restrict__ tile_base,
+                                                                      int32_t *__restrict__ out_rows, TablePayload pl) {
+    __shared__ uint16_t s_list[kFlagTile];
+    __shared__ __attribute__((aligned(16))) uint32_t s_dest[kFlagTile / 4];
+    __shared__ uint32_t s_cnt[kPartGroup * kBlock];
+    __shared__ uint32_t s_start[kMaxParts * kWavesPerBlock];
+    __shared__ uint32_t s_gdelta[kMaxParts];
+    __shared__ uint32_t s_total;
+    const int32_t tile = (int32_t)blockIdx.x;
+    const TileRange tr = locate_tile(st, tile, kFlagTile);
+    const int wave = threadIdx.x >> 6, lane = lane_id();
+    uint32_t d[kFlagIters];   // the lane's rows: wave * 2048 + lane * 32 + (0 .. 31)
+    {
+        const uint32_t *src = dest + (size_t)tile * (kFlagTile / 4) + threadIdx.x * 8;
+        const uint4 a = stream_load4u(src), b = stream_load4u(src + 4);
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+        *reinterpret_cast<uint4 *>(s_dest + threadIdx.x * 8) = a;
+        *reinterpret_cast<uint4 *>(s_dest + threadIdx.x * 8 + 4) = b;
+    }
+    if (wave == 0) {   // (n_parts <= 64: one lane per destination)
+        const bool live = (uint32_t)lane < n_parts;
+        const size_t slot = (size_t)(live ? lane : 0) * st.n_tiles + tile;
+        uint4 wc = *reinterpret_cast<const uint4 *>(counts + slot * kWavesPerBlock);
+        if (!live) wc = make_uint4(0, 0, 0, 0);
+        const uint32_t total = wc.x + wc.y + wc.z + wc.w;
+        const uint32_t incl = wave_incl_scan_u32(total);
+        const uint32_t off = incl - total;
+        if (live) {
+            s_start[lane * kWavesPerBlock + 0] = off;
+            s_start[lane * kWavesPerBlock + 1] = off + wc.x;
+            s_start[lane * kWavesPerBlock + 2] = off + wc.x + wc.y;
+            s_start[lane * kWavesPerBlock + 3] = off + wc.x + wc.y + wc.z;
+            s_gdelta[lane] = (uint32_t)tile_base[slot] - off;   // (positions stay below 2^31: the host checks the row count)
+            if ((uint32_t)lane == n_parts - 1) s_total = incl;
+        }
+    }
+    __syncthreads();
+    const uint32_t rel_first = (uint32_t)threadIdx.x * 32;
+#pragma unroll 1
+    for (uint32_t g8 = 0; g8 < n_parts; g8 += kPartGroup) {
+        uint32_t w[4];
+        spread16(group_counts(d, g8), w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t excl = wave_incl_scan_u32(w[k]) - w[k];
+            const uint32_t p0 = g8 + 2 * k;
+            if (p0 < n_parts) s_cnt[(2 * k) * kBlock + threadIdx.x] = s_start[p0 * kWavesPerBlock + wave] + (excl & 0xFFFFu);
+            if (p0 + 1 < n_parts) s_cnt[(2 * k + 1) * kBlock + threadIdx.x] = s_start[(p0 + 1) * kWavesPerBlock + wave] + (excl >> 16);
+        }
+#pragma unroll
+        for (int it = 0; it < kFlagIters; ++it)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t pg = ((d[it] >> (8 * j)) & 0xFFu) - g8;
+                if (pg < kPartGroup) {
+                    const uint32_t pos = atomicAdd(&s_cnt[pg * kBlock + threadIdx.x], 1u);
+                    s_list[pos] = (uint16_t)(rel_first + it * 4 + j);
+                }
+            }
+    }
+    __syncthreads();
+    const uint32_t total = s_total;
+    const uint8_t *s_dest_b = reinterpret_cast<const uint8_t *>(s_dest);
+    for (uint32_t i0 = 0; i0 < total; i0 += kBlock * kTableRows) {
+        int64_t r[kTableRows];
+        uint64_t pos[kTableRows];
+        bool on[kTableRows];
+#pragma unroll
+        for (int k = 0; k < kTableRows; ++k) {
+            const uint32_t i = i0 + k * kBlock + threadIdx.x;
+            on[k] = i < total;
+            const uint32_t rel = on[k] ? s_list[i] : 0u;
+            r[k] = tr.tile_begin + rel;
+            pos[k] = on[k] ? (uint32_t)(i + s_gdelta[s_dest_b[rel]]) : 0u;
+        }
+        table_move(pl, out_rows, r, pos, on);
+    }
+}
+
 // ---- Partial DISTINCT per tile.  What repeats inside a tile of sellers is the hot key (3/4 of a window's auctions name one of a few
 // sellers; the others are ~2000 different ids of millions): each wave follows the key most of its lanes hold -- kept while it covers
 // >= 16 lanes, re-elected from two lanes otherwise, as q8_sellers_bitmap_kernel does -- and hands it on ONCE; every other row is handed
@@ -449,6 +600,67 @@ int partition_by_key_async(flockgpu_ctx *ctx, const int32_t *keys, int64_t rows,
     *d_group_off = d_off;
     *h_group_off = h_off;
     *n_out = covered;
+    return FLOCKGPU_OK;
+}
+
+// The table form of the pass above (gather.hpp): one window over all rows, the count pass and the tile scan as they are, the table emit kernels.
+// Everything lives under `name` (a plan's exchange keeps its send order until its all-to-all has gone out).
+int partition_table_async(flockgpu_ctx *ctx, const char *name, const int32_t *keys, int64_t rows, int32_t n_parts, const TablePayload *payloads, int n_payloads,
+                          const int32_t **d_rows, const int64_t **d_group_off, const int64_t **h_group_off) {
+    const std::string nm = name;
+    if (rows < 0 || (rows > 0 && !keys) || n_payloads < 1 || !payloads) return fail(ctx, FLOCKGPU_ERR_INVALID, "partition: null argument");
+    if (n_parts < 2 || n_parts > kMaxParts) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "partition: a table is partitioned over 2 to %d destinations", kMaxParts);
+    if (reinterpret_cast<uintptr_t>(keys) & 15) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "partition: key column must be 16-byte aligned");
+    if (rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "partition: relations are limited to 2^31 rows per call");
+    for (int p = 0; p < n_payloads; ++p) {
+        if (payloads[p].n < 0 || payloads[p].n > kTablePayload) return fail(ctx, FLOCKGPU_ERR_INVALID, "partition: at most %d payload columns per launch", kTablePayload);
+        for (int c = 0; c < payloads[p].n; ++c)
+            if (payloads[p].width[c] != 4 && payloads[p].width[c] != 8) return fail(ctx, FLOCKGPU_ERR_INVALID, "partition: payload columns are 4 or 8 bytes wide");
+    }
+    const int64_t sb = 0, se = rows;
+    SegTiles st;
+    FG_TRY(build_seg_tiles(ctx, nm.c_str(), &sb, &se, 1, kFlagTile, &st));
+    const int64_t slots = (int64_t)st.n_tiles * n_parts;
+    if (slots > 0x7fffffff / 2) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "partition: too many (destination, tile) pairs");
+    int32_t *d_first = nullptr, *h_first = nullptr;
+    FG_TRY(arena_get_t(ctx, (nm + ".first").c_str(), (size_t)n_parts + 1, &d_first));
+    FG_TRY(pinned_get_t(ctx, (nm + ".first").c_str(), (size_t)n_parts + 1, &h_first));
+    std::vector<int64_t> &first_key = ctx->host_i64[nm + ".first_key"];
+    const std::vector<int64_t> key_now{n_parts, (int64_t)reinterpret_cast<uintptr_t>(d_first), st.n_tiles};
+    if (first_key != key_now) {   // (the pinned staging of the previous upload may still be in flight)
+        FG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int p = 0; p <= n_parts; ++p) h_first[p] = (int32_t)((int64_t)p * st.n_tiles);
+        FG_HIP(ctx, hipMemcpyAsync(d_first, h_first, sizeof(int32_t) * ((size_t)n_parts + 1), hipMemcpyHostToDevice, ctx->stream));
+        first_key = key_now;
+    }
+    uint32_t *counts = nullptr, *dest = nullptr;
+    uint64_t *tile_base = nullptr;
+    int64_t *d_off = nullptr, *h_off = nullptr;
+    int32_t *o_rows = nullptr;
+    FG_TRY(arena_get_t(ctx, (nm + ".counts").c_str(), (size_t)slots * kWavesPerBlock + 4, &counts));
+    FG_TRY(arena_get_t(ctx, (nm + ".tile_base").c_str(), (size_t)slots + 1, &tile_base));
+    FG_TRY(arena_get_t(ctx, (nm + ".group_off").c_str(), (size_t)n_parts + 1, &d_off));
+    FG_TRY(pinned_get_t(ctx, (nm + ".group_off").c_str(), (size_t)n_parts + 1, &h_off));
+    FG_TRY(arena_get_t(ctx, (nm + ".rows").c_str(), (size_t)rows + 4, &o_rows));
+    FG_TRY(arena_get_t(ctx, (nm + ".dest").c_str(), (size_t)st.n_tiles * (kFlagTile / 4) + 4, &dest));
+    if (st.n_tiles > 0) {
+        LaunchScope ls(ctx, "partition_count_kernel");
+        hipLaunchKernelGGL(partition_count_kernel, dim3((unsigned)st.n_tiles), dim3(kBlock), 0, ctx->stream, keys, rows, st, (uint32_t)n_parts, counts, dest);
+    }
+    FG_TRY(check_launch(ctx, "partition_count_kernel"));
+    FG_TRY(launch_tile_scan(ctx, counts, (int32_t)slots, tile_base, d_first, n_parts, d_off));
+    for (int p = 0; p < n_payloads && st.n_tiles > 0; ++p) {
+        LaunchScope ls(ctx, "partition_emit_table_kernel");
+        if (n_parts <= kPartLoopMax)
+            hipLaunchKernelGGL(partition_emit_table_loop_kernel, dim3((unsigned)st.n_tiles), dim3(kBlock), 0, ctx->stream, dest, st, (uint32_t)n_parts, counts, tile_base, o_rows, payloads[p]);
+        else
+            hipLaunchKernelGGL(partition_emit_table_kernel, dim3((unsigned)st.n_tiles), dim3(kBlock), 0, ctx->stream, dest, st, (uint32_t)n_parts, counts, tile_base, o_rows, payloads[p]);
+    }
+    FG_TRY(check_launch(ctx, "partition_emit_table_kernel"));
+    FG_HIP(ctx, hipMemcpyAsync(h_off, d_off, sizeof(int64_t) * ((size_t)n_parts + 1), hipMemcpyDeviceToHost, ctx->stream));
+    *d_rows = o_rows;
+    *d_group_off = d_off;
+    *h_group_off = h_off;
     return FLOCKGPU_OK;
 }
 

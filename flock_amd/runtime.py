@@ -159,6 +159,15 @@ class _Plan:
         self.gpu._check(self._lib.flockgpu_plan_execute_retain(self.h, C.byref(rows)))
         return rows.value
 
+    def exchange_retain(self, comm, gather_rank: int = -1, no_rows: bool = False) -> int:
+        """The collective twin of `execute_retain` (flockgpu_plan_exchange_retain): every rank of `comm` calls it on its instance of the
+        same stage plan; the result is hash-partitioned over the ranks by the root's hash keys -- or, `gather_rank >= 0`, sent whole to
+        that rank -- and what THIS rank receives stays on the device for `feed_from`.  `no_rows`: the plan is not executed, the rank only
+        takes part in the collectives (it hosts no instance of this stage).  Returns the rows received."""
+        rows = C.c_int64(0)
+        self.gpu._check(self._lib.flockgpu_plan_exchange_retain(self.h, comm.h, int(gather_rank), _ffi.EXCHANGE_NO_ROWS if no_rows else 0, C.byref(rows)))
+        return rows.value
+
     def feed_from(self, i: int, producer: "_Plan") -> bool:
         """Leaf i reads `producer`'s retained result in place.  False -- nothing changed -- when that result lacks a column the leaf reads."""
         rc = self._lib.flockgpu_plan_feed_from(self.h, i, producer.h)
@@ -345,6 +354,10 @@ class ExecutionContext:
     def execute_retain(self):
         """execute, with every plan's result left on the device (`_Plan.execute_retain`): [rows per plan]."""
         return [plan.execute_retain() for plan in self.plans]
+
+    def exchange_retain(self, comm, gather_rank: int = -1, no_rows: bool = False):
+        """execute_retain across the ranks of `comm` (`_Plan.exchange_retain`), plan after plan: [rows received per plan]."""
+        return [plan.exchange_retain(comm, gather_rank, no_rows) for plan in self.plans]
 
     def feed_from(self, producers: Sequence["ExecutionContext"]):
         """feed_data_sources from stages hosted on the same GPU context: every leaf takes the first remaining producer plan whose

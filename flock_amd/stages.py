@@ -246,6 +246,29 @@ def stage_levels(stages):
     return levels
 
 
+def distributed_placement(stages):
+    """How a stage DAG runs over the ranks of a communicator (`StagedRun(comm=...)`): per stage, the edge its result leaves on -- "key": hash
+    partitioned by its root repartition, "gather": everything to rank 0 -- and where it runs -- "all": on every rank, over the rank's stripe
+    or partition, "zero": on rank 0, over gathered inputs.  Raises NotImplementedError, naming the edge, for a stage that reads a gathered
+    input next to a partitioned one (or a base relation): the gathered side would have to be BROADCAST to every rank."""
+    def shuffles(plan):
+        while plan.get("execution_plan") == "coalesce_batches_exec" and isinstance(plan.get("input"), dict):
+            plan = plan["input"]
+        return plan.get("execution_plan") == "repartition_exec" and "Hash" in plan.get("partitioning", {})
+
+    edge = ["key" if shuffles(st.plan) else "gather" for st in stages]
+    where = []
+    for i, st in enumerate(stages):
+        feeders = [j for j in st.inputs if j is not None]
+        kinds = {edge[j] for j in feeders}
+        if "gather" in kinds and (len(kinds) > 1 or any(j is None for j in st.inputs)):
+            g = next(j for j in feeders if edge[j] == "gather")
+            raise NotImplementedError(f"StagedRun(comm=...): broadcast edge stage {g} -> stage {i}: the gathered result of stage {g} is read next to a "
+                                      f"partitioned input and would have to reach every rank; broadcast edges are not built")
+        where.append("zero" if kinds == {"gather"} else "all")
+    return edge, where
+
+
 class StagedRun:
     """The distributed run of a stage DAG in ONE process: every stage is a function group with its plan instantiated once
     (`ExecutionContext`), a shuffling stage is executed with `execute_partitioned` (through `collect`) by `chunks` producers over
@@ -253,7 +276,8 @@ class StagedRun:
     flock-function/src/aws/actor.rs:425-543 without the Lambda invocations in between.  What the reference's
     `launcher/aws` differential tests do with real functions (flock/src/launcher/aws/mod.rs:423-468)."""
 
-    def __init__(self, gpu, stages: List[Stage], chunks: int = 1, instances: int = 0, share_sources: bool = False, on_device: bool = False):
+    def __init__(self, gpu, stages: List[Stage], chunks: int = 1, instances: int = 0, share_sources: bool = False, on_device: bool = False,
+                 comm=None):
         """instances: function instances of a consuming stage.  0 = one per hash partition (the reference's default: the stage's
         concurrency equals its input partitioning); k > 0 = partition p goes to instance p % k, which feeds everything it is sent
         into ONE execute -- a GPU function hosting several partitions.  The union over the instances is the same multiset either
@@ -264,9 +288,21 @@ class StagedRun:
         `ExecutionContext.share_data_sources`): q5's two subplans both scan `bid`.
         on_device: one instance per stage, and a stage's result stays in HBM for the stages that consume it
         (`flockgpu_plan_execute_retain` / `flockgpu_plan_feed_from`): only the base relations come from the host and only the last
-        stage's result goes back to it."""
+        stage's result goes back to it.
+        comm: this object is ONE RANK's part of a distributed run over the ranks of `comm` (a `flock_amd.Comm`; implies on_device).  Every
+        rank builds it over the same stages and calls `run` with ITS stripe of the base relations.  A stage that is not the last hands its
+        result over with `exchange_retain` (flockgpu_plan_exchange_retain) instead of `execute_retain`: a shuffling stage by the key of its
+        root repartition, any other stage -- the input of a CoalescePartitions / Merge, of a sort, of a Final aggregate -- gathered on rank 0,
+        and the stage that consumes gathered inputs runs on rank 0 only (the other ranks take part in the collectives it still owes with
+        `no_rows`).  `run` returns the root stage's batches of this rank: empty where the rank hosts no instance of it.  A stage that reads a
+        gathered input next to a partitioned one would need that input on every rank -- a broadcast edge (q5's `num = maxn` join on the
+        generic operators): refused by name, not built."""
         from .runtime import ExecutionContext
         self.stages, self.chunks, self.instances, self.share_sources, self.on_device = stages, chunks, instances, share_sources, on_device
+        self.comm = comm
+        if comm is not None:
+            self.on_device = True
+            self._edge, self._where = distributed_placement(stages)
         self.ctxs = [ExecutionContext([st.plan], name=f"stage-{i}", gpu=gpu) for i, st in enumerate(stages)]
 
     def close(self):
@@ -276,6 +312,8 @@ class StagedRun:
     def run(self, relations):
         """relations: {name: RecordBatch} of the base relations (one window).  Returns the root stage's batches."""
         from .runtime import collect
+        if self.comm is not None:
+            return self._run_distributed(relations)
         if self.on_device:
             return self._run_on_device(relations)
         outputs = {}
@@ -341,6 +379,30 @@ class StagedRun:
                     out = ctx.execute()[0]
                 else:
                     ctx.execute_retain()
+        finally:
+            for ctx in reversed(self.ctxs):   # consumers first: a producer's buffers are only released once nothing reads them
+                ctx.clean_data_sources()
+        return out
+
+    def _run_distributed(self, relations):
+        src = [[[rb]] for rb in relations.values()]
+        last, rank = len(self.stages) - 1, self.comm.rank
+        donor, out = None, []
+        try:
+            for i, (st, ctx) in enumerate(zip(self.stages, self.ctxs)):
+                here = self._where[i] == "all" or rank == 0
+                if here:
+                    if any(j is None for j in st.inputs):
+                        if donor is None or not (self.share_sources and ctx.share_data_sources(donor)):
+                            ctx.feed_data_sources(src)
+                            donor = donor or ctx
+                    feeders = [self.ctxs[j] for j in st.inputs if j is not None]
+                    if feeders:
+                        ctx.feed_from(feeders)
+                if i == last:
+                    out = ctx.execute()[0] if here else []
+                else:
+                    ctx.exchange_retain(self.comm, -1 if self._edge[i] == "key" else 0, no_rows=not here)
         finally:
             for ctx in reversed(self.ctxs):   # consumers first: a producer's buffers are only released once nothing reads them
                 ctx.clean_data_sources()

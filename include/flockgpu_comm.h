@@ -14,11 +14,16 @@
  *   -> one all-to-all per column buffer  -> regroup (source, window) runs into windows  -> the single-GPU operator.
  * The result stays sharded by key: rank r returns the rows whose key it owns.  Which rank owns a key is unobservable
  * in the union (the reference hashes with ahash).
+ *
+ * Beside the three query exchanges (q3 / q5 / q8: Int32 keys, their own column structs, windows regrouped on arrival) there is ONE
+ * generic exchange for everything else the stage splitter cuts: flockgpu_plan_exchange_retain moves the result of any stage plan --
+ * every column type of the plan boundary, validity included, one window per call -- and leaves it where flockgpu_plan_feed_from reads it.
  */
 #ifndef FLOCKGPU_COMM_H
 #define FLOCKGPU_COMM_H
 
 #include "flockgpu.h"
+#include "flockgpu_plan.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -73,6 +78,36 @@ int flockgpu_q3_join_exchange(flockgpu_ctx *ctx, flockgpu_comm *comm, const floc
 int flockgpu_q8_join_exchange(flockgpu_ctx *ctx, flockgpu_comm *comm, const flockgpu_person_cols *person,
                               const flockgpu_windows *person_win, const flockgpu_auction_cols *auction,
                               const flockgpu_windows *auction_win, flockgpu_q8_result *out);
+
+/* ---- any stage plan's result across the ranks: the collective twin of flockgpu_plan_execute_retain (flockgpu_plan.h).  Every rank calls
+ * it on ITS instance of the same stage plan, in the same order, where the consumers of the stage live on other ranks: the rank executes the
+ * plan over what it was fed, the result is hash-partitioned over the ranks of `comm` and moved by the library's own all-to-all (one per
+ * column buffer), and what the rank RECEIVES is left on the device as the plan's retained result -- flockgpu_plan_feed_from(consumer,
+ * input, plan) then works exactly as after execute_retain, with the same lifetime rule.  *rows = the rows received.
+ *   gather_rank == -1: the root must be a RepartitionExec Hash (anything else: FLOCKGPU_ERR_INVALID; HashDiff: FLOCKGPU_ERR_UNSUPPORTED).
+ *     Rows are placed as flockgpu_plan_execute_partitioned places them, with the partition count replaced by the communicator's size:
+ *     the root's first hash column as a 64-bit key (Utf8 through its 64-bit hash, every NULL key the same key),
+ *         dest = (fmix32(fold32(key)) * n_ranks) >> 32,   fold32(k) = low word ^ high word.
+ *     The plan's OWN partition count is ignored: the consumers are the ranks here.  A filter directly below the repartition is composed
+ *     with the send order, not materialised.
+ *   gather_rank in [0, n_ranks): every row goes to that rank whatever the root is (a root hash repartition is skipped as execute_retain
+ *     skips it): the edge under CoalescePartitionsExec / MergeExec.
+ *   FLOCKGPU_EXCHANGE_NO_ROWS: the plan is not executed and the rank contributes no rows, but takes part in every collective -- for a
+ *     rank that hosts no instance of this stage.
+ * Rank r then holds the rows of all ranks destined to r: sources in rank order, inside a source in the order of the source's result --
+ * the same rows in the same order on every run.  With one rank the result is execute_retain's, row for row.
+ * Columns: Int32, Int64, UInt64, Float64, Timestamp(ms) and any number of Utf8 columns, with their validity bytes.  A received column
+ * carries validity when ANY rank's column does (agreed in the counts message; ranks without NULLs send ones); an all-NULL column (MAX
+ * over nothing) arrives as zeros in the validity bytes with unspecified values.
+ * Agreed before any data moves, in the counts exchange: a 64-bit fingerprint of the root schema (names, types, order), the hash column
+ * and gather_rank -- a mismatch is FLOCKGPU_ERR_INVALID on EVERY rank; the receiver-side limits of 2^31 rows and 2^31 bytes per Utf8
+ * column per rank -- the overflowing rank returns FLOCKGPU_ERR_UNSUPPORTED, the others FLOCKGPU_ERR_PEER; a rank whose execute failed
+ * returns its own status, the others FLOCKGPU_ERR_PEER ("Failure semantics" below).  Returned at once, before any collective: a null
+ * pointer, a gather_rank out of range, unknown flag bits, an asynchronous execute pending on the plan, a dead communicator.
+ * One call is one window; up to 64 ranks; flockgpu_comm_set_max_piece_bytes and the phase timeline (execute, partition+take, counts,
+ * all_to_all) apply as for the query exchanges, on all three transports.  No host wait beyond those of the exchange itself. */
+#define FLOCKGPU_EXCHANGE_NO_ROWS 1u
+int flockgpu_plan_exchange_retain(flockgpu_plan *plan, flockgpu_comm *comm, int gather_rank, uint32_t flags, int64_t *rows);
 
 /* Host barrier + stream synchronisation across the ranks (benchmark bracketing). */
 int flockgpu_comm_barrier(flockgpu_ctx *ctx, flockgpu_comm *comm);
