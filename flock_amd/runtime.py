@@ -58,6 +58,7 @@ class _Plan:
         self.is_shuffling = bool(self._lib.flockgpu_plan_is_shuffling(h))
         self.partitions = self._lib.flockgpu_plan_output_partitions(h)
         self._fed = []   # the library borrows fed buffers until execute / reset returns (flockgpu_plan.h)
+        self._base_fed = set()   # leaves that `feed` / `feed_shared` gave a base relation since the last reset: `feed_from` passes them by
         self._match_cache = {}
 
     def close(self):
@@ -113,6 +114,7 @@ class _Plan:
                 _release(C.addressof(ab), 64)
             _release(C.addressof(sbuf), 56)
         self.gpu._check(rc)
+        self._base_fed.add(i)
 
     def prefetch(self, i: int, batches: Sequence, pane: int) -> bool:
         """The NEXT pane's batches of leaf i start moving to the device now, beside whatever the plan is executing
@@ -151,6 +153,7 @@ class _Plan:
         if rc == _ffi.ERR_UNSUPPORTED:
             return False
         self.gpu._check(rc)
+        self._base_fed.add(i)
         return True
 
     def execute_retain(self) -> int:
@@ -197,6 +200,7 @@ class _Plan:
     def reset(self):
         self.gpu._check(self._lib.flockgpu_plan_reset(self.h))
         self._fed = []
+        self._base_fed = set()
 
     # -- asynchronous execute (flockgpu_plan_execute_async / flockgpu_plan_wait)
     def execute_async(self, partitioned: bool = False):
@@ -361,13 +365,20 @@ class ExecutionContext:
 
     def feed_from(self, producers: Sequence["ExecutionContext"]):
         """feed_data_sources from stages hosted on the same GPU context: every leaf takes the first remaining producer plan whose
-        retained result holds the columns it reads (matched by name and type, as compare_schema matches batches)."""
+        retained result holds the columns it reads (matched by name and type, as compare_schema matches batches).  A leaf that
+        feed_data_sources / share_data_sources already gave a base relation keeps it: a stage may read one next to its producers
+        (a union of a scan and an aggregate, cut at the aggregate's repartition).  Returns how many producer plans found a leaf."""
         left = [p for ctx in producers for p in ctx.plans]
+        taken = 0
         for plan in self.plans:
             for i in range(len(plan.inputs)):
+                if i in plan._base_fed:
+                    continue
                 hit = next((p for p in left if plan.feed_from(i, p)), None)
                 if hit is not None:
                     left.remove(hit)
+                    taken += 1
+        return taken
 
     def _concurrent(self) -> bool:   # every plan on its own GpuContext: their executes can be in flight together
         return len(self.plans) > 1 and len({id(p.gpu) for p in self.plans}) == len(self.plans)

@@ -250,7 +250,21 @@ def distributed_placement(stages):
     """How a stage DAG runs over the ranks of a communicator (`StagedRun(comm=...)`): per stage, the edge its result leaves on -- "key": hash
     partitioned by its root repartition, "gather": everything to rank 0 -- and where it runs -- "all": on every rank, over the rank's stripe
     or partition, "zero": on rank 0, over gathered inputs.  Raises NotImplementedError, naming the edge, for a stage that reads a gathered
-    input next to a partitioned one (or a base relation): the gathered side would have to be BROADCAST to every rank."""
+    input next to a partitioned one (or a base relation): the gathered side would have to be BROADCAST to every rank.
+
+    A stage on "all" sees a stripe of a base relation or one hash partition of a producer, never the whole input, so its plan must give, rank by
+    rank, results whose union is the result over the whole input.  Raises NotImplementedError, naming the stage and the node kind, where it does not
+    (after the broadcast refusal, which keeps its precedence).  Allowed on "all":
+      * row-wise nodes anywhere: `memory_exec`, `coalesce_batches_exec`, `filter_exec`, `projection_exec`, `union_exec` with every one of its
+        inputs, `hash_aggregate_exec` in mode Partial, and a `repartition_exec` that is no Hash (the planner's RoundRobinBatch shuffles nothing);
+      * the edge the result leaves on, at the stage's root only (under an optional `coalesce_batches_exec`): a `repartition_exec` Hash, or the
+        `coalesce_partitions_exec` / `merge_exec` whose input a gather edge carries;
+      * a `hash_join_exec` in mode Partitioned or a `hash_aggregate_exec` in mode FinalPartitioned whose every leaf in the stage is reached
+        through row-wise nodes alone and is fed by a "key" edge -- not a base relation, a gather edge, an inner repartition or a
+        `coalesce_partitions_exec`.  WHICH column the producer hashed on stays the caller's business: that the key edge places rows by the
+        key the join or the aggregate groups on is not checked here (both splitters cut the planner's own repartitions, which do).
+    Everything else is refused there -- `sort_exec`, `global_limit_exec`, `window_agg_exec`, `cross_join_exec`, a Final aggregate, a repartition or
+    a gather below the root: each needs every row of its input in one place.  A stage on "zero" reads gathered inputs whole and takes anything."""
     def shuffles(plan):
         while plan.get("execution_plan") == "coalesce_batches_exec" and isinstance(plan.get("input"), dict):
             plan = plan["input"]
@@ -266,7 +280,65 @@ def distributed_placement(stages):
             raise NotImplementedError(f"StagedRun(comm=...): broadcast edge stage {g} -> stage {i}: the gathered result of stage {g} is read next to a "
                                       f"partitioned input and would have to reach every rank; broadcast edges are not built")
         where.append("zero" if kinds == {"gather"} else "all")
+    for i, st in enumerate(stages):
+        if where[i] == "all":
+            _check_sound_over_partitions(i, st, edge)
     return edge, where
+
+
+_ROW_WISE = ("memory_exec", "coalesce_batches_exec", "filter_exec", "projection_exec", "union_exec")
+_GATHERS = ("coalesce_partitions_exec", "merge_exec")
+
+
+def _check_sound_over_partitions(i: int, st: Stage, edge: List[str]):
+    """`distributed_placement`'s rule for a stage that runs on every rank; raises NotImplementedError naming stage `i` and the node kind."""
+    fed_by = {id(lf): j for lf, j in zip(leaves_bfs(st.plan), st.inputs)}
+
+    def refuse(kind, why):
+        raise NotImplementedError(f"StagedRun(comm=...): stage {i} runs on every rank over a stripe or a partition of its input, where its {kind} is not "
+                                  f"sound: {why}")
+
+    def is_row_wise(n):
+        kind = n.get("execution_plan")
+        return (kind in _ROW_WISE or kind == "hash_aggregate_exec" and n.get("mode") == "Partial"
+                or kind == "repartition_exec" and "Hash" not in n.get("partitioning", {}))   # (RoundRobinBatch: batches for the planner's threads)
+
+    def keyed_leaves_only(n):
+        """every leaf below `n` is reached through row-wise nodes alone and is fed by a "key" edge"""
+        if not is_row_wise(n):
+            return False
+        if n.get("execution_plan") == "memory_exec":
+            j = fed_by.get(id(n))
+            return j is not None and edge[j] == "key"
+        return all(keyed_leaves_only(c) for c in _children(n))
+
+    def visit(n):
+        kind = n.get("execution_plan")
+        if is_row_wise(n):
+            pass
+        elif kind == "hash_join_exec" and n.get("mode") == "Partitioned" or kind == "hash_aggregate_exec" and n.get("mode") == "FinalPartitioned":
+            if not all(keyed_leaves_only(c) for c in _children(n)):
+                refuse(kind, "every input of it must reach it, through row-wise nodes alone, from a stage that hash-partitions its result (a \"key\" "
+                             "edge); cut the plan with split_at_repartitions where a repartition lies below it in this stage")
+        elif kind == "repartition_exec":
+            refuse(kind, "a hash repartition below the stage's root moves no rows between ranks; split_at_repartitions cuts the plan at every "
+                         "inner repartition")
+        elif kind in _GATHERS:
+            refuse(kind, "a gather below the stage's root gathers one rank's rows only; split_at_repartitions makes it a gather edge")
+        else:
+            what = f"{kind} ({n.get('mode')})" if kind == "hash_aggregate_exec" else kind
+            refuse(what, "it needs every row of its input in one place: a gather edge below it -- a stage cut under it, or under a "
+                         "coalesce_partitions_exec -- runs it on rank 0 alone")
+        for c in _children(n):
+            visit(c)
+
+    root = st.plan
+    while root.get("execution_plan") == "coalesce_batches_exec" and isinstance(root.get("input"), dict):
+        root = root["input"]
+    if (root.get("execution_plan") == "repartition_exec" and "Hash" in root.get("partitioning", {}) or root.get("execution_plan") in _GATHERS) \
+            and isinstance(root.get("input"), dict):
+        root = root["input"]          # the edge the result leaves on
+    visit(root)
 
 
 class StagedRun:
@@ -296,7 +368,8 @@ class StagedRun:
         and the stage that consumes gathered inputs runs on rank 0 only (the other ranks take part in the collectives it still owes with
         `no_rows`).  `run` returns the root stage's batches of this rank: empty where the rank hosts no instance of it.  A stage that reads a
         gathered input next to a partitioned one would need that input on every rank -- a broadcast edge (q5's `num = maxn` join on the
-        generic operators): refused by name, not built."""
+        generic operators): refused by name, not built.  So is a stage that would run on every rank and is not sound over stripes or
+        partitions -- a sort over a striped scan, an aggregate finished below an inner repartition (`distributed_placement`)."""
         from .runtime import ExecutionContext
         self.stages, self.chunks, self.instances, self.share_sources, self.on_device = stages, chunks, instances, share_sources, on_device
         self.comm = comm
@@ -309,6 +382,25 @@ class StagedRun:
         for c in self.ctxs:
             c.close()
 
+    def _sources(self, i, relations):
+        """The base relations stage i is fed.  All of them -- feed_data_sources matches them to the leaves by column names -- unless the stage
+        reads producers as well: then only those that share a column name with one of its base leaves, so that no relation lands in a leaf a
+        producer feeds (a join input cut off above the projection of a relation still carries that relation's column names)."""
+        st = self.stages[i]
+        if all(j is None for j in st.inputs):
+            return list(relations.values())
+        base = [{f["name"] for f in lf["schema"]["fields"]} for lf, j in zip(leaves_bfs(st.plan), st.inputs) if j is None]
+        return [rb for rb in relations.values() if any(names & set(rb.schema.names) for names in base)]
+
+    def _feed_from(self, i, ctx):
+        """Stage i's leaves read the retained results of the stages that feed it.  Next to a base relation every producer must find its leaf: one
+        that does not means a relation took that leaf, and the stage would answer over the wrong rows."""
+        st = self.stages[i]
+        feeders = [self.ctxs[j] for j in st.inputs if j is not None]
+        if feeders and ctx.feed_from(feeders) != len(feeders) and any(j is None for j in st.inputs):
+            raise RuntimeError(f"StagedRun: stage {i} reads base relations next to the results of stages {[j for j in st.inputs if j is not None]}, "
+                               f"and not every result found its leaf")
+
     def run(self, relations):
         """relations: {name: RecordBatch} of the base relations (one window).  Returns the root stage's batches."""
         from .runtime import collect
@@ -317,7 +409,7 @@ class StagedRun:
         if self.on_device:
             return self._run_on_device(relations)
         outputs = {}
-        base = [i for i, st in enumerate(self.stages) if any(j is None for j in st.inputs)]
+        base = [i for i, st in enumerate(self.stages) if all(j is None for j in st.inputs)]
         if self.share_sources and self.chunks == 1 and len(base) > 1:
             # one upload per relation: the first source stage is fed, the others read its device copy; all execute before any cleans
             src = [[[rb]] for rb in relations.values()]
@@ -336,7 +428,12 @@ class StagedRun:
                 continue
             feeders = [j for j in st.inputs if j is not None]
             invocations = []
-            if any(j is None for j in st.inputs):
+            if feeders and any(j is None for j in st.inputs):
+                # a stage that reads a base relation NEXT TO its producers (a union of a scan and an aggregate, cut at the aggregate's repartition):
+                # one invocation takes the whole relation and every partition of every producer -- an instance per partition would read the
+                # relation once per instance
+                invocations.append([[[rb]] for rb in self._sources(i, relations)] + [[[b for part in outputs[j] for b in part]] for j in feeders])
+            elif not feeders:
                 for c in range(self.chunks):
                     src = []
                     for rb in relations.values():
@@ -369,12 +466,13 @@ class StagedRun:
         donor, out = None, None
         try:
             for i, (st, ctx) in enumerate(zip(self.stages, self.ctxs)):
-                if any(j is None for j in st.inputs):
+                if all(j is None for j in st.inputs):
                     if donor is None or not (self.share_sources and ctx.share_data_sources(donor)):
                         ctx.feed_data_sources(src)
                         donor = donor or ctx
-                else:
-                    ctx.feed_from([self.ctxs[j] for j in st.inputs if j is not None])
+                elif any(j is None for j in st.inputs):
+                    ctx.feed_data_sources([[[rb]] for rb in self._sources(i, relations)])
+                self._feed_from(i, ctx)   # (also next to a base relation: feed_from passes the leaves that hold one by)
                 if i == last:
                     out = ctx.execute()[0]
                 else:
@@ -392,13 +490,13 @@ class StagedRun:
             for i, (st, ctx) in enumerate(zip(self.stages, self.ctxs)):
                 here = self._where[i] == "all" or rank == 0
                 if here:
-                    if any(j is None for j in st.inputs):
+                    if all(j is None for j in st.inputs):
                         if donor is None or not (self.share_sources and ctx.share_data_sources(donor)):
                             ctx.feed_data_sources(src)
                             donor = donor or ctx
-                    feeders = [self.ctxs[j] for j in st.inputs if j is not None]
-                    if feeders:
-                        ctx.feed_from(feeders)
+                    elif any(j is None for j in st.inputs):
+                        ctx.feed_data_sources([[[rb]] for rb in self._sources(i, relations)])
+                    self._feed_from(i, ctx)
                 if i == last:
                     out = ctx.execute()[0] if here else []
                 else:
