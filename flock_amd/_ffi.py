@@ -132,6 +132,21 @@ class JsonColumn(C.Structure):
 JSON_INT32, JSON_INT64, JSON_UTF8 = 0, 1, 2
 
 
+class CsvField(C.Structure):
+    _fields_ = [("type", C.c_int32)]
+
+
+class CsvOptions(C.Structure):
+    _fields_ = [("delimiter", C.c_uint8), ("has_header", C.c_int32)]
+
+
+class CsvColumn(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("valid", C.c_void_p), ("null_count", C.c_int64), ("utf8", Utf8), ("utf8_bytes", C.c_int64)]
+
+
+CSV_SKIP, CSV_INT32, CSV_INT64, CSV_UINT64, CSV_FLOAT64, CSV_TIMESTAMP_MS, CSV_UTF8 = -1, 0, 1, 2, 3, 4, 5
+
+
 class Q5PartialResult(C.Structure):
     _fields_ = [("auction", C.c_void_p), ("count", C.c_void_p), ("pane_out_offsets", C.POINTER(C.c_int64)), ("rows", C.c_int64)]
 
@@ -183,6 +198,7 @@ SYMBOLS = {
     "flockgpu_inclusive_scan_i32": (_i, [_vp, _vp, _i64]),
     "flockgpu_ipc_pack_body": (_i, [_vp, C.POINTER(IpcBuffer), _i, _vp, _i64, C.POINTER(_i64)]),
     "flockgpu_json_lines_decode": (_i, [_vp, _vp, _i64, C.POINTER(JsonField), _i, C.POINTER(JsonColumn), C.POINTER(_i64)]),
+    "flockgpu_csv_decode": (_i, [_vp, _vp, _i64, C.POINTER(CsvField), _i, C.POINTER(CsvOptions), C.POINTER(CsvColumn), C.POINTER(_i64)]),
     "flockgpu_q5_partial_counts": (_i, [_vp, C.POINTER(BidCols), C.POINTER(Windows), C.POINTER(Q5PartialResult)]),
     "flockgpu_q5_hot_items_weighted": (_i, [_vp, _vp, _vp, _i64, C.POINTER(Windows), C.POINTER(Q5Result)]),
     "flockgpu_q11_user_sessions": (_i, [_vp, C.POINTER(BidCols), C.POINTER(_i64), _i, _i, _i64, C.POINTER(Q11Result)]),

@@ -614,6 +614,57 @@ class GpuContext:
                 out[name] = col
         return out, n
 
+    def csv_decode(self, text, fields, delimiter=",", has_header=True, borrow=False):
+        """Delimited text (uint8 device tensor, 16-byte aligned) -> columns (flockgpu_csv_decode; the rules are A-CSV1..7 in csrc/csv.hpp).
+        `fields` lists EVERY column of the file in file order: [(name, "int32" | "int64" | "uint64" | "float64" | "timestamp_ms" | "utf8" | None)],
+        None = skip the column (a '.tbl' line ends in '|': one more skipped column).  Returns ({name: tensor | DeviceUtf8}, {name: validity
+        tensor (uint8, 1 = not NULL) of the numeric columns that hold NULLs}, rows).  int32 / float64 columns come as such, int64 / timestamp_ms
+        as int64, uint64 as an int64 tensor that holds the 64 bits.  borrow: views of the library's own result columns (valid until the next call
+        on this context) instead of copies, as in json_lines_decode."""
+        torch = _torch()
+        kinds = {None: _ffi.CSV_SKIP, "int32": _ffi.CSV_INT32, "int64": _ffi.CSV_INT64, "uint64": _ffi.CSV_UINT64, "float64": _ffi.CSV_FLOAT64,
+                 "timestamp_ms": _ffi.CSV_TIMESTAMP_MS, "utf8": _ffi.CSV_UTF8}
+        delim = delimiter.encode() if isinstance(delimiter, str) else bytes(delimiter)
+        if len(delim) != 1:
+            raise ValueError("csv_decode: the delimiter is one byte")
+        spec = (_ffi.CsvField * len(fields))(*[_ffi.CsvField(kinds[t]) for _, t in fields])
+        opt = _ffi.CsvOptions(delim[0], 1 if has_header else 0)
+        cols = (_ffi.CsvColumn * len(fields))()
+        rows = C.c_int64(0)
+        self._check(self._lib.flockgpu_csv_decode(self._h, text.data_ptr(), text.numel(), spec, len(fields), C.byref(opt), cols, C.byref(rows)))
+        n, dev, out, valid = rows.value, f"cuda:{self.device}", {}, {}
+
+        def take(ptr, count, dtype, width):
+            if borrow:
+                return self._device_view(ptr, count, dtype)
+            t = torch.empty(count, dtype=dtype, device=dev)
+            if count:
+                self._check(self._lib.flockgpu_memcpy(self._h, t.data_ptr(), ptr, count * width, _ffi.D2D))
+            return t
+
+        for (name, t), c in zip(fields, cols):
+            if t is None:
+                continue
+            if t == "utf8":
+                if borrow:
+                    out[name] = DeviceUtf8(self._device_view(c.utf8.offsets, n + 1, torch.int32), self._device_view(c.utf8.data, int(c.utf8_bytes), torch.uint8))
+                    continue
+                off = take(c.utf8.offsets, n + 1, torch.int32, 4) if n else torch.zeros(1, dtype=torch.int32, device=dev)
+                data = torch.empty(max(int(c.utf8_bytes), 16), dtype=torch.uint8, device=dev)
+                if c.utf8_bytes:
+                    self._check(self._lib.flockgpu_memcpy(self._h, data.data_ptr(), c.utf8.data, int(c.utf8_bytes), _ffi.D2D))
+                out[name] = DeviceUtf8(off, data)
+                continue
+            if t == "int32":
+                out[name] = take(c.values, n, torch.int32, 4)
+            elif t == "float64":   # (the view helper knows integer types: the bits, then the type)
+                out[name] = take(c.values, n, torch.int64, 8).view(torch.float64)
+            else:
+                out[name] = take(c.values, n, torch.int64, 8)
+            if c.null_count:
+                valid[name] = take(c.valid, n, torch.uint8, 1)
+        return out, valid, n
+
     def q5_partial_counts(self, bids: Bids, windows: WindowSchedule):
         """q5.dag's Partial stage: COUNT(*) GROUP BY auction per PANE of the schedule.  Returns (auction int32 tensor, count
         int32 tensor holding uint32 counts, pane_out_offsets np.int64[n_panes + 1])."""

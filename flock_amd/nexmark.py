@@ -212,6 +212,20 @@ def synthetic_side_input(ctx: GpuContext, stream: NEXMarkStream, stride: int = 6
     return key, key * 7 + 1
 
 
+# `side_input_schema()` of the reference (flock-function/src/aws/actor.rs:575-629): two non-nullable Int32 columns, read with a header and ','
+SIDE_INPUT_CSV_SCHEMA = [("key", "int32"), ("value", "int32")]
+
+
+def side_input_from_csv(ctx: GpuContext, text):
+    """q13's side input from the CSV the reference fetches from S3, decoded on the device (`text`: uint8 device tensor, 16-byte aligned):
+    csv::ReaderBuilder::has_header(true).with_delimiter(b',') with side_input_schema().  Returns (key, value) Int32 tensors, what
+    run_query(ctx, 13, stream, side_input=...) takes.  A NULL (an empty field) in either column is an error: the schema's fields are not nullable."""
+    cols, valid, _ = ctx.csv_decode(text, SIDE_INPUT_CSV_SCHEMA, delimiter=",", has_header=True)
+    if valid:
+        raise ValueError("side input: NULL in non-nullable column(s) " + ", ".join(sorted(valid)))
+    return cols["key"], cols["value"]
+
+
 def run_query(ctx: GpuContext, query_number: int, stream: NEXMarkStream, window: Optional[Window] = None, side_input=None):
     """Executes every window of the query's schedule (the per-invocation batch loop of
     flock-function: window launcher + `actor::collect`) and returns the engine's result object."""

@@ -370,6 +370,37 @@ typedef struct {
 int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json /* device */, int64_t n_bytes, const flockgpu_json_field *fields,
                                int32_t n_fields, flockgpu_json_column *out /* n_fields */, int64_t *rows);
 
+/* ---- Delimited text -> columns (csv.hip): the reference's other text format -- q13's side input (arrow's csv::ReaderBuilder with
+ * has_header(true), with_delimiter(b','), flock-function/src/aws/actor.rs:575-629) and the TPC-H '.tbl' files (CsvReadOptions with
+ * delimiter(b'|'), playground/src/distributed_plan/partition.rs:157-179).  `fields` has one entry per column OF THE FILE, in file order;
+ * SKIP columns are walked and not parsed (a '.tbl' line ends in '|': declare one more SKIP column for it).  Records end at \n or \r\n
+ * outside quotes; a field that begins with '"' is quoted, '""' inside is one '"'.  An empty field is NULL for a numeric column
+ * (valid[i] = 0, value 0) and '' for Utf8.  Float64 is converted only where one IEEE operation is exact-then-correctly-rounded (at most
+ * 2^53 as significand, a decimal exponent in [-22, 22]) and refused outside.  The full rules: A-CSV1..7 in flock_amd/csrc/csv.hpp.
+ * Errors name the first offending record (1-based, the header counted), the column and its type: malformed quoting, a wrong field count,
+ * a value that does not parse -> FLOCKGPU_ERR_INVALID; a blank line, a bare \r, a Float64 outside the exact range ->
+ * FLOCKGPU_ERR_UNSUPPORTED.  Outputs are ctx-owned and valid until the next call on the context.  `text`: device, 16-byte aligned, below
+ * 2^31 bytes; no byte at or past text + n_bytes is read.  n_fields <= 64. */
+enum { FLOCKGPU_CSV_SKIP = -1, FLOCKGPU_CSV_INT32 = 0, FLOCKGPU_CSV_INT64 = 1, FLOCKGPU_CSV_UINT64 = 2,
+       FLOCKGPU_CSV_FLOAT64 = 3, FLOCKGPU_CSV_TIMESTAMP_MS = 4, FLOCKGPU_CSV_UTF8 = 5 };
+typedef struct {
+    int32_t type; /* FLOCKGPU_CSV_* */
+} flockgpu_csv_field;
+typedef struct {
+    uint8_t delimiter;  /* any ASCII byte except '"', \r and \n */
+    int32_t has_header; /* non-zero: the first record is dropped unread */
+} flockgpu_csv_options;
+typedef struct {
+    void *values;       /* device: int32_t / int64_t / uint64_t / double per row (NULL for Utf8) */
+    uint8_t *valid;     /* device: one byte per row, 1 = not NULL; always written for numeric columns (NULL for Utf8) */
+    int64_t null_count; /* rows whose valid byte is 0 */
+    flockgpu_utf8 utf8; /* device: offsets (rows + 1) and bytes of a Utf8 column */
+    int64_t utf8_bytes;
+} flockgpu_csv_column;
+int flockgpu_csv_decode(flockgpu_ctx *ctx, const uint8_t *text /* device, 16-byte aligned */, int64_t n_bytes,
+                        const flockgpu_csv_field *fields, int32_t n_fields, const flockgpu_csv_options *opt,
+                        flockgpu_csv_column *out /* n_fields; untouched for SKIP */, int64_t *rows);
+
 /* ---- Arrow IPC body assembly: the body of the Arrow Flight data the reference builds for
  * every output batch (`flight_data_from_arrow_batch`, flock/src/transmute.rs:155-170,190-205; `Payload`,
  * flock/src/runtime/payload.rs:118-192) = the batch's buffers in field order, each padded with zeros to 8 bytes.
