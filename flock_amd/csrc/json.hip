@@ -9,14 +9,45 @@
 //   parse   : 256 lines per workgroup; their bytes are one contiguous range, staged in LDS with 16-byte loads; one lane
 //             walks one line -- first against the exact shape serde_json writes (`"name":value` in schema order, no white
 //             space, no escapes: straight-line checks), and only if that fails through the general parser: keys matched against the schema's field names, integers parsed exactly (sign, overflow),
-//             strings delimited with escape awareness, unknown keys skipped with a depth-counting value skipper.
+//             strings delimited with escape awareness, unknown members checked against the whole grammar and dropped (skip_value).
 //             Int32 / Int64 (Timestamp) columns are written directly (row = line: coalesced); for a Utf8 field the lane
 //             records where the value's bytes lie in the INPUT (start, end) and whether it holds escapes
 //   strings : a field without escapes is exactly a `take` of byte ranges of the input, so it reuses the Utf8 gather
 //             (lengths -> tile scan -> LDS-staged emit, gather.hip) with (start, end) pairs as the "offsets"; a field
 //             with escapes goes through an unescaping copy (one lane per value)
-// Numbers with a fraction or an exponent, blank lines, keys with escapes and rows that lack a schema field are reported
-// as errors with their line number (the generator's lines never have them): FLOCKGPU_ERR_UNSUPPORTED / _INVALID.
+//
+// Semantics.  The reference decodes with arrow's json::Reader over serde_json's lines; neither reader's text is under the reference, so --
+// like csv.hpp's A-CSV list -- ASSUMPTIONS, checked against tests/json_ref.py (a from-scratch decoder of exactly these rules) and, there,
+// against Python's json.loads line by line:
+//   A-JSON1 lines: every raw 0x0A ends a line (a JSON string cannot hold one).  Bytes after the last newline, if there are any, are a
+//           line as well: a last line needs no newline, and white space after the last newline is a (blank) line.  Space, TAB and CR
+//           before and after a line's object are dropped, so a trailing '\r' is white space.  An empty text is zero rows;
+//   A-JSON2 grammar: a line is ONE RFC 8259 object.  White space (space, TAB, CR) may stand wherever the RFC allows it.  A string holds
+//           no raw byte below 0x20; its escapes are \" \\ \/ \b \f \n \r \t and \uXXXX with hex digits of either case; a \u high
+//           surrogate must be followed at once by a \u low surrogate, and the pair is one code point (four UTF-8 bytes); a low surrogate on
+//           its own is malformed; \u0000 is a NUL byte of the value.  A number is -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)?; the
+//           literals are exactly true, false and null;
+//   A-JSON3 members: every line holds every schema member, in any order.  A member whose key is no schema name is checked in full against
+//           A-JSON2 -- scalars, and containers with their commas, colons and keys -- and dropped; keys INSIDE such a value are plain strings
+//           (escapes and repeats are fine).  A repeated key is fine as well and the last occurrence wins; every occurrence is checked and typed.
+//           Keys are compared with the schema names byte for byte;
+//   A-JSON4 values: an Int32 / Int64 member is a JSON integer literal, -?(0|[1-9][0-9]*), inside the type's range ("-0" is 0).  A Utf8
+//           member is a string; the column holds its bytes after unescaping.  There are no NULLs: null, or a value of any other type, is
+//           malformed for a schema member;
+//   A-JSON5 FLOCKGPU_ERR_INVALID: everything that is not A-JSON2..4 and not listed under A-JSON6 -- malformed text of any kind (in a
+//           schema member or in a dropped one), a line that is no object, bytes behind the object, a missing schema member, a value of the
+//           wrong type, an integer outside its type's range;
+//   A-JSON6 FLOCKGPU_ERR_UNSUPPORTED is only well-formed JSON that this decoder declines: a blank line; an escape in a key of the line's
+//           object (a schema name or not); a schema integer written with a well-formed fraction or exponent ("1.5", "1e3" -- but "1.", "1e"
+//           and "1x" are malformed); brackets nested more than kMaxDepth = 64 deep inside a dropped member (the member's own bracket is
+//           level 1), reported where the 65th bracket opens, whatever follows it;
+//   A-JSON7 (A-JSON-verbatim) bytes >= 0x80 between quotes are copied as they are and nothing checks that they are UTF-8 (A-CSV6's choice;
+//           the text operators downstream assume valid UTF-8, DESIGN.md A-L2: a caller that cannot vouch for its text validates it first);
+//   A-JSON8 errors name the first offending line, 1-based, whichever lane or kernel met one first.  Inside a line the first failure from
+//           the left decides, with two exceptions: a missing member is noticed at the closing brace, after everything else in the line; and a
+//           schema integer's digits are read to their end first -- then a malformed tail, then a fraction / exponent, then the range;
+//   A-JSON9 limits: 1 .. 16 fields (more: UNSUPPORTED; none: INVALID), names of 1 .. 31 bytes (UNSUPPORTED otherwise), less than 2^31 - 16 bytes
+//           of text, 16-byte aligned.
 #include <algorithm>
 #include <cstring>
 
@@ -34,7 +65,8 @@ constexpr int kParseLines = kBlock;             // lines per workgroup
 constexpr int kStageBytes = 48 * 1024;          // most LDS a workgroup stages its lines in
 
 enum : int32_t { kInt32 = 0, kInt64 = 1, kUtf8 = 2 };
-enum : uint32_t { kErrSyntax = 1, kErrNumber = 2, kErrMissing = 3, kErrBlank = 4, kErrKeyEscape = 5, kErrRange = 6 };
+constexpr int kMaxDepth = 64;                   // brackets nested inside a member that is not in the schema (A-JSON6)
+enum : uint32_t { kErrSyntax = 1, kErrNumber = 2, kErrMissing = 3, kErrBlank = 4, kErrKeyEscape = 5, kErrRange = 6, kErrDepth = 7 };
 
 struct JsonSpec {
     int32_t n;
@@ -173,43 +205,118 @@ __device__ int32_t scan_string(const Text<kLds> &t, int32_t p, int32_t end, int3
     return -1;
 }
 
-// Skips any JSON value starting at p (after white space); returns the position after it or -1.
+// The fraction and the exponent of a JSON number, each optional: (\.[0-9]+)?([eE][+-]?[0-9]+)?.  Returns the position after them, or -1
+// where one of them begins and is not well formed.
+template <bool kLds>
+__device__ int32_t skip_fraction_exponent(const Text<kLds> &t, int32_t p, int32_t end) {
+    if (p < end && t.at(p) == '.') {
+        const int32_t q = ++p;
+        while (p < end && t.at(p) - '0' <= 9u) ++p;
+        if (p == q) return -1;
+    }
+    if (p < end && (t.at(p) | 0x20u) == 'e') {
+        ++p;
+        if (p < end && (t.at(p) == '+' || t.at(p) == '-')) ++p;
+        const int32_t q = p;
+        while (p < end && t.at(p) - '0' <= 9u) ++p;
+        if (p == q) return -1;
+    }
+    return p;
+}
+
+// What follows the digits of a schema integer at p, a byte that is no delimiter: true where it is a well-formed fraction / exponent that a
+// delimiter (or the line's end) follows -- a number, only not an integer literal (A-JSON6); false where the text is malformed.
+template <bool kLds>
+__device__ bool is_fraction_exponent(const Text<kLds> &t, int32_t p, int32_t end) {
+    const uint32_t c = t.at(p);
+    if (!(c == '.' || c == 'e' || c == 'E')) return false;
+    p = skip_fraction_exponent(t, p, end);
+    if (p < 0) return false;
+    if (p >= end) return true;
+    const uint32_t d = t.at(p);
+    return d == ',' || d == '}' || is_ws(d);
+}
+
+// The value of a member that is not in the schema, checked against the whole grammar (A-JSON2, A-JSON3) and dropped.  p at the value's first
+// byte (after white space).  Returns the position after the value, or -(error code).  What follows the value is the caller's to check.
+// Containers are walked without recursion: `objs` holds one bit per open bracket (1: '{'), the innermost at bit depth - 1.
 template <bool kLds>
 __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
-    if (p >= end) return -1;
-    uint32_t c = t.at(p);
-    if (c == '"') {
-        int32_t b, e, u;
-        bool esc;
-        return scan_string(t, p, end, &b, &e, &u, &esc);
-    }
-    if (c == '{' || c == '[') {
-        int depth = 0;
-        while (p < end) {
-            c = t.at(p);
-            if (c == '"') {
-                int32_t b, e, u;
-                bool esc;
-                p = scan_string(t, p, end, &b, &e, &u, &esc);
-                if (p < 0) return -1;
+    constexpr int32_t kBad = -(int32_t)kErrSyntax;
+    uint64_t objs = 0;
+    int depth = 0;
+    enum { kValue, kFirstOrClose, kAfter };   // a value (in an object: a member) must start here; or the bracket closes at once; , or the close
+    int st = kValue;
+    for (;;) {
+        while (p < end && is_ws(t.at(p))) ++p;
+        if (p >= end) return kBad;
+        uint32_t c = t.at(p);
+        const bool in_obj = depth > 0 && ((objs >> (depth - 1)) & 1u);
+        if (st == kAfter) {
+            if (c == ',') {
+                ++p;
+                st = kValue;
                 continue;
             }
-            if (c == '{' || c == '[') ++depth;
-            if (c == '}' || c == ']') {
-                if (--depth == 0) return p + 1;
-            }
+            if (c != (uint32_t)(in_obj ? '}' : ']')) return kBad;
             ++p;
+            if (--depth == 0) return p;
+            continue;
         }
-        return -1;
+        if (st == kFirstOrClose && c == (uint32_t)(in_obj ? '}' : ']')) {
+            ++p;
+            if (--depth == 0) return p;
+            st = kAfter;
+            continue;
+        }
+        int32_t b, e, u;
+        bool esc;
+        if (in_obj) {   // "key" :
+            if (c != '"') return kBad;
+            p = scan_string(t, p, end, &b, &e, &u, &esc);
+            if (p < 0) return kBad;
+            while (p < end && is_ws(t.at(p))) ++p;
+            if (p >= end || t.at(p) != ':') return kBad;
+            ++p;
+            while (p < end && is_ws(t.at(p))) ++p;
+            if (p >= end) return kBad;
+            c = t.at(p);
+        }
+        if (c == '{' || c == '[') {
+            if (depth == kMaxDepth) return -(int32_t)kErrDepth;
+            objs = (objs & ~(uint64_t(1) << depth)) | (uint64_t(c == '{') << depth);
+            ++depth;
+            ++p;
+            st = kFirstOrClose;
+            continue;
+        }
+        if (c == '"') {
+            p = scan_string(t, p, end, &b, &e, &u, &esc);
+            if (p < 0) return kBad;
+        } else if (c == 't') {
+            if (p + 4 > end || t.at(p + 1) != 'r' || t.at(p + 2) != 'u' || t.at(p + 3) != 'e') return kBad;
+            p += 4;
+        } else if (c == 'n') {
+            if (p + 4 > end || t.at(p + 1) != 'u' || t.at(p + 2) != 'l' || t.at(p + 3) != 'l') return kBad;
+            p += 4;
+        } else if (c == 'f') {
+            if (p + 5 > end || t.at(p + 1) != 'a' || t.at(p + 2) != 'l' || t.at(p + 3) != 's' || t.at(p + 4) != 'e') return kBad;
+            p += 5;
+        } else {   // -?(0|[1-9][0-9]*) and the optional rest
+            if (c == '-') {
+                if (++p >= end) return kBad;
+                c = t.at(p);
+            }
+            if (c - '0' > 9u) return kBad;
+            ++p;
+            if (c != '0')
+                while (p < end && t.at(p) - '0' <= 9u) ++p;
+            p = skip_fraction_exponent(t, p, end);
+            if (p < 0) return kBad;
+        }
+        if (depth == 0) return p;
+        st = kAfter;
     }
-    // number / true / false / null: up to the next delimiter
-    const int32_t p0 = p;
-    while (p < end) {
-        c = t.at(p);
-        if (c == ',' || c == '}' || c == ']' || is_ws(c)) break;
-        ++p;
-    }
-    return p > p0 ? p : -1;
 }
 
 template <bool kLds>
@@ -253,7 +360,7 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
         if (p >= end) return kErrSyntax;
         if (f < 0) {
             p = skip_value(t, p, end);
-            if (p < 0) return kErrSyntax;
+            if (p < 0) return (uint32_t)-p;
         } else if (spec.type[f] == kUtf8) {
             if (t.at(p) != '"') return kErrSyntax;
             int32_t b, e, u;
@@ -274,17 +381,17 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
             if (t.at(p) == '0' && p + 1 < end && t.at(p + 1) >= '0' && t.at(p + 1) <= '9') return kErrSyntax;  // JSON has no leading zeros
             uint64_t v = 0;
             int digits = 0;
-            while (p < end) {
+            while (p < end) {   // (A-JSON8: the digits to their end, then the tail, then the range)
                 const uint32_t c = t.at(p);
                 if (c < '0' || c > '9') break;
-                if (++digits > 19) return kErrRange;
-                v = v * 10 + (c - '0');
+                if (++digits <= 19) v = v * 10 + (c - '0');
                 ++p;
             }
             if (p < end) {
                 const uint32_t c = t.at(p);
-                if (!(c == ',' || c == '}' || is_ws(c))) return kErrNumber;  // fraction / exponent: not an integer literal
+                if (!(c == ',' || c == '}' || is_ws(c))) return is_fraction_exponent(t, p, end) ? kErrNumber : kErrSyntax;  // "1.5": no integer literal; "1x", "1.": malformed
             }
+            if (digits > 19) return kErrRange;
             if (v > (uint64_t)0x7fffffffffffffffull + (neg ? 1u : 0u)) return kErrRange;
             const int64_t sv = neg ? (int64_t)(0 - v) : (int64_t)v;
             if (spec.type[f] == kInt32) {
@@ -991,9 +1098,11 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
         const long long line = (long long)(*h_err >> 8);
         const uint32_t code = (uint32_t)(*h_err & 0xFF);
         static const char *what[] = {"", "malformed JSON", "number with a fraction / exponent (integer literal expected)",
-                                     "a schema field is missing", "blank line", "escape sequence in a key", "integer out of range"};
-        return fail(ctx, code == kErrNumber || code == kErrBlank || code == kErrKeyEscape ? FLOCKGPU_ERR_UNSUPPORTED : FLOCKGPU_ERR_INVALID,
-                    "json: line %lld: %s", line + 1, what[code < 7 ? code : 1]);
+                                     "a schema field is missing", "blank line", "escape sequence in a key", "integer out of range",
+                                     "brackets nested more than 64 deep in a member that is not in the schema"};
+        static_assert(kMaxDepth == 64, "the message names the bound");
+        return fail(ctx, code == kErrNumber || code == kErrBlank || code == kErrKeyEscape || code == kErrDepth ? FLOCKGPU_ERR_UNSUPPORTED : FLOCKGPU_ERR_INVALID,
+                    "json: line %lld: %s", line + 1, what[code < 8 ? code : 1]);
     }
     int32_t *even = nullptr;
     bool have_even = false;

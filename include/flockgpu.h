@@ -352,11 +352,17 @@ int flockgpu_group_rows_by_key(flockgpu_ctx *ctx, const int32_t *keys, int64_t r
  * flock/src/datasource/nexmark/nexmark.rs:180-205): the reference keeps an epoch's events as newline-delimited
  * serde_json objects (generator.rs:79-93) and decodes them with arrow's json::Reader against the relation's schema
  * (`event_bytes_to_batch`, flock/src/transmute.rs:255-266).  Every line is one object; members are matched to `fields`
- * by name in any order, other members are skipped; row = line.  Int32 / Int64 fields take JSON integer literals (a
- * Timestamp(ms) column is Int64 here), Utf8 fields take strings (all escapes, \uXXXX surrogate pairs included).
- * Errors name the first offending line: a missing field, malformed JSON or an integer outside the type ->
- * FLOCKGPU_ERR_INVALID; a number with a fraction / exponent, a blank line, an escape inside a KEY ->
- * FLOCKGPU_ERR_UNSUPPORTED.  `json`: device text, 16-byte aligned, below 2^31 bytes per call. */
+ * by name in any order, other members are checked against the whole JSON grammar and dropped; row = line.  Int32 / Int64
+ * fields take JSON integer literals (a Timestamp(ms) column is Int64 here), Utf8 fields take strings (all escapes, \uXXXX
+ * surrogate pairs included; bytes >= 0x80 are copied as they are, nothing checks that they are UTF-8).  The rules are
+ * A-JSON1..9 at the top of csrc/json.hip.  Errors name the first offending line ("json: line N: ..."):
+ *   FLOCKGPU_ERR_INVALID      malformed JSON anywhere in the line (in a dropped member as well, "1x" or "1." for an integer
+ *                             included), a missing field, a value of the wrong type, an integer outside its type;
+ *   FLOCKGPU_ERR_UNSUPPORTED  well-formed JSON that the decoder declines: a blank line, an escape inside a KEY of the line's
+ *                             object, an integer field written with a well-formed fraction / exponent ("1.5", "1e3"), brackets
+ *                             nested more than 64 deep inside a dropped member; also more than 16 fields or a name that is
+ *                             empty or longer than 31 bytes.
+ * `json`: device text, 16-byte aligned, below 2^31 bytes per call. */
 enum { FLOCKGPU_JSON_INT32 = 0, FLOCKGPU_JSON_INT64 = 1, FLOCKGPU_JSON_UTF8 = 2 };
 typedef struct {
     const char *name; /* host, at most 31 bytes */

@@ -19,6 +19,8 @@ RUNS = [
     ("tests/test_gpu_ysb.py", ""),
     ("tests/test_gpu_q11.py", ""),
     ("tests/test_gpu_json.py", ""),
+    ("tests/test_gpu_csv.py", ""),                        # (its text-ends-at-the-end-of-its-buffer test is written for this run)
+    ("tests/test_gpu_json_edges.py", "not mutants"),      # (likewise; the 8000 five-line texts of the mutant differential end nowhere near a seam)
 ]
 
 

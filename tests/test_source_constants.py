@@ -146,3 +146,31 @@ def test_the_fused_paths_size_and_hash_as_the_collision_tests_assume():
     assert "constexpr uint32_t kLdsBuildCap = 18432;" in q3
     assert "const uint64_t cap64 = std::max<uint64_t>(64, (uint64_t)max_person_rows * 3 / 2 + 8);" in q3
     assert q3.count("slot_of((uint32_t)sv[") == 2                                 # the probes of the global tables and of the LDS build
+
+
+def test_the_json_edge_tests_restate_json_hips_constants_and_messages():
+    """tests/test_gpu_json_edges.py crafts bytes onto the seams of the line index and of the stage, and tests/json_ref.py words the errors: the tile,
+    the lines per workgroup, the stage, the formula that sizes it, the depth bound and the seven messages must be json.hip's own."""
+    import json_ref
+    j, scan = _src("json.hip"), _src("scan.hpp")
+    with open(os.path.join(ROOT, "tests", "test_gpu_json_edges.py")) as f:
+        test = f.read()
+    assert "constexpr int kBlock = 256;" in scan
+    assert "constexpr int kNlBytes = 64;" in j and "constexpr int kNlTile = kBlock * kNlBytes;" in j and "TILE = 256 * 64 " in test
+    assert "constexpr int kParseLines = kBlock;" in j and "LINES = 256 " in test
+    assert "constexpr int kStageBytes = 48 * 1024;" in j and "STAGE_MAX = 48 * 1024 " in test
+    assert "const int64_t want = (n_bytes / std::max<int64_t>(n_lines, 1) + 1) * kParseLines * 5 / 4 + 64;" in j
+    assert "want = (n_bytes // max(n_lines, 1) + 1) * LINES * 5 // 4 + 64" in test
+    assert "const int32_t stage_bytes = (int32_t)std::min<int64_t>(kStageBytes, (want + 1023) & ~int64_t(1023));" in j
+    assert "return min(STAGE_MAX, (want + 1023) & ~1023)" in test
+    assert "const int32_t a0 = b0 & ~15;" in j and "const bool staged = b1 - a0 + 16 <= stage_bytes;" in j
+    assert "return b1 - (b0 & ~15) + 16, stage_bytes(len(text), n_lines)" in test and "return span <= stage" in test
+    assert "constexpr int kMaxDepth = %d;" % json_ref.MAX_DEPTH in j
+    m = re.search(r"enum : uint32_t \{ kErrSyntax = 1, kErrNumber = 2, kErrMissing = 3, kErrBlank = 4, kErrKeyEscape = 5, kErrRange = 6, kErrDepth = 7 \};", j)
+    assert m, "json.hip's error codes are no longer the seven of tests/json_ref.py"
+    table = j[j.index("static const char *what[] = {"):]
+    table = table[:table.index("};")]
+    assert re.findall(r'"([^"]*)"', table) == [""] + [json_ref.MESSAGES[c] for c in ("malformed", "number", "missing", "blank", "key_escape", "range", "depth")]
+    status = j[j.index("return fail(ctx, code == kErrNumber"):][:200]
+    assert "code == kErrNumber || code == kErrBlank || code == kErrKeyEscape || code == kErrDepth ? FLOCKGPU_ERR_UNSUPPORTED : FLOCKGPU_ERR_INVALID" in status
+    assert sorted(c for c, s in json_ref.STATUS.items() if s == "unsupported") == ["blank", "depth", "key_escape", "number"]
