@@ -1364,7 +1364,7 @@ __device__ __forceinline__ uint64_t sort_norm(const void *__restrict__ v, const 
         case (int32_t)ColType::I64: return (uint64_t) static_cast<const int64_t *>(v)[r] ^ (uint64_t(1) << 63);
         case (int32_t)ColType::U64: return static_cast<const uint64_t *>(v)[r];
         case (int32_t)ColType::F64: {
-            const uint64_t b = static_cast<const uint64_t *>(v)[r];
+            const uint64_t b = f64_canonical_bits(static_cast<const uint64_t *>(v)[r]);   // A-FO1: the zeros tie, every NaN ties above +inf
             return (b >> 63) ? ~b : (b | (uint64_t(1) << 63));
         }
         default: {
@@ -1479,8 +1479,13 @@ __global__ __launch_bounds__(kBlock) void run_start_kernel(RunKeys k, int64_t n,
         for (int c = 0; c < k.n && !start; ++c) {
             const bool va = !k.valid[c] || k.valid[c][i], vb = !k.valid[c] || k.valid[c][i - 1];
             if (va != vb) start = true;
-            else if (va) start = k.type[c] == (int32_t)ColType::I32 ? static_cast<const int32_t *>(k.v[c])[i] != static_cast<const int32_t *>(k.v[c])[i - 1]
-                                                                    : static_cast<const uint64_t *>(k.v[c])[i] != static_cast<const uint64_t *>(k.v[c])[i - 1];
+            else if (!va) continue;
+            else if (k.type[c] == (int32_t)ColType::I32) start = static_cast<const int32_t *>(k.v[c])[i] != static_cast<const int32_t *>(k.v[c])[i - 1];
+            else {
+                uint64_t a = static_cast<const uint64_t *>(k.v[c])[i], b = static_cast<const uint64_t *>(k.v[c])[i - 1];
+                if (k.type[c] == (int32_t)ColType::F64) { a = f64_canonical_bits(a); b = f64_canonical_bits(b); }   // A-FO2
+                start = a != b;
+            }
         }
         flag[i] = start ? 1 : 0;
     }

@@ -191,11 +191,23 @@ int fold_keys_i32(flockgpu_ctx *ctx, const int64_t *keys, int64_t rows, int32_t 
 // ---- ORDER BY (SortExec; the reference's boundary goldens end in it, flock/src/runtime/context.rs:471,549, and the stage splitter
 // cuts at it, flock/src/distributed_plan/stage.rs:337): the permutation of [0, rows) that orders the rows by `keys`, first key most
 // significant, ties in input order (stable).  LSD over the keys: every key becomes an order-preserving unsigned 64-bit value in the
-// current order (Int32 / Int64 / Timestamp: sign bit flipped; UInt64: as is; Float64: IEEE total order, NaN last; Utf8: bytewise
+// current order (Int32 / Int64 / Timestamp: sign bit flipped; UInt64: as is; Float64: A-FO1 below -- the order key of the value after
+// f64_canonical_bits (orderkey.hpp), so the two zeros tie and every NaN ties above +inf; Utf8: bytewise
 // lexicographic -- the length as the least significant sub-key, then 8-byte big-endian chunks from the last to the first;
 // descending: complemented), its range is read back (one wait per sub-key; a constant sub-key costs no pass) and the stable radix
 // passes of sort.hpp run over the bits the range needs.  *out_rows: ctx-owned, `rows` entries.  Columns hold no NULLs
 // (`nulls_first` has nothing to place); an all-NULL column ties every row.
+//
+// How Float64 values order and compare.  ASSUMPTIONS: the arrow fork the reference builds against is not at hand; the rule is arrow-rs' of that
+// time (`cmp_nans_last` over `partial_cmp`), pinned by tests/float_order_ref.py.
+//   A-FO1  ORDER BY.  Ascending: -inf < ... < -5e-324 < {-0.0, +0.0} < 5e-324 < ... < +inf < {every NaN}.  The two zeros tie; all NaNs tie,
+//          whatever their sign and payload; ties keep input order (the sort is stable).  DESC is the exact reverse on values (NaNs first among
+//          the non-NULL rows), ties still in input order.  NULLs: `nulls_first` decides, DESC does not move them.
+//   A-FO2  WindowAggExec and ROW_NUMBER.  Two Float64 key values lie in one partition, or one peer group, exactly when A-FO1 ties them.
+//   A-FO3  Filters and computed comparisons are IEEE: a comparison with a NaN operand is FALSE, except `<>`, which is TRUE; -0.0 = +0.0;
+//          subnormals are numbers like any other, nothing is flushed.
+//   A-FO4  MIN / MAX compare order keys (orderkey.hpp f64_order_key): -0.0 lies below +0.0, and "no NaN among the inputs" stays the precondition.
+//   A-FO5  Values that pass through a take, a union, a cross join or an exchange keep their bits, NaN payloads included.
 struct SortKey {
     DevColumn col;
     bool descending = false;

@@ -14,6 +14,7 @@
 //   emit  : one workgroup per tile: the in-tile scan seeded with carry_in, the backward broadcast seeded with look, the finished columns
 //           (Int32 narrowed, Float64 MIN / MAX mapped back, AVG divided) and their validity bytes.
 // 16-byte loads and stores where the column's base is 16-byte aligned (every lane's 8 rows start at a multiple of 8 rows).  No host wait.
+#include "orderkey.hpp"
 #include "relops.hpp"
 #include "scan.hpp"
 
@@ -32,6 +33,7 @@ struct WinKeys {
     const void *v[kWinMaxKeys];
     const uint8_t *valid[kWinMaxKeys];
     int32_t wide[kWinMaxKeys];   // 1: 64-bit storage, 0: Int32
+    int32_t f64[kWinMaxKeys];    // Float64: compared through f64_canonical_bits (A-FO2 of relops.hpp: the zeros are one key, every NaN is one key)
     int32_t n_part, n_all;       // the first n_part columns are the PARTITION BY
 };
 struct WinAccs {
@@ -201,7 +203,8 @@ __device__ __forceinline__ uint32_t valid8(const uint8_t *p, int64_t r0, int64_t
     return m;
 }
 
-// Row flags of a lane: bits 0-7 partition starts, bits 8-15 peer-group ends of rows r0 .. r0 + 7 (rows past n: neither)
+// Row flags of a lane: bits 0-7 partition starts, bits 8-15 peer-group ends of rows r0 .. r0 + 7 (rows past n: neither).  Two Float64 key values
+// are the same key exactly when ORDER BY ties them (A-FO2, relops.hpp): the sort under the node interleaves -0.0 with +0.0 and NaNs of every pattern.
 __device__ __forceinline__ uint32_t row_flags(const WinKeys &K, int64_t r0, int64_t n, bool vec) {
     if (r0 >= n) return 0;
     uint32_t pdiff = 0, gdiff = 0;   // bit k: row r0 + k (k = 0..8) differs from row r0 + k - 1 in a PARTITION BY / any key
@@ -210,7 +213,13 @@ __device__ __forceinline__ uint32_t row_flags(const WinKeys &K, int64_t r0, int6
         load8(K.v[c], K.wide[c], r0, n, vec, v);
         const uint32_t vm = valid8(K.valid[c], r0, n, vec);
         const bool has_prev = r0 > 0, has_next = r0 + kWinRows < n;
-        const uint64_t prev = has_prev ? load1(K.v[c], K.wide[c], r0 - 1) : 0, next = has_next ? load1(K.v[c], K.wide[c], r0 + kWinRows) : 0;
+        uint64_t prev = has_prev ? load1(K.v[c], K.wide[c], r0 - 1) : 0, next = has_next ? load1(K.v[c], K.wide[c], r0 + kWinRows) : 0;
+        if (K.f64[c]) {
+#pragma unroll
+            for (int k = 0; k < kWinRows; ++k) v[k] = f64_canonical_bits(v[k]);
+            prev = f64_canonical_bits(prev);
+            next = f64_canonical_bits(next);
+        }
         const bool pv = has_prev && (!K.valid[c] || K.valid[c][r0 - 1]), nv = has_next && (!K.valid[c] || K.valid[c][r0 + kWinRows]);
         uint32_t d = 0;
 #pragma unroll
@@ -610,6 +619,7 @@ int window_aggregates(flockgpu_ctx *ctx, const char *name, const DevColumn *keys
         K.v[c] = keys[c].values;
         K.valid[c] = keys[c].valid;
         K.wide[c] = keys[c].type == ColType::I32 ? 0 : 1;
+        K.f64[c] = keys[c].type == ColType::F64 ? 1 : 0;
         vec = vec && aligned16(keys[c].values) && aligned16(keys[c].valid);
     }
     for (int i = 0; i < n_aggs; ++i) {

@@ -1,8 +1,10 @@
 """Random plans inside the claimed dialect, for tests/test_plan_differential.py: case(stratum, seed, i) -> Case(plan, tables, batch_cuts, ordered, note),
 a pure function of its three arguments (random.Random and numpy's default_rng seeded from them), so that a failure reproduces without a GPU.
 
-Exactness instead of tolerances.  Float64 inputs are k / 4 with |k| < 2^20 (every sum of up to 2^20 of them is exact in any order), never NaN and never
-both zeros in one column; Float64 literals are multiples of 1 / 4 or divisors whose quotient is ONE correctly rounded IEEE division; SUM and AVG
+Exactness instead of tolerances.  In every stratum but `float_special`, Float64 inputs are k / 4 with |k| < 2^20 (every sum of up to 2^20 of them is
+exact in any order), never NaN and never both zeros in one column; `float_special` alone draws its Float64 columns from float_order_ref.SPECIALS -- NaNs
+of four patterns, both zeros, both infinities, subnormals, +-DBL_MAX -- and only orders, compares, casts and MIN / MAXes them (MIN / MAX never see a
+NaN: column `a_f2`).  Float64 literals are multiples of 1 / 4 or divisors whose quotient is ONE correctly rounded IEEE division; SUM and AVG
 arguments are integers below 2^31 in magnitude, so every sum stays inside 64 bits and inside Float64's 53, and AVG is one correctly rounded division --
 except in `group_wide`, whose column `w` (SUM only, Int64 near 2^62) wraps on purpose.  Integer arithmetic wraps as generic_ops.eval_typed says.
 Zero divisors, INT_MIN / -1 and casts that do not fit are kept out (divisor literals are never 0 or -1, Float64 values fit Int32) except in `errors`.
@@ -27,6 +29,8 @@ import random
 
 import numpy as np
 
+import float_order_ref as fo
+
 Case = collections.namedtuple("Case", "plan tables batch_cuts ordered note")
 
 TS = {"Timestamp": ["Millisecond", None]}
@@ -38,7 +42,8 @@ WORDS = ["", "7", "07", "a", "ab", "abc", "prefix_8", "prefix_8x", "sixteen_byte
          "z" * 40, "w" * 70, "w" * 69 + "v", "été", "€", "\U0001F600", "aé€\U0001F600", "a/b/c", " pad ", "a//b", "xx/é/yy"]
 CASES_PER_SEED = 6
 STRATA = ["filter_project", "text", "group_narrow", "group_composite", "group_wide", "distinct_count", "global_agg", "join_inner", "join_semi_anti",
-          "sort_limit", "window", "cross", "mixed", "errors", "union", "cast_text", "parse_text", "errors_text"]
+          "sort_limit", "window", "cross", "mixed", "errors", "union", "cast_text", "parse_text", "errors_text",
+          "float_special"]                   # (appended: _rngs seeds from STRATA.index, so every earlier stratum's cases stay what they were)
 
 # The kernels every (stratum, seed) must run, by name as profile_read() gives them; `sort_emit_kernel` is a template with an instance per digit
 # width whose profile name may carry the width: names are matched by PREFIX.
@@ -65,6 +70,7 @@ MUST_RUN = {
     "cast_text": ("numtext_len_kernel", "numtext_emit_kernel"),
     "parse_text": ("textnum_parse_kernel",),
     "errors_text": (),
+    "float_special": ("sort_norm_kernel", "win_tile_kernel", "win_carry_kernel", "win_emit_kernel", "run_rank_kernel", "pred_flag_kernel", "valprog_kernel"),
 }
 
 
@@ -1296,12 +1302,96 @@ def r_errors_text(seed, i, rnd, r):
     return _finish(node, [t], r, rnd, False, "n=%d at=%d" % (n, at))
 
 
+# ------------------------------------------------------------------ Float64 special values (A-FO1 .. A-FO5 of relops.hpp; tests/float_order_ref.py)
+FLOAT_SIZES = [65, 700, 2047, 2049, 4095, 4097, 8193]          # (the window tile is 2048 rows, the sort tile 4096)
+FLOAT_LITERALS = [-0.0, 0.0, 5e-324, -5e-324, 1.7976931348623157e308, 1.0]
+ORDINARY = [0.25, -1.5, 3.0, 1024.75]
+# few distinct values, so that partitions and peer groups hold several rows: both zeros, NaNs of three patterns, a subnormal, -inf, two numbers
+FEW_FLOATS = [0x0000000000000000, 0x8000000000000000, 0x7FF8000000000000, 0xFFF8000000000000, 0x7FF0000000000001, 0x0000000000000001, 0xFFF0000000000000,
+              0x3FF0000000000000, 0x3FD0000000000000]
+# either side of what fits Int32, Int64 and UInt64 (tests/test_plan_float_edges.py lists what each gives)
+CAST_EDGES = [2147483647.0, 2147483647.9, 2147483648.0, -2147483648.0, -2147483648.9, -2147483649.0, 9223372036854774784.0, 9223372036854775808.0,
+              -9223372036854775808.0, -9223372036854777856.0, -0.9, -1.0, 18446744073709549568.0, 18446744073709551616.0]
+CMPS = ["Eq", "NotEq", "Lt", "LtEq", "Gt", "GtEq"]
+
+
+def _not(e):
+    return {"physical_expr": "not_expr", "arg": e}
+
+
+def _flag(cond):
+    """a condition as a projected Int32: 1 TRUE, 0 FALSE, NULL for NULL"""
+    return case_([(cond, lit("Int32", 1)), (_not(cond), lit("Int32", 0))])
+
+
+def r_float_special(seed, i, rnd, r):
+    """a_f from float_order_ref.SPECIALS, a few quarter-integers and NULLs; a_f2 from the NaN-free part (what MIN / MAX take).  case 0: ORDER BY a_f,
+    the four ASC / DESC x nulls first / last pairs over the seeds; case 1: a_f as the second key under a small Int32 key, then a limit -- in odd seeds
+    two such limits under a UNION ALL (the ordered NaN payloads cross a copy kernel); case 2: running COUNT, SUM, MIN and MAX with ORDER BY a_f under an
+    Int32 partition, the sort WITHOUT the row's number (tied zeros and NaNs arrive interleaved); case 3: PARTITION BY a_f with ROW_NUMBER and one
+    aggregate; case 4: a filter of one-pass leaves -- a_f against a literal of FLOAT_LITERALS, against a_f2 and against itself, under AND / OR / NOT
+    and IS NULL; case 5: the same comparisons on the general evaluator (a computed right side; as projected flags) and TRY_CAST(a_f AS Int32 /
+    Int64 / UInt64) over the pool widened by CAST_EDGES.  Cases 2 and 3 draw a_f from FEW_FLOATS.  CASES_PER_SEED is 6, so no case index is left
+    undirected: the mixtures ride on cases 1 and 5 by seed."""
+    n = size(seed, i, rnd, FLOAT_SIZES)
+    cols = table_cols("a") + [("a_f2", "Float64")]
+    t = make_table("a", n, r, rnd, style="dense", card=7, groups=rnd.choice([1, 5]), nulls={"g": 0.0, "v": 0.02, "i": 0.02})
+    pool = [fo.from_bits(b) for b in (FEW_FLOATS if i in (2, 3) else fo.SPECIALS)] + (ORDINARY[:1] if i in (2, 3) else ORDINARY) + (CAST_EDGES if i == 5 else [])
+    t["a_f"] = pooled(pool, n, r, rnd.choice([0.02, 0.3]))
+    t["a_f2"] = pooled([fo.from_bits(b) for b in fo.NAN_FREE] + ORDINARY, n, r, rnd.choice([0.0, 0.02, 0.3]))
+    a = scan(cols)
+    c = a.c
+    desc, nf = [(False, False), (False, True), (True, False), (True, True)][seed % 4]
+    ordered = False
+    op = lambda k: CMPS[(seed + k) % 6]
+    if i == 0:
+        node = sort(keep(a, ["a_f", "a_id", "a_v"]), [("a_f", desc, nf), ("a_id", False, False)])
+        ordered = True
+    elif i == 1:
+        src = keep(a, ["a_g", "a_f", "a_id"])
+        first = (rnd.random() < 0.5, rnd.random() < 0.5)
+        node = limit(sort(src, [("a_g",) + first, ("a_f", desc, nf), ("a_id", False, False)]), rnd.choice([50, 5000]))
+        ordered = True
+        if seed % 2:
+            node = union([node, limit(sort(src, [("a_g",) + first, ("a_f", not desc, nf), ("a_id", True, False)]), 50)])
+            ordered = False
+    elif i == 2:
+        part, order = ["a_g"], ["a_f"]
+        srt = sort(a, [("a_g", False, False), ("a_f", False, False)])
+        node = window(srt, [("count", None, part, order), ("sum", "a_v", part, order), ("min", "a_f2", part, order), ("max", "a_f2", part, order)])
+        node = keep(node, [n_ for n_, _ in node.cols[:4]] + ["a_id", "a_g", "a_f"])
+    elif i == 3:
+        part, order = ["a_f"], (["a_g"] if seed % 2 else [])
+        srt = sort(a, [("a_f", False, False)] + [(o, False, False) for o in order] + [("a_id", False, False)])
+        node = window(srt, [("row_number", None, part, []), (("sum", "a_v") if seed < 2 else ("max", "a_f2")) + (part, order)])
+        node = keep(node, [n_ for n_, _ in node.cols[:2]] + ["a_id", "a_f"] + order)
+    elif i == 4:
+        l1 = binop(c("a_f"), op(4), lit("Float64", FLOAT_LITERALS[seed % 6]))
+        l2 = binop(c("a_f"), op(1), c("a_f2"))
+        l3 = {"physical_expr": rnd.choice(["is_null_expr", "is_not_null_expr"]), "arg": c("a_f2")}
+        l4 = binop(c("a_f"), ["Eq", "NotEq", "LtEq", "Lt"][seed % 4], c("a_f"))       # TRUE for no NaN (=, <=), for every NaN (<>), for nothing (<)
+        l5 = binop(lit("Float64", rnd.choice(FLOAT_LITERALS)), op(2), c("a_f"))       # the literal on the left
+        pred = binop(binop(l1, "And", _not(l2)), "Or", binop(l4, "And", binop(l5, "Or", l3)))
+        node = keep(filt(a, pred), ["a_id", "a_f", "a_f2"])
+    else:
+        right = binop(c("a_f2"), "Plus", lit("Float64", 0.0))                          # a computed right side: no one-pass leaf, the general evaluator
+        outs = [(c("a_id"), "a_id", "Int64"), (c("a_f"), "a_f", "Float64")]
+        outs += [(cast(c("a_f"), ty, safe=True), "to_" + ty, ty) for ty in ("Int32", "Int64", "UInt64")]
+        outs += [(_flag(binop(c("a_f"), op(k), c("a_f2") if k % 2 else lit("Float64", FLOAT_LITERALS[(seed + k) % 6]))), "is%d" % k, "Int32") for k in range(3)]
+        outs.append((_flag(binop(c("a_f"), "Eq", c("a_f"))), "self", "Int32"))
+        inp = a
+        if seed % 2:
+            inp = filt(a, binop(binop(c("a_f"), op(3), right), "Or", _not(binop(c("a_f"), op(5), right))))
+        node = proj(inp, outs)
+    return Case(node.plan, [t], [cuts(n, r, rnd)], ordered, "n=%d %s nulls_first=%s" % (n, "DESC" if desc else "ASC", nf))
+
+
 ERROR_STRATA = ("errors", "errors_text")
 
 _RECIPES = {"filter_project": r_filter_project, "text": r_text, "group_narrow": r_group_narrow, "group_composite": r_group_composite, "group_wide": r_group_wide,
             "distinct_count": r_distinct_count, "global_agg": r_global_agg, "join_inner": r_join_inner, "join_semi_anti": r_join_semi_anti,
             "sort_limit": r_sort_limit, "window": r_window, "cross": r_cross, "mixed": r_mixed, "errors": r_errors,
-            "union": r_union, "cast_text": r_cast_text, "parse_text": r_parse_text, "errors_text": r_errors_text}
+            "union": r_union, "cast_text": r_cast_text, "parse_text": r_parse_text, "errors_text": r_errors_text, "float_special": r_float_special}
 
 
 def case(stratum, seed, i):

@@ -5,7 +5,7 @@ What it is made of: oracle.generic_ops (the typed expression rules: wrap-around,
 inner join's build / probe; limit), scalar_fn_ref (every scalar function), text_slice_ref (the slice functions), test_plan_like.reference_like (LIKE),
 wide_group_ref.finish (COUNT / SUM / MIN / MAX / AVG of one group: SUM wraps in 64 bits, AVG is one division), count_distinct_ref (distinct counts),
 semi_anti_ref (Semi / Anti), cross_join_ref (the pair order), union_ref (UNION ALL), cast_text_ref (integers and timestamps as text), parse_text_ref (text as
-integers and timestamps).  The tree walk, the typing of expressions that carry a function, and the window frame are
+integers and timestamps), float_order_ref (how Float64 keys order and tie: A-FO1, A-FO2, A-FO4 of relops.hpp; comparisons stay Python's IEEE).  The tree walk, the typing of expressions that carry a function, and the window frame are
 restated here; test_plan_differential.py pins the result to the reference's transcribed vectors and to every one of those modules on its own table.
 
 Where the parts disagree: generic_ops.hash_aggregate_exec adds SUM without wrapping and AVG as a running Float64 sum, wide_group_ref wraps SUM in 64 bits
@@ -22,6 +22,7 @@ import re
 import cast_text_ref as ctref
 import count_distinct_ref as dref
 import cross_join_ref as xref
+import float_order_ref as fo
 import parse_text_ref as ptref
 import scalar_fn_ref as sref
 import semi_anti_ref as saref
@@ -69,6 +70,12 @@ QUIRKS = {
     "parse_trims_blanks": "parse_text",                    # blanks around a value are skipped
     "parse_minus_zero_is_uint64_zero": "parse_text",       # `-0` is the UInt64 0
     "try_cast_bad_text_is_zero": "parse_text",             # try_cast_expr of a text that does not parse gives 0, not NULL
+    "nan_ordered_by_sign": "float_special",                # a NaN with the sign bit set sorts before -inf (the order of the bit patterns)
+    "zeros_ordered_by_sign": "float_special",              # -0.0 sorts before +0.0, whatever the input order
+    "float_peers_by_bits": "float_special",                # window partitions and peer groups compare Float64 keys by their bit patterns
+    "nan_equals_itself": "float_special",                  # f = f is TRUE for a NaN
+    "subnormals_are_zero": "float_special",                # a subnormal compares as 0
+    "float_cast_saturates": "float_special",               # a TRY_CAST of a Float64 that does not fit clamps (NaN: 0) instead of giving NULL
 }
 
 _NEUTRAL = ("coalesce_batches_exec", "repartition_exec", "coalesce_partitions_exec", "merge_exec")
@@ -171,6 +178,15 @@ def _prefix_cmp(a, b):
     if x.startswith(y):
         return -1
     return -1 if x < y else 1
+
+
+def _is_f64(ty):
+    return ty == "Float64"
+
+
+def _flush(v):
+    """subnormals_are_zero: a subnormal operand as the zero of its sign"""
+    return v * 0.0 if isinstance(v, float) and v == v and 0.0 < abs(v) < 2.2250738585072014e-308 else v
 
 
 class _Interp:
@@ -282,6 +298,9 @@ class _Interp:
                 return None if v is None else self.text_num(v, target, t == "try_cast_expr")
             if ty not in _INT and ty != "Float64":
                 raise NotImplementedError("cast to " + str(ty))
+            if v is not None and t == "try_cast_expr" and isinstance(v, float) and ty in _INT and "float_cast_saturates" in q:
+                lo, hi = _INT[ty]
+                return 0 if v != v else lo if v < lo else hi if v > hi else int(v)
             return None if v is None else g._cast(v, ty, t == "try_cast_expr")
         if t == "negative_expr":
             a = e.get("arg", e.get("expr"))
@@ -352,6 +371,10 @@ class _Interp:
                 if isinstance(a, str) and "utf8_prefix_sorts_last" in q and op not in ("Eq", "NotEq"):
                     c = _prefix_cmp(a, b)
                     return {"Lt": c < 0, "LtEq": c <= 0, "Gt": c > 0, "GtEq": c >= 0}[op]
+                if "subnormals_are_zero" in q:
+                    a, b = _flush(a), _flush(b)
+                if "nan_equals_itself" in q and isinstance(a, float) and isinstance(b, float) and a != a and b != b:
+                    return op in ("Eq", "LtEq", "GtEq")
                 return {"Eq": a == b, "NotEq": a != b, "Lt": a < b, "LtEq": a <= b, "Gt": a > b, "GtEq": a >= b}[op]
             if ty == "Float64" or isinstance(a, float) or isinstance(b, float):
                 import numpy as np
@@ -431,6 +454,21 @@ class _Interp:
         rel = self.run(node["input"])
         return rel.take(range(min(node["limit"], rel.n)))
 
+    def float_key(self, x):
+        """float_order_ref.key (A-FO1), or one of its wrong neighbours"""
+        k = fo.key(x)
+        if "nan_ordered_by_sign" in self.q and k[0] == 1 and fo.bits(x) >> 63:
+            k = (-1, 0.0)
+        if "zeros_ordered_by_sign" in self.q and k == (0, 0.0):
+            k = (0, 0.0, -1 if fo.bits(x) >> 63 else 0)
+        return k
+
+    def group_key(self, ty, v):
+        """what the window's partition / peer tests and ROW_NUMBER's runs compare (A-FO2): float_order_ref.same for Float64"""
+        if v is None or not _is_f64(ty) or not isinstance(v, float):
+            return v
+        return ("bits", fo.bits(v)) if "float_peers_by_bits" in self.q else fo.key(v)
+
     def sort_index(self, rel, specs):
         """generic_ops.sort_exec's passes (last key first, each stable) over computed key columns"""
         q = self.q
@@ -447,6 +485,8 @@ class _Interp:
             nulls = [i for i in idx if col[i] is None]
             if ty == "Utf8" and "utf8_prefix_sorts_last" in q:
                 vals.sort(key=functools.cmp_to_key(lambda i, j: _prefix_cmp(col[i], col[j])), reverse=desc)
+            elif _is_f64(ty):
+                vals.sort(key=lambda i: self.float_key(col[i]), reverse=desc)
             else:
                 vals.sort(key=lambda i: col[i], reverse=desc)
             idx = nulls + vals if nulls_first else vals + nulls
@@ -542,6 +582,8 @@ class _Interp:
             raise NotImplementedError("SUM / AVG of Float64")
         if fn in ("sum", "avg", "min", "max") and a not in ("Int32", "Int64", "UInt64", "Float64"):
             raise NotImplementedError("%s of %s" % (fn, a))
+        if fn in ("min", "max") and a == "Float64":            # A-FO4: the order of the order keys (wide_group_ref's rule where no NaN goes in)
+            return (min if fn == "min" else max)(live, key=fo.total_key) if live else None
         return wref.finish(fn, vals, n_rows, a == "UInt64")
 
     @staticmethod
@@ -661,10 +703,10 @@ class _Interp:
         for w in node["window_expr"]:
             if w.get("window_frame") is not None:
                 raise NotImplementedError("an explicit window frame")
-            part = [self.column(e, rel)[1] for e in w.get("partition_by", [])]
-            order = [self.column(s["expr"], rel)[1] for s in w.get("order_by", [])]
-            pkey = [tuple(c[i] for c in part) for i in range(n)]
-            okey = [tuple(c[i] for c in order) for i in range(n)]
+            part = [self.column(e, rel) for e in w.get("partition_by", [])]
+            order = [self.column(s["expr"], rel) for s in w.get("order_by", [])]
+            pkey = [tuple(self.group_key(ty, c[i]) for ty, c in part) for i in range(n)]
+            okey = [tuple(self.group_key(ty, c[i]) for ty, c in order) for i in range(n)]
             kind = w.get("window_expr")
             if kind == "built_in_window_expr":
                 if w.get("fun") != "RowNumber":
@@ -716,8 +758,12 @@ class _Interp:
                             if fn in ("sum", "avg"):
                                 total += v
                             elif fn in ("min", "max"):
-                                lo = v if lo is None else wref.minimum([lo, v])
-                                hi = v if hi is None else wref.maximum([hi, v])
+                                if _is_f64(ty):                   # A-FO4
+                                    lo = v if lo is None else min(lo, v, key=fo.total_key)
+                                    hi = v if hi is None else max(hi, v, key=fo.total_key)
+                                else:
+                                    lo = v if lo is None else wref.minimum([lo, v])
+                                    hi = v if hi is None else wref.maximum([hi, v])
                         if "window_frame_excludes_peers" in self.q and order:
                             out[r] = value()
                     if not ("window_frame_excludes_peers" in self.q and order):

@@ -298,7 +298,7 @@ def _leaf(node):
 
 
 def test_the_corpus_has_its_floors():
-    assert len(pc.STRATA) >= 18 and len(SEEDS) >= 4 and pc.CASES_PER_SEED >= 6 and set(pc.MUST_RUN) == set(pc.STRATA) == set(pc._RECIPES)
+    assert len(pc.STRATA) >= 19 and len(SEEDS) >= 4 and pc.CASES_PER_SEED >= 6 and set(pc.MUST_RUN) == set(pc.STRATA) == set(pc._RECIPES)
     assert set(pi.QUIRKS.values()) <= set(pc.STRATA)
     for s in pc.STRATA:
         sizes = [max(len(next(iter(t.values()))) for t in _case(s, seed, i).tables) for seed in SEEDS for i in range(pc.CASES_PER_SEED)]
