@@ -147,6 +147,17 @@ class CsvColumn(C.Structure):
 CSV_SKIP, CSV_INT32, CSV_INT64, CSV_UINT64, CSV_FLOAT64, CSV_TIMESTAMP_MS, CSV_UTF8 = -1, 0, 1, 2, 3, 4, 5
 
 
+class TextColumn(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int32), ("values", C.c_void_p), ("valid", C.c_void_p), ("utf8", Utf8)]
+
+
+class TextResult(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("n_bytes", C.c_int64)]
+
+
+TEXT_INT32, TEXT_INT64, TEXT_UINT64, TEXT_FLOAT64, TEXT_TIMESTAMP_MS, TEXT_UTF8 = 0, 1, 2, 3, 4, 5
+
+
 class Q5PartialResult(C.Structure):
     _fields_ = [("auction", C.c_void_p), ("count", C.c_void_p), ("pane_out_offsets", C.POINTER(C.c_int64)), ("rows", C.c_int64)]
 
@@ -199,6 +210,8 @@ SYMBOLS = {
     "flockgpu_ipc_pack_body": (_i, [_vp, C.POINTER(IpcBuffer), _i, _vp, _i64, C.POINTER(_i64)]),
     "flockgpu_json_lines_decode": (_i, [_vp, _vp, _i64, C.POINTER(JsonField), _i, C.POINTER(JsonColumn), C.POINTER(_i64)]),
     "flockgpu_csv_decode": (_i, [_vp, _vp, _i64, C.POINTER(CsvField), _i, C.POINTER(CsvOptions), C.POINTER(CsvColumn), C.POINTER(_i64)]),
+    "flockgpu_json_lines_encode": (_i, [_vp, C.POINTER(TextColumn), _i, _i64, C.POINTER(TextResult)]),
+    "flockgpu_csv_encode": (_i, [_vp, C.POINTER(TextColumn), _i, _i64, C.POINTER(CsvOptions), C.POINTER(TextResult)]),
     "flockgpu_q5_partial_counts": (_i, [_vp, C.POINTER(BidCols), C.POINTER(Windows), C.POINTER(Q5PartialResult)]),
     "flockgpu_q5_hot_items_weighted": (_i, [_vp, _vp, _vp, _i64, C.POINTER(Windows), C.POINTER(Q5Result)]),
     "flockgpu_q11_user_sessions": (_i, [_vp, C.POINTER(BidCols), C.POINTER(_i64), _i, _i, _i64, C.POINTER(Q11Result)]),

@@ -128,42 +128,6 @@ __global__ __launch_bounds__(kBlock) void numtext_len_kernel(const void *__restr
     if (lane_id() == 63) counts[(size_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)] = incl;
 }
 
-// The text `t` into the stage at byte p.  x = the words between two zero words; byte d of x is the one that lands on the dword boundary at or below p:
-// x moves down d >> 2 words (selects, one round per bit of the count: kMaxShift bounds it) and d & 3 bytes (a funnel shift of neighbouring words), and
-// the aligned dwords that result are stored whole where all four bytes are the value's, byte by byte at its two ends.
-template <int kWords, int kMaxShift>
-__device__ __forceinline__ void place(uint8_t *stage, uint32_t p, const NumText<kWords> &t) {
-    constexpr int kX = kWords + 2;
-    uint32_t x[kX];
-    x[0] = 0;
-#pragma unroll
-    for (int k = 0; k < kWords; ++k) x[k + 1] = t.w[k];
-    x[kWords + 1] = 0;
-    const uint32_t lo = p & 3u, hi = lo + t.len;   // bytes [lo, hi) of the aligned dwords are the value's
-    const uint32_t d = t.first + 4u - lo;          // 1 .. 4 kWords + 3
-    const uint32_t wi = d >> 2, sh = 8u * (d & 3u);
-#pragma unroll
-    for (int bit = 1; bit <= kMaxShift; bit <<= 1) {
-        const bool on = (wi & (uint32_t)bit) != 0;
-#pragma unroll
-        for (int k = 0; k < kX; ++k) x[k] = on ? (k + bit < kX ? x[k + bit] : 0u) : x[k];
-    }
-    uint8_t *q = stage + (p - lo);
-#pragma unroll
-    for (int k = 0; k <= kWords; ++k) {
-        const uint32_t b0 = 4u * (uint32_t)k;
-        if (b0 >= hi) continue;
-        const uint32_t a = __funnelshift_r(x[k], x[k + 1], sh);
-        if (b0 >= lo && b0 + 4u <= hi) {
-            *reinterpret_cast<uint32_t *>(q + b0) = a;
-        } else {
-#pragma unroll
-            for (uint32_t c = 0; c < 4u; ++c)
-                if (b0 + c >= lo && b0 + c < hi) q[b0 + c] = (uint8_t)(a >> (8u * c));
-        }
-    }
-}
-
 template <NumTextKind K>
 __global__ __launch_bounds__(kBlock) void numtext_emit_kernel(const void *__restrict__ values, const uint8_t *__restrict__ valid, int64_t n, int32_t vec,
                                                               const uint32_t *__restrict__ counts, const uint64_t *__restrict__ tile_base,
@@ -200,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void numtext_emit_kernel(const void *__rest
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (len[j] == 0) continue;
-        place<kWords, kMaxShift>(s_stage, phase + start[j], format<K>(v[j]));
+        numtext_place<kWords, kMaxShift>(s_stage, phase + start[j], format<K>(v[j]));
     }
     __syncthreads();
     for (uint32_t o = threadIdx.x * 16; o < end; o += kBlock * 16) {

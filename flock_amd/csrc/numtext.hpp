@@ -182,6 +182,44 @@ FG_HD NumText<6> numtext_ts(int64_t ms) {
     return t;
 }
 
+#if defined(__HIPCC__)
+// (device; numtext.hip, textenc.hip) The text `t` into the LDS stage at byte p.  x = the words between two zero words; byte d of x is the one that lands on the dword boundary at or below p:
+// x moves down d >> 2 words (selects, one round per bit of the count: kMaxShift bounds it) and d & 3 bytes (a funnel shift of neighbouring words), and
+// the aligned dwords that result are stored whole where all four bytes are the value's, byte by byte at its two ends.
+template <int kWords, int kMaxShift>
+__device__ __forceinline__ void numtext_place(uint8_t *stage, uint32_t p, const NumText<kWords> &t) {
+    constexpr int kX = kWords + 2;
+    uint32_t x[kX];
+    x[0] = 0;
+#pragma unroll
+    for (int k = 0; k < kWords; ++k) x[k + 1] = t.w[k];
+    x[kWords + 1] = 0;
+    const uint32_t lo = p & 3u, hi = lo + t.len;   // bytes [lo, hi) of the aligned dwords are the value's
+    const uint32_t d = t.first + 4u - lo;          // 1 .. 4 kWords + 3
+    const uint32_t wi = d >> 2, sh = 8u * (d & 3u);
+#pragma unroll
+    for (int bit = 1; bit <= kMaxShift; bit <<= 1) {
+        const bool on = (wi & (uint32_t)bit) != 0;
+#pragma unroll
+        for (int k = 0; k < kX; ++k) x[k] = on ? (k + bit < kX ? x[k + bit] : 0u) : x[k];
+    }
+    uint8_t *q = stage + (p - lo);
+#pragma unroll
+    for (int k = 0; k <= kWords; ++k) {
+        const uint32_t b0 = 4u * (uint32_t)k;
+        if (b0 >= hi) continue;
+        const uint32_t a = __funnelshift_r(x[k], x[k + 1], sh);
+        if (b0 >= lo && b0 + 4u <= hi) {
+            *reinterpret_cast<uint32_t *>(q + b0) = a;
+        } else {
+#pragma unroll
+            for (uint32_t c = 0; c < 4u; ++c)
+                if (b0 + c >= lo && b0 + c < hi) q[b0 + c] = (uint8_t)(a >> (8u * c));
+        }
+    }
+}
+#endif
+
 // byte i of the words (host tests, the emit kernel's tile edges)
 template <int kWords>
 FG_HD uint8_t numtext_byte(const NumText<kWords> &t, uint32_t i) {

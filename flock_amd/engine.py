@@ -665,6 +665,77 @@ class GpuContext:
                 valid[name] = take(c.valid, n, torch.uint8, 1)
         return out, valid, n
 
+    def _text_columns(self, columns, valid):
+        """[(name, type, tensor | DeviceUtf8)] -> (the flockgpu_text_column array, the row count, what must stay alive over the call)."""
+        kinds = {"int32": _ffi.TEXT_INT32, "int64": _ffi.TEXT_INT64, "uint64": _ffi.TEXT_UINT64, "float64": _ffi.TEXT_FLOAT64,
+                 "timestamp_ms": _ffi.TEXT_TIMESTAMP_MS, "utf8": _ffi.TEXT_UTF8}
+        valid = valid or {}
+        unknown = sorted(set(valid) - {name for name, _, _ in columns})
+        if unknown:
+            raise ValueError("text encode: validity for unknown column(s) " + ", ".join(unknown))
+        spec = (_ffi.TextColumn * max(len(columns), 1))()
+        rows, keep = None, []
+        for c, (name, t, col) in zip(spec, columns):
+            if t not in kinds:
+                raise ValueError(f"text encode: column {name!r}: unknown type {t!r}")
+            utf8 = isinstance(col, DeviceUtf8)
+            if utf8 != (t == "utf8"):
+                raise ValueError(f"text encode: column {name!r}: {t} takes a {'DeviceUtf8' if t == 'utf8' else 'tensor'}")
+            n = col.offsets.numel() - 1 if utf8 else col.numel()
+            if rows is not None and n != rows:
+                raise ValueError(f"text encode: column {name!r} has {n} rows, the columns before it {rows}")
+            rows = n
+            first = col.offsets if utf8 else col   # (a torch tensor or a GuardedBuffer: element size from the one or the other)
+            size = first.element_size() if hasattr(first, "element_size") else np.dtype(first.dtype).itemsize
+            if size != (4 if t in ("int32", "utf8") else 8):
+                raise ValueError(f"text encode: column {name!r}: {t} does not take {size}-byte elements")
+            v = valid.get(name)
+            if v is not None and v.numel() != n:
+                raise ValueError(f"text encode: validity of {name!r} has {v.numel()} entries for {n} rows")
+            key = name.encode() if isinstance(name, str) else bytes(name)
+            keep += [key, col, v]
+            c.name, c.type = key, kinds[t]
+            c.values = None if utf8 else col.data_ptr()
+            c.valid = None if v is None else v.data_ptr()
+            c.utf8 = col.ffi() if utf8 else _ffi.Utf8(None, None)
+        return spec, rows or 0, keep
+
+    def _text_result(self, res, borrow):
+        torch = _torch()
+        n = int(res.n_bytes)
+        if borrow:
+            return self._device_view(res.text, n, torch.uint8)
+        out = torch.empty(n, dtype=torch.uint8, device=f"cuda:{self.device}")
+        if n:
+            self._check(self._lib.flockgpu_memcpy(self._h, out.data_ptr(), res.text, n, _ffi.D2D))
+        return out
+
+    def json_lines_encode(self, columns, valid=None, borrow=False):
+        """Columns -> newline-delimited JSON on the device (flockgpu_json_lines_encode; the rules are A-ENC1..10 in csrc/textenc.hpp): one
+        {"name":value,...}\\n per row, what the reference's generator keeps per epoch.  `columns` = [(name, "int32" | "int64" | "uint64" |
+        "timestamp_ms" | "utf8", tensor | DeviceUtf8)] with csv_decode's type names (uint64 as an int64 tensor of the bits; a timestamp prints as
+        its integer), `valid` = {name: uint8 tensor, 1 = not NULL}.  Returns a uint8 device tensor of exactly the text's bytes: a copy, or with
+        `borrow` a view of the library's buffer (16-byte aligned, zero-padded to a multiple of 16, valid until the next call on this context)."""
+        spec, rows, keep = self._text_columns(columns, valid)
+        res = _ffi.TextResult()
+        self._check(self._lib.flockgpu_json_lines_encode(self._h, spec, len(columns), rows, C.byref(res)))
+        del keep
+        return self._text_result(res, borrow)
+
+    def csv_encode(self, columns, valid=None, delimiter=",", has_header=True, borrow=False):
+        """Columns -> delimited text on the device (flockgpu_csv_encode), the text csv_decode reads: csv_decode(csv_encode(columns, valid), fields)
+        gives the columns and their validity back, except that a NULL Utf8 comes back as ''.  Arguments and result as json_lines_encode;
+        "timestamp_ms" prints as YYYY-MM-DD HH:MM:SS[.mmm].  has_header writes one record of the names."""
+        delim = delimiter.encode() if isinstance(delimiter, str) else bytes(delimiter)
+        if len(delim) != 1:
+            raise ValueError("csv_encode: the delimiter is one byte")
+        spec, rows, keep = self._text_columns(columns, valid)
+        opt = _ffi.CsvOptions(delim[0], 1 if has_header else 0)
+        res = _ffi.TextResult()
+        self._check(self._lib.flockgpu_csv_encode(self._h, spec, len(columns), rows, C.byref(opt), C.byref(res)))
+        del keep
+        return self._text_result(res, borrow)
+
     def q5_partial_counts(self, bids: Bids, windows: WindowSchedule):
         """q5.dag's Partial stage: COUNT(*) GROUP BY auction per PANE of the schedule.  Returns (auction int32 tensor, count
         int32 tensor holding uint32 counts, pane_out_offsets np.int64[n_panes + 1])."""

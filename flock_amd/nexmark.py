@@ -200,6 +200,19 @@ def event_bytes_to_columns(ctx: GpuContext, text, relation: str):
     return ctx.json_lines_decode(text, NEXMARK_JSON_SCHEMAS[relation])
 
 
+def columns_to_event_bytes(ctx: GpuContext, relation: str, cols, borrow: bool = False):
+    """The inverse of event_bytes_to_columns: the relation's device columns -> the reference's epoch buffer, serde_json::to_vec(event) + "\\n"
+    per event (generator.rs:79-93) with the struct field order of event.rs, encoded on the device (GpuContext.json_lines_encode).  `cols`: a
+    Bids / Auctions / Persons or a {name: tensor | DeviceUtf8} mapping that holds every field of NEXMARK_JSON_SCHEMAS[relation] (the query
+    projections Auctions and Persons carry only some of them: pass a mapping for the full event).  Returns a uint8 device tensor."""
+    get = cols.get if hasattr(cols, "get") else lambda k: getattr(cols, k, None)
+    schema = NEXMARK_JSON_SCHEMAS[relation]
+    missing = [name for name, _ in schema if get(name) is None]
+    if missing:
+        raise ValueError(f"columns_to_event_bytes: the {relation} columns lack " + ", ".join(missing))
+    return ctx.json_lines_encode([(name, t, get(name)) for name, t in schema], borrow=borrow)
+
+
 def synthetic_side_input(ctx: GpuContext, stream: NEXMarkStream, stride: int = 6007):
     """A bounded q13 side input for a generated stream: key = every `stride`-th auction id the stream's bids can name,
     value = a function of the key.  (The reference reads the table from a user-supplied CSV in S3,

@@ -407,6 +407,38 @@ int flockgpu_csv_decode(flockgpu_ctx *ctx, const uint8_t *text /* device, 16-byt
                         const flockgpu_csv_field *fields, int32_t n_fields, const flockgpu_csv_options *opt,
                         flockgpu_csv_column *out /* n_fields; untouched for SKIP */, int64_t *rows);
 
+/* ---- Columns -> text (textenc.hip): the way back from the two decoders.  flockgpu_json_lines_encode writes what the reference's generator
+ * keeps per epoch -- serde_json::to_vec(event) + "\n" (flock/src/datasource/nexmark/generator.rs:79-93): {"name":value,...}\n per row, the
+ * columns in the given order, no white space; strings with serde_json's escapes (\" \\ \b \f \n \r \t, \u00xx for the other bytes below 0x20,
+ * everything else verbatim), NULL as null, a Timestamp(ms) as its integer.  flockgpu_csv_encode writes what flockgpu_csv_decode reads:
+ * fields joined by the delimiter, records ended by \n, a header record of the names when opt->has_header; a Utf8 value is quoted when it is
+ * empty or holds the delimiter, '"', \n or \r ('"' doubled); a Timestamp(ms) prints as YYYY-MM-DD HH:MM:SS[.mmm]; NULL of any type is an empty
+ * unquoted field (so a NULL Utf8 reads back as ''), and a record that would be empty is written "".  Integers print in their shortest decimal
+ * form.  The full rules: A-ENC1..10 in flock_amd/csrc/textenc.hpp.
+ *   FLOCKGPU_ERR_UNSUPPORTED  a Float64 column, more than 64 columns, a name that is empty or longer than 31 bytes (each names the column);
+ *                             a text of 2^31 - 16 bytes or more;
+ *   FLOCKGPU_ERR_INVALID      no columns, a bad delimiter, rows < 0 or >= 2^31, a Utf8 column without offsets; CSV only: a non-NULL
+ *                             Timestamp(ms) outside the years 0000..9999 -- the message names the first such record (1-based, the header
+ *                             counted) and the column.
+ * Columns may alias each other.  No byte at or past the end of a column is read.  out->text is ctx-owned, 16-byte aligned, valid until the
+ * next call on the context; its allocation is a multiple of 16 bytes with zeros behind n_bytes: both decoders read it in place. */
+enum { FLOCKGPU_TEXT_INT32 = 0, FLOCKGPU_TEXT_INT64 = 1, FLOCKGPU_TEXT_UINT64 = 2,
+       FLOCKGPU_TEXT_FLOAT64 = 3, FLOCKGPU_TEXT_TIMESTAMP_MS = 4, FLOCKGPU_TEXT_UTF8 = 5 };   /* the CSV decoder's numbering */
+typedef struct {
+    const char *name;     /* host; JSON key / CSV header cell, 1 .. 31 bytes */
+    int32_t type;         /* FLOCKGPU_TEXT_* */
+    const void *values;   /* device: int32_t / int64_t / uint64_t per row (NULL for Utf8) */
+    const uint8_t *valid; /* device, one byte per row, 1 = not NULL; NULL pointer = no NULLs */
+    flockgpu_utf8 utf8;   /* device: offsets (rows + 1) and bytes of a Utf8 column */
+} flockgpu_text_column;
+typedef struct {
+    uint8_t *text;   /* device, ctx-owned */
+    int64_t n_bytes;
+} flockgpu_text_result;
+int flockgpu_json_lines_encode(flockgpu_ctx *ctx, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows, flockgpu_text_result *out);
+int flockgpu_csv_encode(flockgpu_ctx *ctx, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows,
+                        const flockgpu_csv_options *opt /* delimiter; has_header: write one */, flockgpu_text_result *out);
+
 /* ---- Arrow IPC body assembly: the body of the Arrow Flight data the reference builds for
  * every output batch (`flight_data_from_arrow_batch`, flock/src/transmute.rs:155-170,190-205; `Payload`,
  * flock/src/runtime/payload.rs:118-192) = the batch's buffers in field order, each padded with zeros to 8 bytes.
