@@ -16,6 +16,7 @@ raises `FlockGpuError` with status FLOCKGPU_ERR_UNSUPPORTED (the reference host 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 from typing import List, Optional, Sequence, Union
@@ -42,6 +43,23 @@ def _release(addr: int, offset: int):
     fn = C.c_void_p.from_address(addr + offset).value
     if fn:
         _RELEASE(fn)(addr)
+
+
+@contextlib.contextmanager
+def _exported(batches):
+    """`batches` (not empty) and their schema as Arrow C structs: (schema pointer, array of batch pointers).  The library only borrows
+    the batches -- the caller keeps them alive -- so the exported structs are handed back as the block ends."""
+    sbuf = C.create_string_buffer(_ARROW_SCHEMA_BYTES)
+    batches[0].schema._export_to_c(C.addressof(sbuf))
+    abufs = [C.create_string_buffer(_ARROW_ARRAY_BYTES) for _ in batches]
+    for b, ab in zip(batches, abufs):
+        b._export_to_c(C.addressof(ab))
+    try:
+        yield C.cast(sbuf, C.c_void_p), (C.c_void_p * len(batches))(*[C.addressof(ab) for ab in abufs])
+    finally:
+        for ab in abufs:
+            _release(C.addressof(ab), 64)
+        _release(C.addressof(sbuf), 56)
 
 
 class _Plan:
@@ -96,23 +114,12 @@ class _Plan:
             if pane is not None:   # an empty pane still advances the ring
                 self.gpu._check(self._lib.flockgpu_plan_feed_pane(self.h, i, pane, None, None, 0))
             return
-        sbuf = C.create_string_buffer(_ARROW_SCHEMA_BYTES)
-        batches[0].schema._export_to_c(C.addressof(sbuf))
-        abufs = [C.create_string_buffer(_ARROW_ARRAY_BYTES) for _ in batches]
-        for b, ab in zip(batches, abufs):
-            b._export_to_c(C.addressof(ab))
-        ptrs = (C.c_void_p * len(batches))(*[C.addressof(ab) for ab in abufs])
         self._fed.append(batches)
-        try:
+        with _exported(batches) as (schema, ptrs):
             if pane is None:
-                rc = self._lib.flockgpu_plan_feed(self.h, i, C.cast(sbuf, C.c_void_p), ptrs, len(batches))
+                rc = self._lib.flockgpu_plan_feed(self.h, i, schema, ptrs, len(batches))
             else:
-                rc = self._lib.flockgpu_plan_feed_pane(self.h, i, pane, C.cast(sbuf, C.c_void_p), ptrs, len(batches))
-        finally:
-            # the library only borrowed the batches (self._fed keeps them alive): hand the exported structs back
-            for ab in abufs:
-                _release(C.addressof(ab), 64)
-            _release(C.addressof(sbuf), 56)
+                rc = self._lib.flockgpu_plan_feed_pane(self.h, i, pane, schema, ptrs, len(batches))
         self.gpu._check(rc)
         self._base_fed.add(i)
 
@@ -123,18 +130,8 @@ class _Plan:
         batches = [b for b in batches if b is not None]
         if not batches:
             return False
-        sbuf = C.create_string_buffer(_ARROW_SCHEMA_BYTES)
-        batches[0].schema._export_to_c(C.addressof(sbuf))
-        abufs = [C.create_string_buffer(_ARROW_ARRAY_BYTES) for _ in batches]
-        for b, ab in zip(batches, abufs):
-            b._export_to_c(C.addressof(ab))
-        ptrs = (C.c_void_p * len(batches))(*[C.addressof(ab) for ab in abufs])
-        try:
-            rc = self._lib.flockgpu_plan_prefetch_pane(self.h, i, pane, C.cast(sbuf, C.c_void_p), ptrs, len(batches))
-        finally:
-            for ab in abufs:
-                _release(C.addressof(ab), 64)
-            _release(C.addressof(sbuf), 56)
+        with _exported(batches) as (schema, ptrs):
+            rc = self._lib.flockgpu_plan_prefetch_pane(self.h, i, pane, schema, ptrs, len(batches))
         if rc == _ffi.ERR_UNSUPPORTED:
             return False
         self.gpu._check(rc)
@@ -289,24 +286,26 @@ class ExecutionContext:
             return
         if pre is not None:
             raise ValueError("feed_data_sources: pane %d was prefetched -- feed it with sources=None first" % pre["pane"])
+        fed = set()
+        for plan, i, batches in self._leaf_sources(sources):
+            plan.feed(i, batches, pane)
+            fed.add(id(plan))
+        if pane is not None:
+            for plan in self.plans:
+                if id(plan) not in fed and plan.inputs:   # nothing arrived in this pane: the ring still advances
+                    plan.feed(0, [], pane)
+
+    def _leaf_sources(self, sources):
+        """(plan, leaf, batches) for every plan leaf that finds a source: the first remaining source whose first batch matches the
+        leaf's columns by name.  A source goes to one leaf only."""
         sources = [list(s) for s in sources]
         for plan in self.plans:
-            fed_a_pane = False
             for i in range(len(plan.inputs)):
-                found = None
                 for si, partitions in enumerate(sources):
                     first = next((b for part in partitions for b in part), None)
-                    if first is None:
-                        continue
-                    if plan.matches(i, first.schema):
-                        found = si
+                    if first is not None and plan.matches(i, first.schema):
+                        yield plan, i, [b for part in sources.pop(si) for b in part]
                         break
-                if found is not None:
-                    partitions = sources.pop(found)
-                    plan.feed(i, [b for part in partitions for b in part], pane)
-                    fed_a_pane = True
-            if pane is not None and not fed_a_pane and plan.inputs:   # nothing arrived in this pane: the ring still advances
-                plan.feed(0, [], pane)
 
     def prefetch_data_sources(self, sources, pane: int):
         """The sources of pane `pane` -- the ring's NEXT pane -- matched to the leaves as feed_data_sources matches them; what a prefetch
@@ -315,24 +314,13 @@ class ExecutionContext:
         if not self._ring:
             raise ValueError("prefetch_data_sources: open a window ring first")
         pre = {"pane": pane, "moving": [], "later": []}
-        sources = [list(s) for s in sources]
-        for plan in self.plans:
-            started = False
-            for i in range(len(plan.inputs)):
-                found = None
-                for si, partitions in enumerate(sources):
-                    first = next((b for part in partitions for b in part), None)
-                    if first is not None and plan.matches(i, first.schema):
-                        found = si
-                        break
-                if found is None:
-                    continue
-                batches = [b for part in sources.pop(found) for b in part]
-                if not started and plan.prefetch(i, batches, pane):
-                    started = True
-                    pre["moving"].append((plan, i))
-                else:
-                    pre["later"].append((plan, i, batches))
+        started = set()
+        for plan, i, batches in self._leaf_sources(sources):
+            if id(plan) not in started and plan.prefetch(i, batches, pane):
+                started.add(id(plan))
+                pre["moving"].append((plan, i))
+            else:
+                pre["later"].append((plan, i, batches))
         self._pre = pre
 
     def share_data_sources(self, donor: "ExecutionContext") -> bool:

@@ -473,7 +473,7 @@ def test_rows_ring_carries_validity(gpu):
 
 @pytest.mark.gpu
 def test_prefetched_pane_behind_a_pane_with_nulls_on_the_rows_ring(gpu):
-    """ADVICE r4 (plan.hip, feed_pane's prefetch append): a small pane WITH NULLs fed the ordinary way leaves validity bytes on its columns;
+    """ADVICE r4 (plan_feed.hip, feed_pane's prefetch append): a small pane WITH NULLs fed the ordinary way leaves validity bytes on its columns;
     the next, much larger pane holds no NULL and arrives by prefetch -- its rows are appended device to device, and the scan then fills
     "valid" up to the leaf's row count.  The validity buffer has to have grown with the values (it used to be written past its end)."""
     from flock_amd.runtime import ExecutionContext
