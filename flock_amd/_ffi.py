@@ -238,6 +238,8 @@ SYMBOLS = {
     "flockgpu_plan_feed_shared": (_i, [_vp, _i, _vp, _i]),
     "flockgpu_plan_execute_retain": (_i, [_vp, C.POINTER(C.c_int64)]),
     "flockgpu_plan_feed_from": (_i, [_vp, _i, _vp]),
+    "flockgpu_plan_feed_columns": (_i, [_vp, _i, C.POINTER(TextColumn), C.c_int32, _i64, C.c_uint32]),
+    "flockgpu_plan_result_columns": (_i, [_vp, C.POINTER(TextColumn), C.c_int32, C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "flockgpu_plan_execute": (_i, [_vp, _vp, _vp]),
     "flockgpu_plan_execute_partitioned": (_i, [_vp, _vp, _vp, _i, C.POINTER(_i)]),
     "flockgpu_plan_explain": (_i, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
@@ -291,6 +293,7 @@ SYMBOLS = {
 }
 PLAN_GENERIC_ONLY = 1
 EXCHANGE_NO_ROWS = 1
+FEED_BORROW = 1
 
 _lib = None
 

@@ -3,11 +3,14 @@
 //   clean_data_sources context.rs:227-254                     -> flockgpu_plan_reset
 // and what this library adds to it: the device-side pane ring (flockgpu_plan_ring_*, flockgpu_plan_feed_pane), the prefetch of the next
 // pane (flockgpu_plan_prefetch_pane), leaves that read another plan's relation or result in place (flockgpu_plan_feed_shared / _from).
+// At the end: device columns into a leaf and a retained result out as device columns (flockgpu_plan_feed_columns / _result_columns; the kernels
+// are plan_source.hip's).
 // Host-side code only.  Each decision has one owner: check_feed / apply_feed (what a feed is, and doing it), match_schema / check_column
 // (a fed batch against the leaf), reserve_rows (room for an append), add_run / issue_runs (what travels as one copy, and how).
 #include <memory>
 #include <thread>
 
+#include "plan_source.hpp"
 #include "plan_state.hpp"
 
 using namespace flockgpu;
@@ -339,6 +342,51 @@ static int reserve_rows(flockgpu_plan *plan, int input, size_t c, int64_t add_ro
     return FLOCKGPU_OK;
 }
 
+// A leaf that reads the caller's columns in place (flockgpu_plan_feed_columns, FLOCKGPU_FEED_BORROW) becomes a leaf of its own buffers with the
+// same contents, so that a later feed can append: device-to-device copies on the ctx stream.  On failure the leaf stays as it was.
+static int own_user_columns(flockgpu_plan *plan, int input) {
+    flockgpu_ctx *ctx = plan->ctx;
+    const Leaf &lf = plan->ir.leaves[(size_t)input];
+    LeafData &ld = plan->leaves[(size_t)input];
+    const std::vector<DevBuf> user = ld.cols;
+    const int64_t rows = ld.rows;
+    for (auto &c : ld.cols) c = DevBuf{};
+    ld.rows = 0;
+    ld.borrowed = ld.user_cols = false;
+    const int rc = [&]() -> int {
+        for (size_t c = 0; c < user.size(); ++c) {
+            const DevBuf &u = user[c];
+            if (!u.values && !u.offsets) continue;
+            DevBuf &dc = ld.cols[c];
+            FG_TRY(reserve_rows(plan, input, c, rows, u.bytes));
+            if (lf.schema[c].type == ColType::UTF8) {
+                FG_HIP(ctx, hipMemcpyAsync(dc.offsets, u.offsets, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));   // (offsets[0] == 0: only such columns are read in place)
+                if (u.bytes) FG_HIP(ctx, hipMemcpyAsync(dc.values, u.values, (size_t)u.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                dc.bytes = u.bytes;
+            } else if (rows) {
+                FG_HIP(ctx, hipMemcpyAsync(dc.values, u.values, (size_t)rows * col_width(lf.schema[c].type), hipMemcpyDeviceToDevice, ctx->stream));
+            }
+            if (u.valid && u.valid_rows > 0) {
+                void *vp = nullptr;
+                FG_TRY(grow(ctx, leaf_key(plan, input, (int)c, "valid"), 0, (size_t)rows + 64, &vp));
+                dc.valid = static_cast<uint8_t *>(vp);
+                FG_HIP(ctx, hipMemcpyAsync(dc.valid, u.valid, (size_t)u.valid_rows, hipMemcpyDeviceToDevice, ctx->stream));
+                dc.valid_rows = u.valid_rows;
+            }
+        }
+        return FLOCKGPU_OK;
+    }();
+    if (rc != FLOCKGPU_OK) {
+        ld.cols = user;
+        ld.borrowed = ld.user_cols = true;
+        ld.rows = rows;
+        return rc;
+    }
+    ld.rows = rows;
+    plan->col_stats.clear();
+    return FLOCKGPU_OK;
+}
+
 // feed_data_sources for one leaf, second half: the checked batches are appended behind the rows the leaf holds NOW.
 static int apply_feed(flockgpu_plan *plan, int input, const FeedCheck &chk, const struct ArrowArray *const *batches) {
     flockgpu_ctx *ctx = plan->ctx;
@@ -430,6 +478,8 @@ int flockgpu_plan_feed(flockgpu_plan *plan, int input, const struct ArrowSchema 
                        int n_batches) {
     if (!plan) return FLOCKGPU_ERR_INVALID;
     if (plan->ring_ppw) return fail(plan->ctx, FLOCKGPU_ERR_INVALID, "plan_feed: the plan has an open pane ring (flockgpu_plan_feed_pane, or flockgpu_plan_ring_close first)");
+    // (a leaf that reads the caller's device columns in place -- FLOCKGPU_FEED_BORROW -- gets its own copy of them first: feeds append)
+    if (input >= 0 && input < (int)plan->leaves.size() && plan->leaves[(size_t)input].user_cols && !plan->async_pending) FG_TRY(own_user_columns(plan, input));
     FeedCheck chk;
     FG_TRY(check_feed(plan, input, schema, batches, n_batches, chk));
     return apply_feed(plan, input, chk, batches);
@@ -898,8 +948,9 @@ int flockgpu_plan_reset(flockgpu_plan *plan) {
     plan->col_stats.clear();
     API_CLOCK("reset");
     // borrowed pinned buffers may still be read by the DMA engine: the caller is about to drop them
-    if (plan->fed_bytes) (void)hipStreamSynchronize(plan->ctx->stream);
+    if (plan->fed_bytes || plan->device_fed) (void)hipStreamSynchronize(plan->ctx->stream);
     plan->fed_bytes = 0;
+    plan->device_fed = false;
     plan->has_retained = false;   // (its columns may alias the leaves, and the arena buffers behind it are reused by the next execute)
     plan->scheme_state = -1;
     plan->scheme_tag.clear();
@@ -918,6 +969,7 @@ int flockgpu_plan_reset(flockgpu_plan *plan) {
             if (ld.borrowed) c.values = nullptr, c.offsets = nullptr, c.valid = nullptr;   // the donor's memory: never grown or appended to from here
         }
         ld.borrowed = false;
+        ld.user_cols = false;
     }
     return FLOCKGPU_OK;
 }
@@ -991,5 +1043,280 @@ int flockgpu_plan_feed_from(flockgpu_plan *plan, int input, const flockgpu_plan 
     }
     ld.rows = t.rows;
     ld.borrowed = true;
+    return FLOCKGPU_OK;
+}
+
+// ------------------------------------------------------------------ device columns in and out (flockgpu_plan_feed_columns / _result_columns)
+namespace {
+
+// The Arrow format a FLOCKGPU_TEXT_* type stands for (the refusals speak the host feed's language).
+const char *text_format(int32_t t) {
+    switch (t) {
+        case FLOCKGPU_TEXT_INT32: return "i";
+        case FLOCKGPU_TEXT_INT64: return "l";
+        case FLOCKGPU_TEXT_UINT64: return "L";
+        case FLOCKGPU_TEXT_FLOAT64: return "g";
+        case FLOCKGPU_TEXT_TIMESTAMP_MS: return "tsm:";
+        case FLOCKGPU_TEXT_UTF8: return "u";
+        default: return "?";
+    }
+}
+int32_t text_type_of(const Field &f) {
+    if (f.is_ts) return FLOCKGPU_TEXT_TIMESTAMP_MS;
+    switch (f.type) {
+        case ColType::I32: return FLOCKGPU_TEXT_INT32;
+        case ColType::I64: return FLOCKGPU_TEXT_INT64;
+        case ColType::U64: return FLOCKGPU_TEXT_UINT64;
+        case ColType::F64: return FLOCKGPU_TEXT_FLOAT64;
+        default: return FLOCKGPU_TEXT_UTF8;
+    }
+}
+bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows, uint32_t flags) {
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    if (plan->ring_ppw) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: the plan has an open pane ring (flockgpu_plan_feed_pane, or flockgpu_plan_ring_close first)");
+    if (input < 0 || input >= (int)plan->ir.leaves.size() || n_cols < 0 || (n_cols && !cols) || rows < 0 || (flags & ~(uint32_t)FLOCKGPU_FEED_BORROW))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: bad argument");
+    if (plan->async_pending) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: an asynchronous execute is in flight (flockgpu_plan_wait first)");
+    FG_HIP(ctx, hipSetDevice(ctx->device));
+    const Leaf &lf = plan->ir.leaves[(size_t)input];
+    LeafData &ld = plan->leaves[(size_t)input];
+    if (ld.borrowed && !ld.user_cols) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: input %d shares another plan's relation; reset the plan first", input);
+    // hash placement: device columns carry no scheme tag -- an untagged batch
+    int scheme_state = plan->scheme_state;
+    if (lf.co_partitioned && rows > 0) {
+        if (scheme_state == 1)
+            return fail(ctx, FLOCKGPU_ERR_INVALID,
+                        "plan_feed_columns: mixed hash placement -- this stage was fed partitions tagged '%s' and untagged ones (another engine's hash): "
+                        "every producer of a stage must place rows the same way", kPartitionScheme);
+        scheme_state = 0;
+    }
+    // the columns the leaf reads, by name (match_schema's rules and messages)
+    const size_t n_leaf = lf.schema.size();
+    std::vector<int> at(n_leaf, -1);
+    for (size_t c = 0; c < n_leaf; ++c) {
+        if (!lf.needed[c]) continue;
+        for (int32_t i = 0; i < n_cols && at[c] < 0; ++i)
+            if (cols[i].name && lf.schema[c].name == cols[i].name) at[c] = i;
+        if (at[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: column '%s' missing from the fed schema", lf.schema[c].name.c_str());
+        const flockgpu_text_column &col = cols[at[c]];
+        if (!format_ok(lf.schema[c], text_format(col.type)))
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: column '%s' has Arrow format '%s', the plan scans %s", lf.schema[c].name.c_str(), text_format(col.type),
+                        type_name(lf.schema[c]));
+    }
+    // (before anything is allocated or launched)
+    if (rows >= (int64_t(1) << 31) || ld.rows + rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than 2^31 rows per relation");
+    if (rows == 0) return FLOCKGPU_OK;
+    CensusArgs ca;
+    std::vector<int> census_of(n_leaf, -1), utf8_of(n_leaf, -1);
+    for (size_t c = 0; c < n_leaf; ++c) {
+        if (at[c] < 0) continue;
+        const flockgpu_text_column &col = cols[at[c]];
+        const bool utf8 = lf.schema[c].type == ColType::UTF8;
+        if (utf8 ? !col.utf8.offsets : !col.values)
+            return fail(ctx, FLOCKGPU_ERR_INVALID, utf8 ? "plan_feed_columns: Utf8 column '%s' without offsets" : "plan_feed_columns: column '%s' without a data buffer", lf.schema[c].name.c_str());
+        if (!aligned_to(utf8 ? (const void *)col.utf8.offsets : col.values, utf8 ? 4 : col_width(lf.schema[c].type)))
+            return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: column '%s' is not aligned to its element size", lf.schema[c].name.c_str());
+        if (col.valid) {
+            if (ca.n_valid == kCensusCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than %d columns with validity bytes", kCensusCols);
+            if (lf.null_droppable[c]) ca.droppable |= uint64_t(1) << ca.n_valid;
+            ca.valid[ca.n_valid] = col.valid;
+            census_of[c] = ca.n_valid++;
+        }
+        if (utf8) {
+            if (ca.n_utf8 == kCensusUtf8) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than %d Utf8 columns", kCensusUtf8);
+            ca.offsets[ca.n_utf8] = col.utf8.offsets;
+            utf8_of[c] = ca.n_utf8++;
+        }
+    }
+    // ---- census: NULLs per column, the rows that stay, the Utf8 columns' byte ranges -- one launch, one wait (none without validity and Utf8)
+    const std::string base = leaf_key(plan, input, 0, "src");
+    CensusResult cr;
+    FG_TRY(feed_census_begin(ctx, base.c_str(), ca, rows, &cr));
+    FG_TRY(feed_census_wait(ctx, cr));
+    bool drop = false;
+    std::vector<char> with_valid(n_leaf, 0);
+    for (size_t c = 0; c < n_leaf; ++c) {
+        if (census_of[c] < 0 || cr.nulls(census_of[c]) == 0) continue;   // (validity bytes that are all 1 do not reach the leaf)
+        if (lf.null_droppable[c]) drop = true;
+        else with_valid[c] = 1;
+    }
+    const int64_t n_keep = drop ? cr.kept() : rows;
+    std::vector<int64_t> first(n_leaf, 0), add_bytes(n_leaf, 0);
+    for (size_t c = 0; c < n_leaf; ++c) {
+        if (utf8_of[c] < 0) continue;
+        first[c] = cr.utf8_first(utf8_of[c]);
+        add_bytes[c] = cr.utf8_last(utf8_of[c]) - first[c];
+        if (first[c] < 0 || add_bytes[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: the offsets of Utf8 column '%s' decrease", lf.schema[c].name.c_str());
+        if (add_bytes[c] && !cols[at[c]].utf8.data) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: Utf8 column '%s' without a data buffer", lf.schema[c].name.c_str());
+    }
+    // ---- rows with NULLs that may be left out: the row list, and the Utf8 columns taken at it (their byte totals: the take's own wait)
+    const int32_t *keep_rows = nullptr;
+    std::vector<flockgpu_utf8> taken(n_leaf, flockgpu_utf8{nullptr, nullptr});
+    if (drop && n_keep > 0) {
+        FG_TRY(feed_census_rows(ctx, base.c_str(), cr, rows, n_keep, &keep_rows));
+        std::vector<size_t> u8;
+        for (size_t c = 0; c < n_leaf; ++c)
+            if (utf8_of[c] >= 0) u8.push_back(c);
+        for (size_t g0 = 0; g0 < u8.size(); g0 += 4) {
+            const int k = (int)std::min<size_t>(4, u8.size() - g0);
+            flockgpu_utf8 srcs[4], outs[4];
+            int64_t nb[4] = {0, 0, 0, 0};
+            for (int j = 0; j < k; ++j) srcs[j] = cols[at[u8[g0 + (size_t)j]]].utf8;
+            Utf8MultiGather g;
+            FG_TRY(gather_utf8_multi_begin(ctx, (base + ".take" + std::to_string(g0)).c_str(), srcs, k, keep_rows, n_keep, &g));
+            FG_TRY(gather_utf8_multi_wait(ctx, g));
+            FG_TRY(gather_utf8_multi_finish(ctx, g, outs, nb));
+            for (int j = 0; j < k; ++j) {
+                taken[u8[g0 + (size_t)j]] = outs[j];
+                add_bytes[u8[g0 + (size_t)j]] = nb[j];
+            }
+        }
+    } else if (drop) {
+        for (size_t c = 0; c < n_leaf; ++c) add_bytes[c] = 0;
+    }
+    for (size_t c = 0; c < n_leaf; ++c)
+        if (utf8_of[c] >= 0 && ld.cols[c].bytes + add_bytes[c] >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: Utf8 column exceeds 2^31 bytes");
+    // (rows behind columns that are read in place: the leaf gets its own copy of those first -- before anything of the plan's state changes, so that
+    // a failure here leaves plan and leaf as they were)
+    if (n_keep > 0 && ld.user_cols) FG_TRY(own_user_columns(plan, input));
+    // ---- every check is behind us: from here on the leaf changes (apply_feed's resets)
+    plan->has_retained = false;
+    plan->col_stats.clear();
+    plan->scheme_state = scheme_state;
+    if (scheme_state == 0) plan->scheme_tag.clear();
+    plan->device_fed = true;   // (reset waits for the stream before the caller's columns may go)
+    if (n_keep == 0) {
+        ld.dropped += rows;
+        return FLOCKGPU_OK;
+    }
+    // ---- in place, when the caller lends the columns and nothing has to move
+    if ((flags & FLOCKGPU_FEED_BORROW) && ld.rows == 0 && !ld.borrowed && !drop) {
+        bool ok = true;
+        for (size_t c = 0; c < n_leaf && ok; ++c) {
+            if (at[c] < 0) continue;
+            const flockgpu_text_column &col = cols[at[c]];
+            if (utf8_of[c] >= 0) ok = first[c] == 0 && col.utf8.data && aligned_to(col.utf8.offsets, 16) && aligned_to(col.utf8.data, 16);
+            else ok = aligned_to(col.values, 16);
+            if (with_valid[c]) ok = ok && aligned_to(col.valid, 4);   // (the evaluator reads validity bytes four at a time)
+        }
+        if (ok) {
+            for (size_t c = 0; c < n_leaf; ++c) {
+                if (at[c] < 0) continue;
+                const flockgpu_text_column &col = cols[at[c]];
+                const bool utf8 = utf8_of[c] >= 0;
+                ld.cols[c] = DevBuf{const_cast<void *>(utf8 ? (const void *)col.utf8.data : col.values), utf8 ? const_cast<int32_t *>(col.utf8.offsets) : nullptr,
+                                    utf8 ? add_bytes[c] : 0, with_valid[c] ? const_cast<uint8_t *>(col.valid) : nullptr, with_valid[c] ? rows : 0};
+            }
+            ld.rows = rows;
+            ld.borrowed = ld.user_cols = true;
+            return FLOCKGPU_OK;
+        }
+    }
+    // ---- append behind what the leaf holds
+    const LeafSnapshot before(ld);
+    const int rc = [&]() -> int {
+        for (size_t c = 0; c < n_leaf; ++c)
+            if (at[c] >= 0) FG_TRY(reserve_rows(plan, input, c, n_keep, add_bytes[c]));
+        const int64_t rows_end = ld.rows + n_keep;
+        TailTakeCols tk;
+        auto take = [&](const void *src, void *out, int32_t width) -> int {
+            tk.src[tk.n] = src;
+            tk.out[tk.n] = out;
+            tk.width[tk.n] = width;
+            if (++tk.n < kGatherMulti) return FLOCKGPU_OK;
+            const int rc_take = take_to_tail(ctx, tk, keep_rows, n_keep);
+            tk.n = 0;
+            return rc_take;
+        };
+        for (size_t c = 0; c < n_leaf; ++c) {
+            if (at[c] < 0) continue;
+            const flockgpu_text_column &col = cols[at[c]];
+            DevBuf &dc = ld.cols[c];
+            if (with_valid[c]) {   // this feed's validity bytes (of the rows that stay) behind what the column holds; the rows before, if they had none: valid
+                void *vp = nullptr;
+                FG_TRY(grow(ctx, leaf_key(plan, input, (int)c, "valid"), (size_t)dc.valid_rows, (size_t)rows_end + 64, &vp));
+                dc.valid = static_cast<uint8_t *>(vp);
+                if (dc.valid_rows < ld.rows) FG_HIP(ctx, hipMemsetAsync(dc.valid + dc.valid_rows, 1, (size_t)(ld.rows - dc.valid_rows), ctx->stream));
+                if (drop) FG_TRY(take(col.valid, dc.valid + ld.rows, 1));
+                else FG_HIP(ctx, hipMemcpyAsync(dc.valid + ld.rows, col.valid, (size_t)rows, hipMemcpyDeviceToDevice, ctx->stream));
+                dc.valid_rows = rows_end;
+            }
+            if (utf8_of[c] >= 0) {   // offsets land rebased onto the column's byte cursor; only the bytes the offsets name are copied
+                const int32_t *so = drop ? taken[c].offsets : col.utf8.offsets;
+                const uint8_t *sb = drop ? taken[c].data : col.utf8.data + first[c];
+                FG_TRY(append_offsets_rebased(ctx, dc.offsets + ld.rows + 1, so, n_keep, (int32_t)dc.bytes));
+                if (add_bytes[c]) FG_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(dc.values) + dc.bytes, sb, (size_t)add_bytes[c], hipMemcpyDeviceToDevice, ctx->stream));
+                dc.bytes += add_bytes[c];
+            } else {
+                const size_t w = col_width(lf.schema[c].type);
+                uint8_t *dst = static_cast<uint8_t *>(dc.values) + (size_t)ld.rows * w;
+                if (drop) FG_TRY(take(col.values, dst, (int32_t)w));
+                else FG_HIP(ctx, hipMemcpyAsync(dst, col.values, (size_t)rows * w, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+        }
+        if (tk.n) FG_TRY(take_to_tail(ctx, tk, keep_rows, n_keep));
+        return FLOCKGPU_OK;
+    }();
+    if (rc != FLOCKGPU_OK) {
+        before.restore(ld);
+        return rc;
+    }
+    ld.rows += n_keep;
+    ld.dropped += rows - n_keep;
+    return FLOCKGPU_OK;   // the copies are ordered before the plan's kernels on the ctx stream
+}
+
+int flockgpu_plan_result_columns(const flockgpu_plan *plan, flockgpu_text_column *out, int32_t capacity, int32_t *n_cols, int64_t *rows) {
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    const Node *root = plan->ir.root.get();
+    const int32_t n = (int32_t)root->schema.size();
+    if (n_cols) *n_cols = n;
+    if (rows) *rows = 0;
+    if (!plan->has_retained) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_result_columns: the plan holds no retained result (flockgpu_plan_execute_retain)");
+    if (!out || capacity < n) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_result_columns: room for %d columns, the result has %d", out ? capacity : 0, n);
+    const Table &t = plan->retained;
+    if ((int32_t)t.cols.size() != n) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_result_columns: the retained result has %d columns, the root's schema %d", (int)t.cols.size(), n);
+    FG_HIP(ctx, hipSetDevice(ctx->device));
+    // what an all_null column (MAX over no rows) and the columns of an empty result point at: zeros -- values, offsets and validity alike
+    const size_t zero_bytes = (size_t)std::max<int64_t>(t.rows, 0) * 8 + 64;
+    uint8_t *zeros = nullptr;
+    bool zeros_ready = false;
+    auto need_zeros = [&]() -> int {
+        if (zeros_ready) return FLOCKGPU_OK;
+        FG_TRY(arena_get_t(ctx, node_key(plan, root, "zeros").c_str(), zero_bytes, &zeros));
+        FG_HIP(ctx, hipMemsetAsync(zeros, 0, zero_bytes, ctx->stream));
+        zeros_ready = true;
+        return FLOCKGPU_OK;
+    };
+    for (int32_t c = 0; c < n; ++c) {
+        const Field &f = root->schema[(size_t)c];
+        const DevColumn &col = t.cols[(size_t)c].c;
+        flockgpu_text_column &o = out[c];
+        o.name = f.name.c_str();
+        o.type = text_type_of(f);
+        o.values = nullptr;
+        o.valid = nullptr;
+        o.utf8 = flockgpu_utf8{nullptr, nullptr};
+        const bool utf8 = f.type == ColType::UTF8;
+        const bool absent = col.all_null || (utf8 ? !col.offsets || !col.values : !col.values);
+        if (absent) {
+            if (!col.all_null && t.rows > 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_result_columns: column '%s' of the retained result holds no data", f.name.c_str());
+            FG_TRY(need_zeros());
+            if (utf8) o.utf8 = flockgpu_utf8{reinterpret_cast<const int32_t *>(zeros), zeros};
+            else o.values = zeros;
+            if (col.all_null) o.valid = zeros;
+            continue;
+        }
+        if (utf8) o.utf8 = flockgpu_utf8{col.offsets, static_cast<const uint8_t *>(col.values)};
+        else o.values = col.values;
+        o.valid = col.valid;
+    }
+    if (rows) *rows = t.rows;
     return FLOCKGPU_OK;
 }

@@ -64,6 +64,7 @@ struct LeafData {
     int64_t rows = 0;
     int64_t dropped = 0;     // rows a feed left out because of NULLs
     bool borrowed = false;   // cols alias another plan's leaf (flockgpu_plan_feed_shared): nothing here is this leaf's to grow
+    bool user_cols = false;  // ... or the caller's own columns (flockgpu_plan_feed_columns with FLOCKGPU_FEED_BORROW): the next feed copies them first
     // pane ring (flockgpu_plan_ring_open): rows -- and per Utf8 column, bytes -- of every pane whose rows this leaf still holds, oldest first
     std::vector<int64_t> pane_rows;
     std::vector<std::vector<int64_t>> pane_bytes;   // [pane][column]
@@ -101,6 +102,7 @@ struct flockgpu_plan {
     struct CopyJob { void *dst; const void *src; size_t bytes; };
     std::vector<CopyJob> runs;   // transfers of the feed in progress, merged while they stay contiguous (h2d)
     int64_t fed_bytes = 0;
+    bool device_fed = false;     // flockgpu_plan_feed_columns queued reads of the caller's device columns: reset waits for the stream before they may go
     flockgpu::plan_detail::Table retained;              // flockgpu_plan_execute_retain: the result, left on the device for the plans that consume it
     bool has_retained = false;
     // ---- device-side pane ring (flockgpu_plan.h): the last ring_ppw panes stay in HBM across executes

@@ -665,33 +665,34 @@ class GpuContext:
                 valid[name] = take(c.valid, n, torch.uint8, 1)
         return out, valid, n
 
-    def _text_columns(self, columns, valid):
-        """[(name, type, tensor | DeviceUtf8)] -> (the flockgpu_text_column array, the row count, what must stay alive over the call)."""
+    def _text_columns(self, columns, valid, who="text encode"):
+        """[(name, type, tensor | DeviceUtf8)] -> (the flockgpu_text_column array, the row count, what must stay alive over the call).
+        `who` begins the messages: the caller's name for what it is doing."""
         kinds = {"int32": _ffi.TEXT_INT32, "int64": _ffi.TEXT_INT64, "uint64": _ffi.TEXT_UINT64, "float64": _ffi.TEXT_FLOAT64,
                  "timestamp_ms": _ffi.TEXT_TIMESTAMP_MS, "utf8": _ffi.TEXT_UTF8}
         valid = valid or {}
         unknown = sorted(set(valid) - {name for name, _, _ in columns})
         if unknown:
-            raise ValueError("text encode: validity for unknown column(s) " + ", ".join(unknown))
+            raise ValueError(who + ": validity for unknown column(s) " + ", ".join(unknown))
         spec = (_ffi.TextColumn * max(len(columns), 1))()
         rows, keep = None, []
         for c, (name, t, col) in zip(spec, columns):
             if t not in kinds:
-                raise ValueError(f"text encode: column {name!r}: unknown type {t!r}")
+                raise ValueError(f"{who}: column {name!r}: unknown type {t!r}")
             utf8 = isinstance(col, DeviceUtf8)
             if utf8 != (t == "utf8"):
-                raise ValueError(f"text encode: column {name!r}: {t} takes a {'DeviceUtf8' if t == 'utf8' else 'tensor'}")
+                raise ValueError(f"{who}: column {name!r}: {t} takes a {'DeviceUtf8' if t == 'utf8' else 'tensor'}")
             n = col.offsets.numel() - 1 if utf8 else col.numel()
             if rows is not None and n != rows:
-                raise ValueError(f"text encode: column {name!r} has {n} rows, the columns before it {rows}")
+                raise ValueError(f"{who}: column {name!r} has {n} rows, the columns before it {rows}")
             rows = n
             first = col.offsets if utf8 else col   # (a torch tensor or a GuardedBuffer: element size from the one or the other)
             size = first.element_size() if hasattr(first, "element_size") else np.dtype(first.dtype).itemsize
             if size != (4 if t in ("int32", "utf8") else 8):
-                raise ValueError(f"text encode: column {name!r}: {t} does not take {size}-byte elements")
+                raise ValueError(f"{who}: column {name!r}: {t} does not take {size}-byte elements")
             v = valid.get(name)
             if v is not None and v.numel() != n:
-                raise ValueError(f"text encode: validity of {name!r} has {v.numel()} entries for {n} rows")
+                raise ValueError(f"{who}: validity of {name!r} has {v.numel()} entries for {n} rows")
             key = name.encode() if isinstance(name, str) else bytes(name)
             keep += [key, col, v]
             c.name, c.type = key, kinds[t]

@@ -213,6 +213,22 @@ def columns_to_event_bytes(ctx: GpuContext, relation: str, cols, borrow: bool = 
     return ctx.json_lines_encode([(name, t, get(name)) for name, t in schema], borrow=borrow)
 
 
+# the Epoch fields of the three relations (event.rs): Timestamp(Millisecond) in the reference's Arrow schemas
+NEXMARK_TIMESTAMP_FIELDS = ("b_date_time", "a_date_time", "expires", "p_date_time")
+
+
+def event_source(relation: str, cols):
+    """What event_bytes_to_columns or the device generator returns for `relation` -- a {name: column} mapping or a Bids / Auctions / Persons --
+    as a device source: (columns, valid) for `ExecutionContext.feed_device_sources` / `_Plan.feed_columns`, the fields that are there in the
+    relation's order and under its types, the Epoch fields as "timestamp_ms".  NEXMark events hold no NULLs: `valid` is empty."""
+    get = cols.get if hasattr(cols, "get") else lambda k: getattr(cols, k, None)
+    columns = [(name, "timestamp_ms" if name in NEXMARK_TIMESTAMP_FIELDS else t, get(name))
+               for name, t in NEXMARK_JSON_SCHEMAS[relation] if get(name) is not None]
+    if not columns:
+        raise ValueError(f"event_source: no {relation} column in what was passed")
+    return columns, {}
+
+
 def synthetic_side_input(ctx: GpuContext, stream: NEXMarkStream, stride: int = 6007):
     """A bounded q13 side input for a generated stream: key = every `stride`-th auction id the stream's bids can name,
     value = a function of the key.  (The reference reads the table from a user-supplied CSV in S3,

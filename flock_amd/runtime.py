@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence, Union
 
 from . import _ffi
 from ._ffi import FlockGpuError
-from .engine import GpuContext
+from .engine import DeviceUtf8, GpuContext
 
 _ARROW_SCHEMA_BYTES, _ARROW_ARRAY_BYTES = 72, 80
 
@@ -60,6 +60,17 @@ def _exported(batches):
         for ab in abufs:
             _release(C.addressof(ab), 64)
         _release(C.addressof(sbuf), 56)
+
+
+def _columns_schema(columns):
+    """The Arrow schema [(name, type, column)] stands for (the type names of csv_decode / csv_encode)."""
+    pa = _pa()
+    types = {"int32": pa.int32(), "int64": pa.int64(), "uint64": pa.uint64(), "float64": pa.float64(), "timestamp_ms": pa.timestamp("ms"),
+             "utf8": pa.utf8()}
+    for name, t, _ in columns:
+        if t not in types:
+            raise ValueError(f"device source: column {name!r}: unknown type {t!r}")
+    return pa.schema([(name, types[t]) for name, t, _ in columns])
 
 
 class _Plan:
@@ -175,6 +186,57 @@ class _Plan:
             return False
         self.gpu._check(rc)
         return True
+
+    def feed_columns(self, i: int, columns, valid=None, borrow: bool = False):
+        """`feed` for rows that already lie in device memory (flockgpu_plan_feed_columns): `columns` = [(name, "int32" | "int64" | "uint64" |
+        "float64" | "timestamp_ms" | "utf8", tensor | DeviceUtf8)] and `valid` = {name: uint8 tensor, 1 = not NULL}, csv_encode's argument
+        shape -- what csv_decode, json_lines_decode and the device generator leave in HBM.  Columns are matched to the leaf by name, extra
+        ones are ignored; the rows append behind what the leaf holds.  `borrow`: the tensors stay as they are until `reset`, and the library
+        may read them in place instead of copying (it decides; the result is the same).  Either way this object holds the tensors until
+        `reset`: the library reads them on its own stream."""
+        spec, rows, keep = self.gpu._text_columns(columns, valid, who="feed_columns")
+        rc = self._lib.flockgpu_plan_feed_columns(self.h, i, spec, len(columns), rows, _ffi.FEED_BORROW if borrow else 0)
+        self.gpu._check(rc)
+        self._fed.append(keep)
+        self._base_fed.add(i)
+
+    def result_columns(self):
+        """The result `execute_retain` / `exchange_retain` left on the device, as (columns, valid, rows) in `feed_columns`' and csv_encode's
+        shape: views of the plan's own buffers (flockgpu_plan_result_columns), valid until the plan's next execute, feed or reset."""
+        import torch
+        cap = 64
+        while True:
+            spec = (_ffi.TextColumn * cap)()
+            n, rows = C.c_int32(0), C.c_int64(0)
+            rc = self._lib.flockgpu_plan_result_columns(self.h, spec, cap, C.byref(n), C.byref(rows))
+            if rc == _ffi.ERR_INVALID and n.value > cap:
+                cap = n.value
+                continue
+            self.gpu._check(rc)
+            break
+        names = {_ffi.TEXT_INT32: "int32", _ffi.TEXT_INT64: "int64", _ffi.TEXT_UINT64: "uint64", _ffi.TEXT_FLOAT64: "float64",
+                 _ffi.TEXT_TIMESTAMP_MS: "timestamp_ms", _ffi.TEXT_UTF8: "utf8"}
+        view, r = self.gpu._device_view, rows.value
+        columns, valid = [], {}
+        utf8 = [c for c in spec[:n.value] if c.type == _ffi.TEXT_UTF8]
+        ends = {}
+        if utf8 and r:   # a Utf8 column's byte count is its last offset: read once for all of them
+            self.gpu.synchronize()
+            ends = {c.name: int(view(c.utf8.offsets + 4 * r, 1, torch.int32).cpu()[0]) for c in utf8}
+        for c in spec[:n.value]:
+            name, t = c.name.decode(), names[c.type]
+            if t == "utf8":
+                col = DeviceUtf8(view(c.utf8.offsets, r + 1, torch.int32), view(c.utf8.data, ends.get(c.name, 0), torch.uint8))
+            elif t == "int32":
+                col = view(c.values, r, torch.int32)
+            elif t == "float64":
+                col = view(c.values, r, torch.int64).view(torch.float64)
+            else:
+                col = view(c.values, r, torch.int64)
+            columns.append((name, t, col))
+            if c.valid:
+                valid[name] = view(c.valid, r, torch.uint8)
+        return columns, valid, r
 
     def execute(self):
         pa = _pa()
@@ -306,6 +368,35 @@ class ExecutionContext:
                     if first is not None and plan.matches(i, first.schema):
                         yield plan, i, [b for part in sources.pop(si) for b in part]
                         break
+
+    # -- device columns in and out (flockgpu_plan_feed_columns / flockgpu_plan_result_columns)
+    def _device_leaf_sources(self, sources):
+        """(plan, leaf, index into `sources`) for every plan leaf that finds a device source: the first source whose column names cover what
+        the leaf reads -- feed_data_sources' matching (flockgpu_plan_input_matches) on a schema made of the names and types.  Nothing moves
+        when a device source is fed, so one source may serve several leaves (q5's plan scans `bid` twice)."""
+        schemas = [_columns_schema(columns) for columns, _ in sources]
+        for plan in self.plans:
+            for i in range(len(plan.inputs)):
+                hit = next((si for si, schema in enumerate(schemas) if plan.matches(i, schema)), None)
+                if hit is not None:
+                    yield plan, i, hit
+
+    def feed_device_sources(self, sources, borrow: bool = False):
+        """feed_data_sources for relations that already lie in device memory: `sources` = [(columns, valid)], each as `_Plan.feed_columns`
+        takes them (what csv_decode / event_source return).  Every source goes to every plan leaf whose columns it covers.  `borrow`: the
+        tensors stay unchanged until clean_data_sources, and the library may read them in place.  Returns how many leaves were fed."""
+        if self._ring:
+            raise ValueError("feed_device_sources: a window ring takes panes from the host (feed_data_sources(sources, pane))")
+        fed = 0
+        for plan, i, si in list(self._device_leaf_sources(sources)):
+            columns, valid = sources[si]
+            plan.feed_columns(i, columns, valid, borrow)
+            fed += 1
+        return fed
+
+    def result_columns(self, plan: int = 0):
+        """After execute_retain(): plan `plan`'s result as (columns, valid, rows), borrowed views in csv_encode's argument shape."""
+        return self.plans[plan].result_columns()
 
     def prefetch_data_sources(self, sources, pane: int):
         """The sources of pane `pane` -- the ring's NEXT pane -- matched to the leaves as feed_data_sources matches them; what a prefetch

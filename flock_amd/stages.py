@@ -341,6 +341,21 @@ def _check_sound_over_partitions(i: int, st: Stage, edge: List[str]):
     visit(root)
 
 
+def _relation_names(rel) -> set:
+    """The column names of a base relation: a RecordBatch, or a device source (columns, valid) as `ExecutionContext.feed_device_sources` takes it."""
+    return {name for name, _, _ in rel[0]} if isinstance(rel, tuple) else set(rel.schema.names)
+
+
+def _feed_base(ctx, relations):
+    """Base relations into a stage's leaves: RecordBatches from the host, device sources -- (columns, valid) tuples -- in place in HBM."""
+    host = [[[rb]] for rb in relations if not isinstance(rb, tuple)]
+    device = [rb for rb in relations if isinstance(rb, tuple)]
+    if host:
+        ctx.feed_data_sources(host)
+    if device:
+        ctx.feed_device_sources(device)
+
+
 class StagedRun:
     """The distributed run of a stage DAG in ONE process: every stage is a function group with its plan instantiated once
     (`ExecutionContext`), a shuffling stage is executed with `execute_partitioned` (through `collect`) by `chunks` producers over
@@ -390,7 +405,7 @@ class StagedRun:
         if all(j is None for j in st.inputs):
             return list(relations.values())
         base = [{f["name"] for f in lf["schema"]["fields"]} for lf, j in zip(leaves_bfs(st.plan), st.inputs) if j is None]
-        return [rb for rb in relations.values() if any(names & set(rb.schema.names) for names in base)]
+        return [rb for rb in relations.values() if any(names & _relation_names(rb) for names in base)]
 
     def _feed_from(self, i, ctx):
         """Stage i's leaves read the retained results of the stages that feed it.  Next to a base relation every producer must find its leaf: one
@@ -402,8 +417,11 @@ class StagedRun:
                                f"and not every result found its leaf")
 
     def run(self, relations):
-        """relations: {name: RecordBatch} of the base relations (one window).  Returns the root stage's batches."""
+        """relations: {name: RecordBatch} of the base relations (one window).  Returns the root stage's batches.  With `on_device` a relation may
+        also be a device source, (columns, valid) as `ExecutionContext.feed_device_sources` takes it: it never leaves HBM."""
         from .runtime import collect
+        if any(isinstance(rb, tuple) for rb in relations.values()) and (self.comm is not None or not self.on_device):
+            raise ValueError("StagedRun: device sources take an on_device run")
         if self.comm is not None:
             return self._run_distributed(relations)
         if self.on_device:
@@ -461,17 +479,17 @@ class StagedRun:
         return [b for part in outputs[len(self.stages) - 1] for b in part]
 
     def _run_on_device(self, relations):
-        src = [[[rb]] for rb in relations.values()]
+        src = list(relations.values())
         last = len(self.stages) - 1
         donor, out = None, None
         try:
             for i, (st, ctx) in enumerate(zip(self.stages, self.ctxs)):
                 if all(j is None for j in st.inputs):
                     if donor is None or not (self.share_sources and ctx.share_data_sources(donor)):
-                        ctx.feed_data_sources(src)
+                        _feed_base(ctx, src)
                         donor = donor or ctx
                 elif any(j is None for j in st.inputs):
-                    ctx.feed_data_sources([[[rb]] for rb in self._sources(i, relations)])
+                    _feed_base(ctx, self._sources(i, relations))
                 self._feed_from(i, ctx)   # (also next to a base relation: feed_from passes the leaves that hold one by)
                 if i == last:
                     out = ctx.execute()[0]

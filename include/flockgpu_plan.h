@@ -175,6 +175,39 @@ int flockgpu_plan_execute_partitioned(flockgpu_plan *plan, struct ArrowSchema *o
 int flockgpu_plan_execute_retain(flockgpu_plan *plan, int64_t *rows);
 int flockgpu_plan_feed_from(flockgpu_plan *plan, int input, const flockgpu_plan *producer);
 
+/* Device columns in and out of a plan: what the decoders leave in HBM (flockgpu_json_lines_decode, flockgpu_csv_decode), what the generator
+ * writes and what the encoders read (flockgpu_text_column, flockgpu.h) without a detour through host Arrow.
+ *
+ * flockgpu_plan_feed_columns is flockgpu_plan_feed for `rows` rows that already lie in device memory: the same rows fed either way give the same
+ * result.  `cols` are matched to the leaf's columns by name (extra ones are ignored); an Int64 field takes FLOCKGPU_TEXT_INT64 or
+ * FLOCKGPU_TEXT_TIMESTAMP_MS and so does a Timestamp(ms) field, every other type matches exactly.  Each call appends behind what the leaf
+ * holds; host feeds and device feeds of one leaf may alternate.  `valid` is one byte per row, 0 = NULL (NULL pointer: no NULLs), and follows
+ * flockgpu_plan_feed's rules: a column whose bytes are all 1 reaches the leaf WITHOUT validity (the fused pipelines stay available), a row
+ * whose NULL cannot change the result is left out, every other column that holds a NULL carries its validity bytes along.  Pointers need only
+ * their element's natural alignment.  The columns are read on the context's stream; work queued on other streams is the caller's to order.
+ * At most one host wait per call (none when no fed column has validity bytes and none is Utf8), one more when rows are left out of a leaf
+ * that reads Utf8 columns.
+ * FLOCKGPU_FEED_BORROW: the caller promises that the columns stay alive and unchanged until the next flockgpu_plan_reset (or destroy); the
+ * library then MAY read them in place instead of copying -- it does when the leaf is empty, no row has to be left out, values / offsets /
+ * bytes are 16-byte aligned, offsets[0] is 0 and validity bytes are 4-byte aligned -- and copies otherwise.  Without the flag the columns may
+ * be released once the stream has passed the call (flockgpu_plan_reset and every execute wait for it).
+ *   FLOCKGPU_ERR_INVALID      bad arguments, an asynchronous execute in flight, a leaf that reads another plan's relation, an open pane ring
+ *                             (feed panes with flockgpu_plan_feed_pane), a needed column missing, a column without its buffer;
+ *   FLOCKGPU_ERR_UNSUPPORTED  a needed column of another type, 2^31 rows (decided from `rows` before anything is allocated or launched),
+ *                             2^31 bytes in a Utf8 column, more than 64 columns with validity bytes or 32 Utf8 columns.
+ * A refused call leaves the leaf as it was.
+ *
+ * flockgpu_plan_result_columns: a view of the result flockgpu_plan_execute_retain / flockgpu_plan_exchange_retain left on the device, one entry
+ * per column of the root's schema (names owned by the plan; Float64 as FLOCKGPU_TEXT_FLOAT64, Timestamp as FLOCKGPU_TEXT_TIMESTAMP_MS), ready
+ * for flockgpu_csv_encode / flockgpu_json_lines_encode.  `valid` is set where the column carries validity; an all-NULL column (MAX over no rows)
+ * comes as zero values with zero validity bytes.  Valid until the plan's next execute, feed or reset.  *n_cols is always set; no retained
+ * result or `capacity` < *n_cols: FLOCKGPU_ERR_INVALID. */
+enum { FLOCKGPU_FEED_BORROW = 1u };
+int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int32_t n_cols,
+                               int64_t rows, uint32_t flags);
+int flockgpu_plan_result_columns(const flockgpu_plan *plan, flockgpu_text_column *out, int32_t capacity,
+                                 int32_t *n_cols, int64_t *rows);
+
 /* clean_data_sources(): drops the inputs, keeps device arenas and hash-table sizing for the next invocation.  On a plan with
  * an open pane ring (below) it ends the window instead: the oldest pane of a full ring is retired, the others stay. */
 int flockgpu_plan_reset(flockgpu_plan *plan);
