@@ -132,6 +132,14 @@ class JsonColumn(C.Structure):
 JSON_INT32, JSON_INT64, JSON_UTF8 = 0, 1, 2
 
 
+class JsonNField(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int32), ("nullable", C.c_int32)]
+
+
+class JsonNColumn(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("valid", C.c_void_p), ("null_count", C.c_int64), ("utf8", Utf8), ("utf8_bytes", C.c_int64)]
+
+
 class CsvField(C.Structure):
     _fields_ = [("type", C.c_int32)]
 
@@ -209,6 +217,7 @@ SYMBOLS = {
     "flockgpu_inclusive_scan_i32": (_i, [_vp, _vp, _i64]),
     "flockgpu_ipc_pack_body": (_i, [_vp, C.POINTER(IpcBuffer), _i, _vp, _i64, C.POINTER(_i64)]),
     "flockgpu_json_lines_decode": (_i, [_vp, _vp, _i64, C.POINTER(JsonField), _i, C.POINTER(JsonColumn), C.POINTER(_i64)]),
+    "flockgpu_json_lines_decode_nullable": (_i, [_vp, _vp, _i64, C.POINTER(JsonNField), _i, C.POINTER(JsonNColumn), C.POINTER(_i64)]),
     "flockgpu_csv_decode": (_i, [_vp, _vp, _i64, C.POINTER(CsvField), _i, C.POINTER(CsvOptions), C.POINTER(CsvColumn), C.POINTER(_i64)]),
     "flockgpu_json_lines_encode": (_i, [_vp, C.POINTER(TextColumn), _i, _i64, C.POINTER(TextResult)]),
     "flockgpu_csv_encode": (_i, [_vp, C.POINTER(TextColumn), _i, _i64, C.POINTER(CsvOptions), C.POINTER(TextResult)]),

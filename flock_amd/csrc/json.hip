@@ -48,9 +48,35 @@
 //           schema integer's digits are read to their end first -- then a malformed tail, then a fraction / exponent, then the range;
 //   A-JSON9 limits: 1 .. 16 fields (more: UNSUPPORTED; none: INVALID), names of 1 .. 31 bytes (UNSUPPORTED otherwise), less than 2^31 - 16 bytes
 //           of text, 16-byte aligned.
+//
+// flockgpu_json_lines_decode_nullable: the same decoder with NULLs, optional members and the encoders' six types (what
+// flockgpu_json_lines_encode writes reads back).  A second entry point beside the first: flockgpu_json_lines_decode keeps every rule above,
+// every message and the kernel instances it launches.  Its rules -- ASSUMPTIONS like the list above, checked against tests/json_nullable_ref.py
+// and, there, against json.loads and Python's float():
+//   A-JSONN1 carried over: lines, grammar, dropped members, repeated keys, verbatim bytes, error order and limits are A-JSON1, 2, 3, 6, 7, 8
+//            and 9 as they stand (1 .. 16 fields, `json: line N: ...`);
+//   A-JSONN2 every field is REQUIRED or NULLABLE.  A required field is A-JSON3 / A-JSON4's: null where its value belongs is malformed, a line
+//            without it fails with "a schema field is missing";
+//   A-JSONN3 a nullable field is NULL where its value is the literal null and where the line has no member of its name.  With a repeated key
+//            the last occurrence wins (1 then null: NULL; null then 1: 1) and every occurrence is checked and typed.  {} is a row of NULLs
+//            when every field is nullable.  A blank line stays UNSUPPORTED.  nul, NULL, nullx are malformed;
+//   A-JSONN4 a NULL is validity byte 0 and value 0; a Utf8 NULL is a value of length 0 (two equal offsets) with validity 0, "" is one with
+//            validity 1 (flockgpu_csv_decode's and feed_columns' convention).  Validity bytes are written for every nullable field;
+//   A-JSONN5 Int32 / Int64 / Utf8 are A-JSON4's.  Timestamp(ms) is a JSON integer in Int64's range (what the encoder writes; a string is a
+//            wrong type).  UInt64 is a JSON integer literal in 0 .. 18446744073709551615; a '-' in front is out of range, "-0" included
+//            (textnum.hpp A-TN1);
+//   A-JSONN6 Float64 is a JSON number, -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? -- the grammar first: +1, 01, .5, 1., 1e, nan and
+//            Infinity are malformed -- and is converted only inside csv_f64's exact range (csv.hpp A-CSV5: a significand of at most 2^53
+//            without its trailing zeros, a folded decimal exponent in [-22, 22]; a zero significand is +-0 whatever the exponent, "-0.0" is
+//            negative zero, "3" is 3.0).  A well-formed number outside it fails with FLOCKGPU_ERR_UNSUPPORTED, naming the line and the field;
+//            like an integer's range it is decided once the number's text has been read to its end and found well formed;
+//   A-JSONN7 true, false, a string where a number belongs and a number where a string belongs are a wrong type: INVALID ("malformed JSON"), as
+//            today.  An integer field (UInt64 and Timestamp included) with a well-formed fraction / exponent stays UNSUPPORTED (A-JSON6).
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
+#include "csv.hpp"
 #include "gather.hpp"
 
 using namespace flockgpu;
@@ -84,6 +110,53 @@ struct JsonOut {
     int32_t *pairs[kMaxFields];  // Utf8: (start, end) of the raw value in the input, 2 per row
     int32_t *ulen[kMaxFields];   // Utf8: length after unescaping
 };
+
+// flockgpu_json_lines_decode_nullable (A-JSONN1..7): the same walkers, instantiated over a schema that says which fields may be NULL and over
+// columns that carry validity bytes.  The first entry point's instances take JsonSpec / JsonOut and compile to what they were.
+enum : int32_t { kUInt64 = 3, kFloat64 = 4 };   // (Timestamp(ms) is kInt64 here)
+enum : uint32_t { kErrFloat = 8 };              // a well-formed Float64 outside csv_f64's exact range; the field rides in bits 4..7 of the code
+struct JsonNSpec : JsonSpec {
+    uint32_t nullable;           // bit f: field f may be NULL
+};
+struct JsonNOut : JsonOut {
+    uint8_t *valid[kMaxFields];  // one byte per row, 1 = not NULL; nullable fields only
+};
+template <class S>
+constexpr bool kIsNullable = std::is_same<S, JsonNSpec>::value;
+constexpr int kNullCountBlocks = 512;            // most workgroups per field of json_null_count_kernel
+constexpr uint32_t kNullWord = 0x6C6C756Eu;     // "null", little-endian
+__device__ const double kPow10[kCsvMaxPow10 + 1] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+__device__ const uint64_t kPow10U[19] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull,
+                                         10000000000ull, 100000000000ull, 1000000000000ull, 10000000000000ull, 100000000000000ull, 1000000000000000ull,
+                                         10000000000000000ull, 100000000000000000ull, 1000000000000000000ull};
+
+// A NULL / a value's validity byte in row `row` of field f (A-JSONN4); required fields have no validity bytes
+template <class S, class O>
+__device__ __forceinline__ void put_null(const S &spec, const O &out, int32_t type, int f, int64_t row) {
+    if constexpr (kIsNullable<S>) {
+        out.valid[f][row] = 0;
+        if (type == kUtf8) {
+            out.pairs[f][2 * row] = 0;
+            out.pairs[f][2 * row + 1] = 0;
+            out.ulen[f][row] = 0;
+        } else if (type == kInt32) {
+            reinterpret_cast<int32_t *>(out.values[f])[row] = 0;
+        } else {
+            reinterpret_cast<int64_t *>(out.values[f])[row] = 0;
+        }
+    }
+}
+template <class S>
+__device__ __forceinline__ bool nullable_field(const S &spec, int f) {
+    if constexpr (kIsNullable<S>) return (spec.nullable >> f) & 1u;
+    else return false;
+}
+template <class S, class O>
+__device__ __forceinline__ void put_valid(const S &spec, const O &out, int f, int64_t row) {
+    if constexpr (kIsNullable<S>) {
+        if ((spec.nullable >> f) & 1u) out.valid[f][row] = 1;
+    }
+}
 
 // ---- line index --------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t newline_mask(const uint8_t *__restrict__ bytes, int64_t n, int64_t p0) {
@@ -139,6 +212,7 @@ struct Text {
     const uint8_t *s;       // LDS copy of [s_base, ...)
     int32_t s_base;
     __device__ __forceinline__ uint32_t at(int32_t p) const { return kLds ? s[p - s_base] : g[p]; }
+    __device__ __forceinline__ const uint8_t *ptr(int32_t p) const { return kLds ? s + (p - s_base) : g + p; }
 };
 
 __device__ __forceinline__ bool is_ws(uint32_t c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
@@ -148,7 +222,9 @@ __device__ __forceinline__ int hex_of(uint32_t c) {
 
 // p at the opening quote.  Returns the position after the closing quote, or -1; [*b, *e) = raw bytes between the quotes,
 // *ulen = bytes after unescaping, *esc = the value holds a backslash.
-template <bool kLds>
+// (Tag, here and in the helpers below: the schema type of the parse_line that calls them.  Each entry point gets instances of its own, so that what
+// the compiler inlines into the first entry's second kernel does not depend on the nullable entry's callers.)
+template <bool kLds, class Tag>
 __device__ int32_t scan_string(const Text<kLds> &t, int32_t p, int32_t end, int32_t *b, int32_t *e, int32_t *ulen, bool *esc) {
     ++p;
     *b = p;
@@ -207,7 +283,7 @@ __device__ int32_t scan_string(const Text<kLds> &t, int32_t p, int32_t end, int3
 
 // The fraction and the exponent of a JSON number, each optional: (\.[0-9]+)?([eE][+-]?[0-9]+)?.  Returns the position after them, or -1
 // where one of them begins and is not well formed.
-template <bool kLds>
+template <bool kLds, class Tag>
 __device__ int32_t skip_fraction_exponent(const Text<kLds> &t, int32_t p, int32_t end) {
     if (p < end && t.at(p) == '.') {
         const int32_t q = ++p;
@@ -226,11 +302,11 @@ __device__ int32_t skip_fraction_exponent(const Text<kLds> &t, int32_t p, int32_
 
 // What follows the digits of a schema integer at p, a byte that is no delimiter: true where it is a well-formed fraction / exponent that a
 // delimiter (or the line's end) follows -- a number, only not an integer literal (A-JSON6); false where the text is malformed.
-template <bool kLds>
+template <bool kLds, class Tag>
 __device__ bool is_fraction_exponent(const Text<kLds> &t, int32_t p, int32_t end) {
     const uint32_t c = t.at(p);
     if (!(c == '.' || c == 'e' || c == 'E')) return false;
-    p = skip_fraction_exponent(t, p, end);
+    p = skip_fraction_exponent<kLds, Tag>(t, p, end);
     if (p < 0) return false;
     if (p >= end) return true;
     const uint32_t d = t.at(p);
@@ -240,7 +316,7 @@ __device__ bool is_fraction_exponent(const Text<kLds> &t, int32_t p, int32_t end
 // The value of a member that is not in the schema, checked against the whole grammar (A-JSON2, A-JSON3) and dropped.  p at the value's first
 // byte (after white space).  Returns the position after the value, or -(error code).  What follows the value is the caller's to check.
 // Containers are walked without recursion: `objs` holds one bit per open bracket (1: '{'), the innermost at bit depth - 1.
-template <bool kLds>
+template <bool kLds, class Tag>
 __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
     constexpr int32_t kBad = -(int32_t)kErrSyntax;
     uint64_t objs = 0;
@@ -273,7 +349,7 @@ __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
         bool esc;
         if (in_obj) {   // "key" :
             if (c != '"') return kBad;
-            p = scan_string(t, p, end, &b, &e, &u, &esc);
+            p = scan_string<kLds, Tag>(t, p, end, &b, &e, &u, &esc);
             if (p < 0) return kBad;
             while (p < end && is_ws(t.at(p))) ++p;
             if (p >= end || t.at(p) != ':') return kBad;
@@ -291,7 +367,7 @@ __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
             continue;
         }
         if (c == '"') {
-            p = scan_string(t, p, end, &b, &e, &u, &esc);
+            p = scan_string<kLds, Tag>(t, p, end, &b, &e, &u, &esc);
             if (p < 0) return kBad;
         } else if (c == 't') {
             if (p + 4 > end || t.at(p + 1) != 'r' || t.at(p + 2) != 'u' || t.at(p + 3) != 'e') return kBad;
@@ -311,7 +387,7 @@ __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
             ++p;
             if (c != '0')
                 while (p < end && t.at(p) - '0' <= 9u) ++p;
-            p = skip_fraction_exponent(t, p, end);
+            p = skip_fraction_exponent<kLds, Tag>(t, p, end);
             if (p < 0) return kBad;
         }
         if (depth == 0) return p;
@@ -319,8 +395,10 @@ __device__ int32_t skip_value(const Text<kLds> &t, int32_t p, int32_t end) {
     }
 }
 
-template <bool kLds>
-__device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, const JsonSpec &spec, int64_t row, const JsonOut &out) {
+template <bool kLds, class S, class O>
+__device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, const S &spec, int64_t row, const O &out) {
+    constexpr bool kN = kIsNullable<S>;
+    using Tag = S;
     while (end > p && is_ws(t.at(end - 1))) --end;
     while (p < end && is_ws(t.at(p))) ++p;
     if (p >= end) return kErrBlank;
@@ -337,7 +415,7 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
         if (t.at(p) != '"') return kErrSyntax;
         int32_t kb, ke, ku;
         bool kesc;
-        p = scan_string(t, p, end, &kb, &ke, &ku, &kesc);
+        p = scan_string<kLds, Tag>(t, p, end, &kb, &ke, &ku, &kesc);
         if (p < 0) return kErrSyntax;
         if (kesc) return kErrKeyEscape;
         int f = -1;
@@ -359,17 +437,40 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
         while (p < end && is_ws(t.at(p))) ++p;
         if (p >= end) return kErrSyntax;
         if (f < 0) {
-            p = skip_value(t, p, end);
+            p = skip_value<kLds, Tag>(t, p, end);
             if (p < 0) return (uint32_t)-p;
+        } else if (kN && t.at(p) == 'n' && nullable_field(spec, f)) {   // (A-JSONN3) exactly null; what follows it is checked below
+            if (p + 4 > end || t.at(p + 1) != 'u' || t.at(p + 2) != 'l' || t.at(p + 3) != 'l') return kErrSyntax;
+            p += 4;
+            put_null(spec, out, spec.type[f], f, row);
+            seen |= 1u << f;
         } else if (spec.type[f] == kUtf8) {
             if (t.at(p) != '"') return kErrSyntax;
             int32_t b, e, u;
             bool esc;
-            p = scan_string(t, p, end, &b, &e, &u, &esc);
+            p = scan_string<kLds, Tag>(t, p, end, &b, &e, &u, &esc);
             if (p < 0) return kErrSyntax;
             out.pairs[f][2 * row] = b;
             out.pairs[f][2 * row + 1] = e;
             out.ulen[f][row] = esc ? -u - 1 : u;  // negative: needs unescaping (length = -(v + 1))
+            put_valid(spec, out, f, row);
+            seen |= 1u << f;
+        } else if (kN && spec.type[f] == kFloat64) {   // (A-JSONN6) the JSON grammar first, then csv_f64's range
+            const int32_t b = p;
+            if (t.at(p) == '-') ++p;
+            if (p >= end || t.at(p) - '0' > 9u) return kErrSyntax;
+            if (t.at(p) == '0' && p + 1 < end && t.at(p + 1) - '0' <= 9u) return kErrSyntax;
+            while (p < end && t.at(p) - '0' <= 9u) ++p;
+            p = skip_fraction_exponent<kLds, Tag>(t, p, end);
+            if (p < 0) return kErrSyntax;
+            if (p < end) {
+                const uint32_t c = t.at(p);
+                if (!(c == ',' || c == '}' || is_ws(c))) return kErrSyntax;
+            }
+            double v = 0.0;
+            if (!csv_f64(t.ptr(b), p - b, &v)) return kErrFloat | ((uint32_t)f << 4);   // (csv.hpp A-CSV5 itself: LDS and global memory are both flat pointers)
+            reinterpret_cast<double *>(out.values[f])[row] = v;
+            put_valid(spec, out, f, row);
             seen |= 1u << f;
         } else {
             bool neg = false;
@@ -381,25 +482,37 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
             if (t.at(p) == '0' && p + 1 < end && t.at(p + 1) >= '0' && t.at(p + 1) <= '9') return kErrSyntax;  // JSON has no leading zeros
             uint64_t v = 0;
             int digits = 0;
+            uint32_t d20 = 0;   // (kN) a UInt64's twentieth digit
             while (p < end) {   // (A-JSON8: the digits to their end, then the tail, then the range)
                 const uint32_t c = t.at(p);
                 if (c < '0' || c > '9') break;
                 if (++digits <= 19) v = v * 10 + (c - '0');
+                else if (kN && digits == 20) d20 = c - '0';
                 ++p;
             }
             if (p < end) {
                 const uint32_t c = t.at(p);
-                if (!(c == ',' || c == '}' || is_ws(c))) return is_fraction_exponent(t, p, end) ? kErrNumber : kErrSyntax;  // "1.5": no integer literal; "1x", "1.": malformed
+                if (!(c == ',' || c == '}' || is_ws(c))) return is_fraction_exponent<kLds, Tag>(t, p, end) ? kErrNumber : kErrSyntax;  // "1.5": no integer literal; "1x", "1.": malformed
             }
-            if (digits > 19) return kErrRange;
-            if (v > (uint64_t)0x7fffffffffffffffull + (neg ? 1u : 0u)) return kErrRange;
-            const int64_t sv = neg ? (int64_t)(0 - v) : (int64_t)v;
-            if (spec.type[f] == kInt32) {
-                if (sv < -2147483648ll || sv > 2147483647ll) return kErrRange;
-                reinterpret_cast<int32_t *>(out.values[f])[row] = (int32_t)sv;
+            if (kN && spec.type[f] == kUInt64) {   // (A-JSONN5) 0 .. 2^64 - 1; a '-' is out of range, "-0" included
+                if (neg || digits > 20) return kErrRange;
+                if (digits == 20) {
+                    if (v > 1844674407370955161ull || (v == 1844674407370955161ull && d20 > 5u)) return kErrRange;
+                    v = v * 10 + d20;
+                }
+                reinterpret_cast<uint64_t *>(out.values[f])[row] = v;
             } else {
-                reinterpret_cast<int64_t *>(out.values[f])[row] = sv;
+                if (digits > 19) return kErrRange;
+                if (v > (uint64_t)0x7fffffffffffffffull + (neg ? 1u : 0u)) return kErrRange;
+                const int64_t sv = neg ? (int64_t)(0 - v) : (int64_t)v;
+                if (spec.type[f] == kInt32) {
+                    if (sv < -2147483648ll || sv > 2147483647ll) return kErrRange;
+                    reinterpret_cast<int32_t *>(out.values[f])[row] = (int32_t)sv;
+                } else {
+                    reinterpret_cast<int64_t *>(out.values[f])[row] = sv;
+                }
             }
+            put_valid(spec, out, f, row);
             seen |= 1u << f;
         }
         while (p < end && is_ws(t.at(p))) ++p;
@@ -415,6 +528,13 @@ __device__ uint32_t parse_line(const Text<kLds> &t, int32_t p, int32_t end, cons
         return kErrSyntax;
     }
     if (p != end) return kErrSyntax;  // trailing bytes after the object
+    if constexpr (kN) {   // (A-JSONN3) a nullable field that the line does not hold is NULL; a required one is missing as before
+        const uint32_t unseen = ((1u << spec.n) - 1u) & ~seen;
+        if (unseen & ~spec.nullable) return kErrMissing;
+        for (int f = 0; f < spec.n; ++f)
+            if ((unseen >> f) & 1u) put_null(spec, out, spec.type[f], f, row);
+        return 0;
+    }
     if (seen != (spec.n >= 32 ? ~0u : (1u << spec.n) - 1u)) return kErrMissing;
     return 0;
 }
@@ -502,14 +622,114 @@ __device__ __forceinline__ uint32_t leading_digits(uint64_t x, int nd) {
     return four_digits((uint32_t)t) * 10000u + four_digits((uint32_t)(t >> 32));
 }
 
+// (nullable entry) The run of ASCII digits at p, through up to three dword-aligned 8-byte reads, as the integer walk below reads it:
+// -> its length as far as 24 bytes show it, cut at `end`; *v = its value where that length is 1 .. 20 and the value fits 64 bits (*fits);
+// *first = the byte at p.  x0 = lds_u64(s, p), which the caller has read already.
+__device__ __forceinline__ int digits_words(const uint8_t *s, int32_t p, int32_t end, uint64_t x0, uint64_t *v, bool *fits, uint32_t *first) {
+    uint64_t x1 = 0, x2 = 0;
+    const uint64_t m0 = non_digit_flags(x0);
+    int total = m0 ? (__ffsll((unsigned long long)m0) - 1) >> 3 : 8;
+    if (total == 8 && p + 8 < end) {  // (never a read beyond the slack)
+        x1 = lds_u64(s, p + 8);
+        const uint64_t m1 = non_digit_flags(x1);
+        total += m1 ? (__ffsll((unsigned long long)m1) - 1) >> 3 : 8;
+        if (total == 16 && p + 16 < end) {
+            x2 = lds_u64(s, p + 16);
+            const uint64_t m2 = non_digit_flags(x2);
+            total += m2 ? (__ffsll((unsigned long long)m2) - 1) >> 3 : 8;
+        }
+    }
+    total = min(total, end - p);
+    *first = (uint32_t)x0 & 0xFFu;
+    *fits = true;
+    *v = 0;
+    if (total <= 0 || total > 20) return total;
+    const int lead = total - ((total - 1) & ~7);
+    uint64_t w = leading_digits(x0, lead);
+    if (total > 8) {
+        const int sh = 8 * lead;  // 8 .. 64
+        w = w * 100000000ull + leading_digits(lead == 8 ? x1 : (x0 >> sh) | (x1 << (64 - sh)), 8);
+        if (total > 16) {   // at most 12 digits so far: 2^64 - 1 = 184467440737 09551615
+            const uint64_t g = leading_digits(lead == 8 ? x2 : (x1 >> sh) | (x2 << (64 - sh)), 8);
+            *fits = w < 184467440737ull || (w == 184467440737ull && g <= 9551615ull);
+            w = w * 100000000ull + g;
+        }
+    }
+    *v = w;
+    return total;
+}
+
+// (nullable entry, A-JSONN6) A Float64 at *p as the compact writers print it: -?digits(.digits)?([eE][+-]?digits)? with at most 18 digits in
+// all and at most three in the exponent, converted with csv_f64's arithmetic (csv.hpp A-CSV5) where that is exact.  false: anything else --
+// longer, malformed, outside the exact range -- is the general parser's to take or to word.  x0 = lds_u64(s, *p).  What follows the number is
+// the caller's to check.
+__device__ __forceinline__ bool f64_words(const uint8_t *s, int32_t *pp, int32_t end, uint64_t x0, uint64_t *bits) {
+    int32_t p = *pp;
+    const bool neg = (x0 & 0xFFu) == '-';
+    if (neg) x0 = lds_u64(s, ++p);
+    uint64_t vi = 0, vf = 0;
+    bool fits;
+    uint32_t first;
+    const int ni = digits_words(s, p, end, x0, &vi, &fits, &first);
+    if (ni <= 0 || ni > 18 || (ni > 1 && first == '0')) return false;
+    p += ni;
+    uint64_t x = p < end ? lds_u64(s, p) : 0ull;
+    int nf = 0;
+    if ((x & 0xFFu) == '.') {
+        ++p;
+        if (p >= end) return false;
+        uint32_t unused;
+        nf = digits_words(s, p, end, lds_u64(s, p), &vf, &fits, &unused);
+        if (nf <= 0 || ni + nf > 18) return false;
+        p += nf;
+        x = p < end ? lds_u64(s, p) : 0ull;
+    }
+    int32_t exp10 = 0;
+    if (((x & 0xFFu) | 0x20u) == 'e') {   // e, a sign, up to three digits and the byte behind them: inside the eight bytes of x
+        int i = 1;
+        const uint32_t sign = (uint32_t)(x >> 8) & 0xFFu;
+        const bool eneg = sign == '-';
+        if (eneg || sign == '+') i = 2;
+        int ne = 0;
+        for (; ne < 4; ++ne) {
+            const uint32_t d = ((uint32_t)(x >> (8 * (i + ne))) & 0xFFu) - '0';
+            if (d > 9u) break;
+            exp10 = exp10 * 10 + (int32_t)d;
+        }
+        if (ne == 0 || ne == 4 || p + i + ne > end) return false;
+        p += i + ne;
+        exp10 = eneg ? -exp10 : exp10;
+    }
+    uint64_t w = vi * kPow10U[nf] + vf;   // (ni + nf <= 18 digits)
+    double v = 0.0;
+    if (w != 0) {
+        int32_t e = exp10 - nf;
+        while (w % 10u == 0) {   // the trailing zeros belong to the exponent
+            w /= 10u;
+            ++e;
+        }
+        if (w > kCsvMaxSignificand || e < -kCsvMaxPow10 || e > kCsvMaxPow10) return false;
+        v = e < 0 ? (double)w / kPow10[-e] : (double)w * kPow10[e];
+    }
+    *bits = (uint64_t)__double_as_longlong(neg ? -v : v);
+    *pp = p;
+    return true;
+}
+
 // (The LDS pipe is what this walk is bound by -- SQ_LDS_IDX_ACTIVE at 82 % of the kernel's cycles with the first version's
 // ~25 byte-offset reads per bid line: hence few reads, ~14 per line, and every one of them dword-aligned.)
 // kUnroll >= spec.n: the trip over the fields is unrolled at compile time, so that everything read from `spec` (the kernel's
 // argument block) sits at a constant offset and arrives in a few wide scalar loads up front -- indexed by a loop counter it
 // was ~8 dependent scalar loads per field, each waited for with the LDS counter.
-template <int kUnroll>
-__device__ __forceinline__ bool parse_line_words(const uint8_t *s, int32_t s_base, int32_t p, int32_t end, const JsonSpec &spec,
-                                                 int64_t row, const JsonOut &out) {
+//
+// Over a JsonNSpec (the nullable entry): where a nullable field's value begins, ONE 4-byte compare against `null` settles a NULL -- on the low
+// word of the eight bytes that the value's own walk reads there anyway, put together from dword-aligned reads exactly as lds_u32 does, so a
+// NULL costs no LDS read of its own and a line of `null`s stays with this walker.  A UInt64 takes the 20 digits the three words hold; a
+// Float64 goes through f64_words.  A member that is absent is the second kernel's.
+template <int kUnroll, class S, class O>
+__device__ __forceinline__ bool parse_line_words(const uint8_t *s, int32_t s_base, int32_t p, int32_t end, const S &spec,
+                                                 int64_t row, const O &out) {
+    constexpr bool kN = kIsNullable<S>;
     p -= s_base;
     end -= s_base;
 #pragma unroll
@@ -528,9 +748,19 @@ __device__ __forceinline__ bool parse_line_words(const uint8_t *s, int32_t s_bas
         }
         if (diff) return false;
         p += pl;
+        uint64_t xv = 0;   // (kN) the eight bytes at the value's start
+        if constexpr (kN) {
+            xv = lds_u64(s, p);
+            if (((spec.nullable >> f) & 1u) && (uint32_t)xv == kNullWord) {   // (what follows it is the next field's prefix, or the brace)
+                if (p + 4 > end) return false;
+                put_null(spec, out, spec.type[f], f, row);
+                p += 4;
+                continue;
+            }
+        }
         if (spec.type[f] == kUtf8) {
             const int32_t b = p + 1;
-            uint64_t x = lds_u64(s, p);
+            uint64_t x = kN ? xv : lds_u64(s, p);
             if ((x & 0xFFu) != '"') return false;
             x |= 0xFFu;  // the opening quote is not the closing one
             uint32_t c = 0;
@@ -552,9 +782,24 @@ __device__ __forceinline__ bool parse_line_words(const uint8_t *s, int32_t s_bas
             out.pairs[f][2 * row] = b + s_base;
             out.pairs[f][2 * row + 1] = p + s_base;
             out.ulen[f][row] = p - b;
+            put_valid(spec, out, f, row);
             ++p;
+        } else if (kN && spec.type[f] == kFloat64) {
+            uint64_t bits;
+            if (!f64_words(s, &p, end, xv, &bits)) return false;
+            reinterpret_cast<uint64_t *>(out.values[f])[row] = bits;
+            put_valid(spec, out, f, row);
+        } else if (kN && spec.type[f] == kUInt64) {   // (a '-' is the general parser's range error)
+            uint64_t v;
+            bool fits;
+            uint32_t first;
+            const int total = digits_words(s, p, end, xv, &v, &fits, &first);
+            if (total <= 0 || total > 20 || !fits || (total > 1 && first == '0')) return false;
+            p += total;
+            reinterpret_cast<uint64_t *>(out.values[f])[row] = v;
+            put_valid(spec, out, f, row);
         } else {
-            uint64_t x0 = lds_u64(s, p);
+            uint64_t x0 = kN ? xv : lds_u64(s, p);
             const bool neg = (x0 & 0xFFu) == '-';
             if (neg) x0 = lds_u64(s, ++p);
             // how many digits (up to 18), eight at a time; then the leading 1..8 digits and whole groups of eight, the
@@ -589,6 +834,7 @@ __device__ __forceinline__ bool parse_line_words(const uint8_t *s, int32_t s_bas
             } else {
                 reinterpret_cast<int64_t *>(out.values[f])[row] = sv;
             }
+            put_valid(spec, out, f, row);
         }
     }
     return p + 1 == end && s[p] == '}';
@@ -642,7 +888,11 @@ __device__ __forceinline__ Tok next_tok(const uint8_t *s, int32_t p, int32_t end
     return Tok{end, end, 0u};
 }
 
-__device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int32_t end, const JsonSpec &spec, const JsonOut &out, int64_t row) {
+// Over a JsonNSpec (the nullable entry): null for a nullable field is a NULL, and so is, at the closing brace, every nullable field that the
+// line did not hold.
+template <class S, class O>
+__device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int32_t end, const S &spec, const O &out, int64_t row) {
+    constexpr bool kN = kIsNullable<S>;
     p -= s_base;
     end -= s_base;
     while (end > p && is_ws(s[end - 1])) --end;
@@ -694,7 +944,16 @@ __device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int
         int32_t type = 0;
         for (int i = 0; i < spec.n; ++i)
             if (i == f) type = spec.type[i];
-        if (type == kUtf8) {
+        uint8_t *vb = nullptr;   // (kN) the validity bytes of a nullable field
+        if constexpr (kN) {
+            for (int i = 0; i < spec.n; ++i)
+                if (i == f && ((spec.nullable >> i) & 1u)) vb = out.valid[i];
+        }
+        if (kN && vb && lds_u32(s, p) == kNullWord) {   // (what follows it is checked as a separator below)
+            if (p + 4 > end) return false;
+            put_null(spec, out, type, f, row);
+            p += 4;
+        } else if (type == kUtf8) {
             const int32_t b = p + 1;
             uint64_t x = lds_u64(s, p);
             if ((x & 0xFFu) != '"') return false;
@@ -719,7 +978,28 @@ __device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int
             pairs[2 * row] = b + s_base;
             pairs[2 * row + 1] = p + s_base;
             ulen[row] = p - b;
+            if (kN && vb) vb[row] = 1;
             ++p;
+        } else if (kN && (type == kFloat64 || type == kUInt64)) {
+            uint64_t bits;
+            if (type == kFloat64) {
+                if (!f64_words(s, &p, end, lds_u64(s, p), &bits)) return false;
+            } else {
+                bool fits;
+                uint32_t first;
+                const int total = digits_words(s, p, end, lds_u64(s, p), &bits, &fits, &first);
+                if (total <= 0 || total > 20 || !fits || (total > 1 && first == '0')) return false;
+                p += total;
+            }
+            if (p < end) {   // what follows a number: a delimiter (anything else is the general parser's to word)
+                const uint32_t c = s[p];
+                if (!(c == ',' || c == '}' || is_ws(c))) return false;
+            }
+            uint64_t *col = nullptr;
+            for (int i = 0; i < spec.n; ++i)
+                if (i == f) col = reinterpret_cast<uint64_t *>(out.values[i]);
+            col[row] = bits;
+            if (vb) vb[row] = 1;
         } else {
             uint64_t x0 = lds_u64(s, p);
             const bool neg = (x0 & 0xFFu) == '-';
@@ -761,6 +1041,7 @@ __device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int
             } else {
                 reinterpret_cast<int64_t *>(col)[row] = sv;
             }
+            if (kN && vb) vb[row] = 1;
         }
         // ---- , or }
         const Tok sep = next_tok(s, p, end);
@@ -770,6 +1051,13 @@ __device__ bool parse_line_flex(const uint8_t *s, int32_t s_base, int32_t p, int
         }
         if (sep.c != ',') return false;
         p = sep.after;
+    }
+    if constexpr (kN) {   // (A-JSONN3) the nullable fields the line did not hold; a required one is the general parser's error
+        const uint32_t unseen = ((1u << spec.n) - 1u) & ~seen;
+        if (p != end || (unseen & ~spec.nullable)) return false;
+        for (int f = 0; f < spec.n; ++f)
+            if ((unseen >> f) & 1u) put_null(spec, out, spec.type[f], f, row);
+        return true;
     }
     return p == end && seen == (spec.n >= 32 ? ~0u : (1u << spec.n) - 1u);
 }
@@ -834,6 +1122,84 @@ __global__ __launch_bounds__(kBlock) void json_parse_kernel(const uint8_t *__res
         rc = parse_line_fast(t, p, e, s_spec, line, out) ? 0u : parse_line(t, p, e, s_spec, line, out);
     }
     if (rc) atomicMin(err, ((unsigned long long)line << 8) | rc);
+}
+
+// The nullable entry's two kernels: json_parse_kernel's frame over JsonNSpec / JsonNOut.  A kernel of their own, so that the instances
+// above stay what flockgpu_json_lines_decode has always launched.  The lane that parses a row writes its validity bytes (row = line:
+// consecutive bytes across a wave).  A workgroup whose lines do not fit the stage goes through the general parser alone.
+template <int kUnroll, bool kRetry>
+__global__ __launch_bounds__(kBlock) void json_nparse_kernel(const uint8_t *__restrict__ bytes, int64_t n_bytes,
+                                                             const int32_t *__restrict__ line_start, int64_t n_lines, JsonNSpec spec,
+                                                             JsonNOut out, int32_t stage_bytes, uint32_t *block_retry, uint32_t *any_retry,
+                                                             unsigned long long *err) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_stage[];
+    __shared__ JsonNSpec s_spec;
+    __shared__ JsonNOut s_out;   // (kRetry) the general parser indexes the columns with its own f as well: a by-value argument it takes by reference costs a copy in scratch
+    if (kRetry) {
+        if (block_retry && !block_retry[blockIdx.x]) return;
+        for (int i = threadIdx.x; i < (int)(sizeof(JsonNSpec) / 4); i += kBlock)
+            reinterpret_cast<uint32_t *>(&s_spec)[i] = reinterpret_cast<const uint32_t *>(&spec)[i];
+        for (int i = threadIdx.x; i < (int)(sizeof(JsonNOut) / 4); i += kBlock)
+            reinterpret_cast<uint32_t *>(&s_out)[i] = reinterpret_cast<const uint32_t *>(&out)[i];
+    }
+    const int64_t l0 = (int64_t)blockIdx.x * kParseLines;
+    const int64_t l1 = min(l0 + kParseLines, n_lines);
+    const int32_t b0 = line_start[l0], b1 = min((int64_t)line_start[l1], n_bytes);
+    const int32_t a0 = b0 & ~15;
+    const bool staged = b1 - a0 + 16 <= stage_bytes;
+    const int64_t line = l0 + threadIdx.x;
+    const int64_t line_c = min(line, n_lines - 1);
+    const int32_t p = line_start[line_c];
+    const int32_t e = min((int64_t)line_start[line_c + 1] - 1, n_bytes);
+    if (staged) {
+        for (int32_t o = a0 + (int32_t)threadIdx.x * 16; o < b1; o += kBlock * 16) {
+            if ((int64_t)o + 16 <= n_bytes) {
+                *reinterpret_cast<uint4 *>(s_stage + (o - a0)) = *reinterpret_cast<const uint4 *>(bytes + o);
+            } else {
+                for (int32_t i = o; i < b1; ++i) s_stage[i - a0] = bytes[i];
+            }
+        }
+    }
+    __syncthreads();
+    if (!kRetry) {
+        const bool bad = line < n_lines && !(staged && parse_line_words<kUnroll>(s_stage, a0, p, e, spec, line, out));
+        const bool any = __syncthreads_or(bad);
+        if (threadIdx.x == 0) {
+            block_retry[blockIdx.x] = any ? 1u : 0u;
+            if (any) atomicOr(any_retry, 1u);
+        }
+        return;
+    }
+    if (line >= n_lines) return;
+    uint32_t rc;
+    if (staged) {
+        const Text<true> t{bytes, s_stage, a0};
+        rc = parse_line_flex(s_stage, a0, p, e, spec, out, line) ? 0u : parse_line(t, p, e, s_spec, line, s_out);
+    } else {
+        const Text<false> t{bytes, nullptr, 0};
+        rc = parse_line(t, p, e, s_spec, line, s_out);
+    }
+    if (rc) atomicMin(err, ((unsigned long long)line << 8) | rc);
+}
+
+// null_count per nullable field (blockIdx.y): the validity bytes are 0 or 1, sixteen of them per lane and trip.  The grid is capped
+// (kNullCountBlocks) and strides over the rows: one atomic per wave on ONE address per field, so few waves -- with a workgroup per 4096 rows the
+// 72 000 atomics per field of 1.84e7 rows took longer than the parse (profiles/json_nullable/bench_null_count_uncapped.json).
+__global__ __launch_bounds__(kBlock) void json_null_count_kernel(JsonNOut out, uint32_t nullable, int64_t n, unsigned long long *__restrict__ nulls) {
+    const int f = (int)blockIdx.y;
+    if (!((nullable >> f) & 1u)) return;
+    const uint8_t *__restrict__ v = out.valid[f];
+    uint32_t zeros = 0;
+    for (int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 16; i0 < n; i0 += (int64_t)gridDim.x * kBlock * 16) {
+        if (i0 + 16 <= n) {
+            const uint4 w = *reinterpret_cast<const uint4 *>(v + i0);
+            zeros += 16u - (uint32_t)(__popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w));
+        } else {
+            for (int64_t i = i0; i < n; ++i) zeros += v[i] == 0 ? 1u : 0u;
+        }
+    }
+    const uint32_t incl = wave_incl_scan_u32(zeros);
+    if (lane_id() == 63 && incl) atomicAdd(nulls + f, (unsigned long long)incl);
 }
 
 // Utf8 field after the parse: len[i] = |ulen[i]| (unescaped length), any = some value needs unescaping
@@ -932,23 +1298,29 @@ __global__ __launch_bounds__(kBlock) void json_even_rows_kernel(int32_t *__restr
     if (i < n) rows[i] = (int32_t)(2 * i);
 }
 
-}  // namespace
+// One field as both entry points hand it on: the type in this file's numbering (kInt32 .. kFloat64)
+struct FieldIn {
+    const char *name;
+    int32_t type;
+    bool nullable;
+};
 
-extern "C" {
-
-int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n_bytes, const flockgpu_json_field *fields,
-                               int32_t n_fields, flockgpu_json_column *out, int64_t *rows) {
-    if (!ctx) return FLOCKGPU_ERR_INVALID;
-    if (!fields || !out || !rows || n_bytes < 0 || n_fields < 1 || (n_bytes > 0 && !json))
-        return fail(ctx, FLOCKGPU_ERR_INVALID, "json: null argument");
-    if (n_fields > kMaxFields) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: more than %d fields", kMaxFields);
+// Both entry points.  kN = false is flockgpu_json_lines_decode: JsonSpec, the json_parse_kernel instances, the route hint "json.retry_hint".
+// kN = true is flockgpu_json_lines_decode_nullable: JsonNSpec, json_nparse_kernel, validity bytes and null counts, a route hint of its own.
+// `fields` holds 1 .. kMaxFields entries, a type outside this file's numbering as -1; `out` is zeroed.
+template <bool kN>
+int decode_lines(flockgpu_ctx *ctx, const uint8_t *json, int64_t n_bytes, const FieldIn *fields, int32_t n_fields, flockgpu_json_ncolumn *out,
+                 int64_t *rows) {
+    using Spec = typename std::conditional<kN, JsonNSpec, JsonSpec>::type;
+    using Out = typename std::conditional<kN, JsonNOut, JsonOut>::type;
     if (n_bytes >= (int64_t(1) << 31) - 16)
         return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: at most 2^31 bytes of text per call (Arrow Utf8 offsets are int32)");
     if (reinterpret_cast<uintptr_t>(json) & 15) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: the text must be 16-byte aligned");
-    JsonSpec spec{};
+    Spec spec{};
     spec.n = n_fields;
+    uint32_t nullable = 0;
     for (int f = 0; f < n_fields; ++f) {
-        if (!fields[f].name || fields[f].type < kInt32 || fields[f].type > kUtf8) return fail(ctx, FLOCKGPU_ERR_INVALID, "json: bad field %d", f);
+        if (!fields[f].name || fields[f].type < kInt32 || fields[f].type > (kN ? kFloat64 : kUtf8)) return fail(ctx, FLOCKGPU_ERR_INVALID, "json: bad field %d", f);
         const size_t len = std::strlen(fields[f].name);
         if (len == 0 || len >= (size_t)kMaxName) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: field name longer than %d bytes", kMaxName - 1);
         spec.type[f] = fields[f].type;
@@ -962,9 +1334,10 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
         pre[len + 3] = ':';
         spec.pre_len[f] = (int32_t)len + 4;
         std::memcpy(spec.pre[f], pre, sizeof spec.pre[f]);
+        if (fields[f].nullable) nullable |= 1u << f;
     }
+    if constexpr (kN) spec.nullable = nullable;
     FG_HIP(ctx, hipSetDevice(ctx->device));
-    for (int f = 0; f < n_fields; ++f) out[f] = flockgpu_json_column{};
     *rows = 0;
 
     // ---- line index
@@ -1008,7 +1381,19 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
     }
 
     // ---- parse
-    JsonOut jo{};
+    Out jo{};
+    unsigned long long *d_nulls = nullptr, *h_nulls = nullptr;   // (kN) NULLs per field
+    if constexpr (kN) {
+        for (int f = 0; f < n_fields; ++f) {
+            if (!((nullable >> f) & 1u)) continue;
+            char name[48];
+            snprintf(name, sizeof name, "json.valid.%d", f);
+            FG_TRY(arena_get_t(ctx, name, ((size_t)n_lines + 31) & ~size_t(15), &jo.valid[f]));   // (a multiple of 16: json_null_count_kernel's loads)
+        }
+        FG_TRY(arena_get_t(ctx, "json.nulls", kMaxFields, &d_nulls));
+        FG_TRY(pinned_get_t(ctx, "json.nulls", kMaxFields, &h_nulls));
+        std::memset(h_nulls, 0, sizeof(unsigned long long) * kMaxFields);
+    }
     for (int f = 0; f < n_fields; ++f) {
         char name[48];
         if (spec.type[f] == kUtf8) {
@@ -1049,7 +1434,7 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
     const int32_t stage_bytes = (int32_t)std::min<int64_t>(kStageBytes, (want + 1023) & ~int64_t(1023));
     // hint = {route, calls on that route}: when most workgroups of a call ended in the second kernel (a writer other than serde_json)
     // the next calls go there directly; every sixteenth of them tries the compact walk first again
-    std::vector<int64_t> &hint = ctx->host_i64["json.retry_hint"];
+    std::vector<int64_t> &hint = ctx->host_i64[kN ? "json.nullable_retry_hint" : "json.retry_hint"];   // (one per entry point: alternating calls leave each other's alone)
     if (hint.size() < 2) hint.assign(2, 0);
     const bool straight = hint[0] == 1 && (++hint[1] % 16) != 0;
     *h_any_retry = 0;
@@ -1058,14 +1443,33 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
         if (n_lines > 0) {
             if (!second) FG_HIP(ctx, hipMemsetAsync(d_any_retry, 0, sizeof(uint32_t), ctx->stream));
             FG_HIP(ctx, hipMemsetAsync(d_any, 0, sizeof(uint32_t) * kMaxFields, ctx->stream));
-            auto kernel = second ? (n_fields <= 4 ? json_parse_kernel<4, true> : n_fields <= 8 ? json_parse_kernel<8, true> : json_parse_kernel<kMaxFields, true>)
-                                 : (n_fields <= 4 ? json_parse_kernel<4, false> : n_fields <= 8 ? json_parse_kernel<8, false> : json_parse_kernel<kMaxFields, false>);
-            {
-                LaunchScope ls(ctx, second ? "json_parse_retry_kernel" : "json_parse_kernel");
+            const char *kernel_name = kN ? (second ? "json_nparse_retry_kernel" : "json_nparse_kernel") : (second ? "json_parse_retry_kernel" : "json_parse_kernel");
+            if constexpr (kN) {
+                auto kernel = second ? (n_fields <= 4 ? json_nparse_kernel<4, true> : n_fields <= 8 ? json_nparse_kernel<8, true> : json_nparse_kernel<kMaxFields, true>)
+                                     : (n_fields <= 4 ? json_nparse_kernel<4, false> : n_fields <= 8 ? json_nparse_kernel<8, false> : json_nparse_kernel<kMaxFields, false>);
+                LaunchScope ls(ctx, kernel_name);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)n_blocks), dim3(kBlock), (size_t)stage_bytes, ctx->stream, json, n_bytes, line_start, n_lines, spec, jo,
+                                   stage_bytes, second && straight ? (uint32_t *)nullptr : d_retry, d_any_retry, d_err);
+            } else {
+                auto kernel = second ? (n_fields <= 4 ? json_parse_kernel<4, true> : n_fields <= 8 ? json_parse_kernel<8, true> : json_parse_kernel<kMaxFields, true>)
+                                     : (n_fields <= 4 ? json_parse_kernel<4, false> : n_fields <= 8 ? json_parse_kernel<8, false> : json_parse_kernel<kMaxFields, false>);
+                LaunchScope ls(ctx, kernel_name);
                 hipLaunchKernelGGL(kernel, dim3((unsigned)n_blocks), dim3(kBlock), (size_t)stage_bytes, ctx->stream, json, n_bytes, line_start, n_lines, spec, jo,
                                    stage_bytes, second && straight ? (uint32_t *)nullptr : d_retry, d_any_retry, d_err);
             }
-            FG_TRY(check_launch(ctx, second ? "json_parse_retry_kernel" : "json_parse_kernel"));
+            FG_TRY(check_launch(ctx, kernel_name));
+            if constexpr (kN) {   // null_count per field, behind the parse and in front of the round's one host wait
+                if (nullable) {
+                    FG_HIP(ctx, hipMemsetAsync(d_nulls, 0, sizeof(unsigned long long) * kMaxFields, ctx->stream));
+                    {
+                        LaunchScope ls(ctx, "json_null_count_kernel");
+                        hipLaunchKernelGGL(json_null_count_kernel, dim3((unsigned)std::min<int64_t>(kNullCountBlocks, div_up(n_lines, (int64_t)kBlock * 16)), (unsigned)n_fields), dim3(kBlock), 0,
+                                           ctx->stream, jo, nullable, n_lines, d_nulls);
+                    }
+                    FG_TRY(check_launch(ctx, "json_null_count_kernel"));
+                    FG_HIP(ctx, hipMemcpyAsync(h_nulls, d_nulls, sizeof(unsigned long long) * kMaxFields, hipMemcpyDeviceToHost, ctx->stream));
+                }
+            }
             for (int f = 0; f < n_fields; ++f) {
                 if (spec.type[f] != kUtf8) continue;
                 hipLaunchKernelGGL(json_string_lengths_kernel, dim3((unsigned)div_up(n_lines, kBlock)), dim3(kBlock), 0, ctx->stream, jo.ulen[f], n_lines, soff[f],
@@ -1097,6 +1501,10 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
     if (*h_err != ~0ull) {
         const long long line = (long long)(*h_err >> 8);
         const uint32_t code = (uint32_t)(*h_err & 0xFF);
+        if (kN && (code & 0xFu) == kErrFloat)   // (A-JSONN6; the field in the code's upper four bits)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED,
+                        "json: line %lld: field '%s': Float64 outside the exactly convertible range (a significand of at most 2^53, a decimal exponent in [-22, 22])",
+                        line + 1, fields[(code >> 4) < (uint32_t)n_fields ? code >> 4 : 0].name);
         static const char *what[] = {"", "malformed JSON", "number with a fraction / exponent (integer literal expected)",
                                      "a schema field is missing", "blank line", "escape sequence in a key", "integer out of range",
                                      "brackets nested more than 64 deep in a member that is not in the schema"};
@@ -1107,6 +1515,10 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
     int32_t *even = nullptr;
     bool have_even = false;
     for (int f = 0; f < n_fields; ++f) {
+        if constexpr (kN) {
+            out[f].valid = jo.valid[f];
+            out[f].null_count = (int64_t)h_nulls[f];
+        }
         if (spec.type[f] != kUtf8) {
             out[f].values = jo.values[f];
             continue;
@@ -1146,6 +1558,55 @@ int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n
     }
     *rows = n_lines;
     return FLOCKGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flockgpu_json_lines_decode(flockgpu_ctx *ctx, const uint8_t *json, int64_t n_bytes, const flockgpu_json_field *fields,
+                               int32_t n_fields, flockgpu_json_column *out, int64_t *rows) {
+    if (!ctx) return FLOCKGPU_ERR_INVALID;
+    if (!fields || !out || !rows || n_bytes < 0 || n_fields < 1 || (n_bytes > 0 && !json))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "json: null argument");
+    if (n_fields > kMaxFields) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: more than %d fields", kMaxFields);
+    FieldIn in[kMaxFields];
+    flockgpu_json_ncolumn cols[kMaxFields] = {};
+    for (int f = 0; f < n_fields; ++f)   // (FLOCKGPU_JSON_* is this file's numbering; anything else is "bad field")
+        in[f] = FieldIn{fields[f].name, fields[f].type >= kInt32 && fields[f].type <= kUtf8 ? fields[f].type : -1, false};
+    for (int f = 0; f < n_fields; ++f) out[f] = flockgpu_json_column{};
+    const int rc = decode_lines<false>(ctx, json, n_bytes, in, n_fields, cols, rows);
+    if (rc != FLOCKGPU_OK) return rc;
+    for (int f = 0; f < n_fields; ++f) {
+        out[f].values = cols[f].values;
+        out[f].utf8 = cols[f].utf8;
+        out[f].utf8_bytes = cols[f].utf8_bytes;
+    }
+    return FLOCKGPU_OK;
+}
+
+int flockgpu_json_lines_decode_nullable(flockgpu_ctx *ctx, const uint8_t *json, int64_t n_bytes, const flockgpu_json_nfield *fields,
+                                        int32_t n_fields, flockgpu_json_ncolumn *out, int64_t *rows) {
+    if (!ctx) return FLOCKGPU_ERR_INVALID;
+    if (!fields || !out || !rows || n_bytes < 0 || n_fields < 1 || (n_bytes > 0 && !json))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "json: null argument");
+    if (n_fields > kMaxFields) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "json: more than %d fields", kMaxFields);
+    FieldIn in[kMaxFields];
+    for (int f = 0; f < n_fields; ++f) {
+        int32_t type = -1;   // FLOCKGPU_TEXT_* -> this file's numbering
+        switch (fields[f].type) {
+            case FLOCKGPU_TEXT_INT32: type = kInt32; break;
+            case FLOCKGPU_TEXT_INT64: type = kInt64; break;
+            case FLOCKGPU_TEXT_TIMESTAMP_MS: type = kInt64; break;
+            case FLOCKGPU_TEXT_UINT64: type = kUInt64; break;
+            case FLOCKGPU_TEXT_FLOAT64: type = kFloat64; break;
+            case FLOCKGPU_TEXT_UTF8: type = kUtf8; break;
+            default: break;
+        }
+        in[f] = FieldIn{fields[f].name, type, fields[f].nullable != 0};
+        out[f] = flockgpu_json_ncolumn{};
+    }
+    return decode_lines<true>(ctx, json, n_bytes, in, n_fields, out, rows);
 }
 
 }  // extern "C"

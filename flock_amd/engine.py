@@ -614,6 +614,55 @@ class GpuContext:
                 out[name] = col
         return out, n
 
+    def json_lines_decode_nullable(self, text, fields, borrow=False):
+        """Newline-delimited JSON (uint8 device tensor, 16-byte aligned) -> columns with NULLs (flockgpu_json_lines_decode_nullable; the rules are
+        A-JSONN1..7 in csrc/json.hip): what json_lines_encode writes reads back, `null` and absent members included.  `fields` = [(name, type)] or
+        [(name, type, nullable)] with csv_decode's type names ("int32" | "int64" | "uint64" | "float64" | "timestamp_ms" | "utf8"); nullable
+        defaults to True, and a field that is not nullable behaves as in json_lines_decode.  Returns ({name: tensor | DeviceUtf8}, {name: validity
+        tensor (uint8, 1 = not NULL) of the columns that hold NULLs, Utf8 included}, rows) -- csv_decode's shape, which feed_device_sources and
+        the encoders take as it is; a column without NULLs carries no validity.  uint64 comes as an int64 tensor of the bits, float64 as
+        float64.  borrow: views of the library's own result columns (valid until the next call on this context) instead of copies."""
+        torch = _torch()
+        kinds = {"int32": _ffi.TEXT_INT32, "int64": _ffi.TEXT_INT64, "uint64": _ffi.TEXT_UINT64, "float64": _ffi.TEXT_FLOAT64,
+                 "timestamp_ms": _ffi.TEXT_TIMESTAMP_MS, "utf8": _ffi.TEXT_UTF8}
+        fields = [(f[0], f[1], bool(f[2]) if len(f) > 2 else True) for f in fields]
+        for name, t, _ in fields:
+            if t not in kinds:
+                raise ValueError(f"json_lines_decode_nullable: field {name!r}: unknown type {t!r}")
+        spec = (_ffi.JsonNField * max(len(fields), 1))(*[_ffi.JsonNField(n.encode(), kinds[t], 1 if nl else 0) for n, t, nl in fields])
+        cols = (_ffi.JsonNColumn * max(len(fields), 1))()
+        rows = C.c_int64(0)
+        self._check(self._lib.flockgpu_json_lines_decode_nullable(self._h, text.data_ptr(), text.numel(), spec, len(fields), cols, C.byref(rows)))
+        n, dev, out, valid = rows.value, f"cuda:{self.device}", {}, {}
+
+        def take(ptr, count, dtype, width):
+            if borrow:
+                return self._device_view(ptr, count, dtype)
+            t = torch.empty(count, dtype=dtype, device=dev)
+            if count:
+                self._check(self._lib.flockgpu_memcpy(self._h, t.data_ptr(), ptr, count * width, _ffi.D2D))
+            return t
+
+        for (name, t, _), c in zip(fields, cols):
+            if t == "utf8":
+                if borrow:
+                    out[name] = DeviceUtf8(self._device_view(c.utf8.offsets, n + 1, torch.int32), self._device_view(c.utf8.data, int(c.utf8_bytes), torch.uint8))
+                else:
+                    off = take(c.utf8.offsets, n + 1, torch.int32, 4) if n else torch.zeros(1, dtype=torch.int32, device=dev)
+                    data = torch.empty(max(int(c.utf8_bytes), 16), dtype=torch.uint8, device=dev)
+                    if c.utf8_bytes:
+                        self._check(self._lib.flockgpu_memcpy(self._h, data.data_ptr(), c.utf8.data, int(c.utf8_bytes), _ffi.D2D))
+                    out[name] = DeviceUtf8(off, data)
+            elif t == "int32":
+                out[name] = take(c.values, n, torch.int32, 4)
+            elif t == "float64":   # (the view helper knows integer types: the bits, then the type)
+                out[name] = take(c.values, n, torch.int64, 8).view(torch.float64)
+            else:
+                out[name] = take(c.values, n, torch.int64, 8)
+            if c.null_count:
+                valid[name] = take(c.valid, n, torch.uint8, 1)
+        return out, valid, n
+
     def csv_decode(self, text, fields, delimiter=",", has_header=True, borrow=False):
         """Delimited text (uint8 device tensor, 16-byte aligned) -> columns (flockgpu_csv_decode; the rules are A-CSV1..7 in csrc/csv.hpp).
         `fields` lists EVERY column of the file in file order: [(name, "int32" | "int64" | "uint64" | "float64" | "timestamp_ms" | "utf8" | None)],

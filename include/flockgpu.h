@@ -439,6 +439,39 @@ int flockgpu_json_lines_encode(flockgpu_ctx *ctx, const flockgpu_text_column *co
 int flockgpu_csv_encode(flockgpu_ctx *ctx, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows,
                         const flockgpu_csv_options *opt /* delimiter; has_header: write one */, flockgpu_text_result *out);
 
+/* ---- JSON lines -> columns with NULLs (json.hip): reads what flockgpu_json_lines_encode writes, and what writers other than serde_json
+ * produce -- `null` and members that are simply not there.  An entry point BESIDE flockgpu_json_lines_decode, whose rules, messages and
+ * kernels stay as they are.  Lines, grammar, dropped members, repeated keys (the last occurrence wins), verbatim bytes, error order and the
+ * limits (1 .. 16 fields, names of 1 .. 31 bytes, "json: line N: ...") are flockgpu_json_lines_decode's.  What is new (A-JSONN1..7 at the
+ * top of csrc/json.hip):
+ *   - every field is required (nullable = 0: exactly the first entry point's behaviour, null or absence is FLOCKGPU_ERR_INVALID with its
+ *     messages) or nullable: the literal null, and a line that lacks the member, give a NULL -- valid[i] = 0 and value 0; a Utf8 NULL is a
+ *     value of length 0 with valid[i] = 0, "" one with valid[i] = 1.  {} is a row of NULLs when every field is nullable;
+ *   - the encoders' six types, FLOCKGPU_TEXT_*: Timestamp(ms) is a JSON integer in Int64's range, UInt64 an integer literal in
+ *     0 .. 18446744073709551615 (a '-' in front, "-0" included, is out of range), Float64 a JSON number that is converted only inside
+ *     flockgpu_csv_decode's exact range (a significand of at most 2^53, a decimal exponent in [-22, 22]; "3" is 3.0, "-0.0" is -0.0) and
+ *     refused outside it with FLOCKGPU_ERR_UNSUPPORTED, the message naming the line and the field;
+ *   - true, false, a string for a number, a number for a string, nul, NULL, nullx: FLOCKGPU_ERR_INVALID; an integer field with a well-formed
+ *     fraction / exponent and a blank line stay FLOCKGPU_ERR_UNSUPPORTED.
+ * `valid` (one byte per row, 1 = not NULL) is written for every nullable field, Utf8 included, and is a null pointer for a required one;
+ * null_count is filled per column.  Outputs are ctx-owned and valid until the next call on the context.  `json`: device text, 16-byte
+ * aligned, below 2^31 - 16 bytes; no byte at or past json + n_bytes is read. */
+typedef struct {
+    const char *name; /* host, 1 .. 31 bytes */
+    int32_t type;     /* FLOCKGPU_TEXT_* */
+    int32_t nullable; /* non-zero: null and an absent member are NULL */
+} flockgpu_json_nfield;
+typedef struct {
+    void *values;       /* device: int32_t / int64_t / uint64_t / double per row (NULL for Utf8) */
+    uint8_t *valid;     /* device: one byte per row, 1 = not NULL (NULL pointer for a required field) */
+    int64_t null_count; /* rows whose valid byte is 0 */
+    flockgpu_utf8 utf8; /* device: offsets (rows + 1) and bytes of a Utf8 field */
+    int64_t utf8_bytes;
+} flockgpu_json_ncolumn;
+int flockgpu_json_lines_decode_nullable(flockgpu_ctx *ctx, const uint8_t *json /* device, 16-byte aligned */, int64_t n_bytes,
+                                        const flockgpu_json_nfield *fields, int32_t n_fields, flockgpu_json_ncolumn *out /* n_fields */,
+                                        int64_t *rows);
+
 /* ---- Arrow IPC body assembly: the body of the Arrow Flight data the reference builds for
  * every output batch (`flight_data_from_arrow_batch`, flock/src/transmute.rs:155-170,190-205; `Payload`,
  * flock/src/runtime/payload.rs:118-192) = the batch's buffers in field order, each padded with zeros to 8 bytes.
