@@ -6,6 +6,7 @@ import struct
 import numpy as np
 import pyarrow as pa
 
+import null_poison as npz
 import plan_corpus as pc
 import plan_interp as pi
 
@@ -39,18 +40,23 @@ def batch_rows(batches):
     return rows
 
 
-def host_batch(fields, table, lo=0, hi=None):
+def host_batch(fields, table, lo=0, hi=None, poison=None, leaf=0):
+    """poison: None, or (pool, key) -- the NULL slots hold tests/null_poison.py's values for leaf `leaf` of that key"""
     arrs = []
     for f in fields:
+        if poison is not None:
+            arrs.append(npz.poisoned_column(poison[0], poison[1], leaf, f["name"], table[f["name"]], f["data_type"], lo, hi))
+            continue
         ty, vals = arrow_type(f["data_type"]), table[f["name"]][lo:hi]
         arrs.append(pa.array(vals, pa.int64()).cast(ty) if pa.types.is_timestamp(ty) else pa.array(vals, ty))
     return pa.record_batch(arrs, names=[f["name"] for f in fields])
 
 
-def device_source(fields, table, lo=0, hi=None, device="cuda:0", validity="nulls", shift=0, null_slot=0):
+def device_source(fields, table, lo=0, hi=None, device="cuda:0", validity="nulls", shift=0, null_slot=0, poison=None, leaf=0):
     """Rows [lo, hi) of `table` as (columns, valid) for feed_columns.  validity: "nulls" -- validity bytes for the columns that hold a NULL in these
     rows; "always" -- for every column, all 1 where there is none.  shift: every tensor is the [shift:] slice of a larger one (values, validity and
-    offsets alike: element-aligned, not 16-byte aligned) and a Utf8 column's offsets start at 3 instead of 0.  NULL slots hold `null_slot` / ''."""
+    offsets alike: element-aligned, not 16-byte aligned) and a Utf8 column's offsets start at 3 instead of 0.  NULL slots hold `null_slot` / '' -- or, poison = (pool, key), what tests/null_poison.py puts under the NULLs of leaf
+    `leaf` of that key: values of the pool, and BYTES under the NULL rows of a Utf8 column (a row's poison does not depend on lo and hi)."""
     import torch
     from flock_amd.engine import DeviceUtf8
 
@@ -62,11 +68,12 @@ def device_source(fields, table, lo=0, hi=None, device="cuda:0", validity="nulls
     for f in fields:
         name, t = f["name"], f["data_type"]
         vals = table[name][lo:hi]
+        under = npz.slots(poison[0], *poison[1], leaf, name, table[name], t)[lo:hi] if poison is not None else None
         ok = np.array([v is not None for v in vals], np.uint8)
         if validity == "always" or not ok.all():
             valid[name] = dev(ok)
         if t == "Utf8":
-            raw = [b"" if v is None else v.encode() for v in vals]
+            raw = under if under is not None else [b"" if v is None else v.encode() for v in vals]
             junk = b"\x01\x02\x03" if shift else b""
             off = np.zeros(len(raw) + 1, np.int32)
             off[1:] = np.cumsum([len(b) for b in raw], dtype=np.int64)
@@ -74,7 +81,7 @@ def device_source(fields, table, lo=0, hi=None, device="cuda:0", validity="nulls
             columns.append((name, "utf8", DeviceUtf8(dev(off + len(junk)), torch.from_numpy(data).to(device))))
             continue
         kind, dtype = ("timestamp_ms", np.int64) if isinstance(t, dict) else _DEV[t]
-        arr = np.array([null_slot if v is None else v for v in vals], dtype=dtype)
+        arr = npz.numeric_slots(under, t) if under is not None else np.array([null_slot if v is None else v for v in vals], dtype=dtype)
         if dtype is np.uint64:
             arr = arr.view(np.int64)
         columns.append((name, kind, dev(arr)))
@@ -140,11 +147,11 @@ class Run:
             used.add(i)
             self.leaf.append(i)
 
-    def host(self, t, table, lo=0, hi=None):
-        self.p.feed(self.leaf[t], [host_batch(self.fields[t], table, lo, hi)])
+    def host(self, t, table, lo=0, hi=None, poison=None):
+        self.p.feed(self.leaf[t], [host_batch(self.fields[t], table, lo, hi, poison=poison, leaf=t)])
 
     def device(self, t, table, lo=0, hi=None, borrow=False, **kw):
-        columns, valid = device_source(self.fields[t], table, lo, hi, device=f"cuda:{self.gpu.device}", **kw)
+        columns, valid = device_source(self.fields[t], table, lo, hi, device=f"cuda:{self.gpu.device}", leaf=t, **kw)
         self.p.feed_columns(self.leaf[t], columns, valid, borrow=borrow)
         return columns, valid
 

@@ -290,6 +290,59 @@ def test_nulls_in_a_droppable_key_drop_the_rows_the_host_feed_drops(gpu, kind):
     _check_route(kind, ran)
 
 
+# ---- what lies under a NULL (tests/null_poison.py, the far pool: type extremes, NaNs, texts that match, that do not parse and that are no UTF-8)
+def _far(kind):
+    return ("far", ("device_feed", u.KINDS.index(kind), 0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [5, BIG])
+@pytest.mark.parametrize("kind", u.KINDS)
+def test_device_fed_and_host_fed_over_far_poison_equal_the_interpreter(gpu, kind, n):
+    """test_device_fed_equals_host_fed_equals_the_interpreter with hostile values and bytes under every NULL, from the host and from the device"""
+    tables, want = _tables(kind, n), _want(kind, n)
+    assert any(v is None for t in tables for col in t.values() for v in col)
+    host = _fed(gpu, kind, tables, lambda run, t, table: run.host(t, table, poison=_far(kind)))
+    dev = _fed(gpu, kind, tables, lambda run, t, table: run.device(t, table, poison=_far(kind)))
+    assert host == want, (kind, n, "host-fed differs from the interpreter")
+    assert dev == want, (kind, n, "device-fed differs")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", u.KINDS)
+def test_far_poison_under_the_nulls_of_a_droppable_key_drops_the_rows_the_host_feed_drops(gpu, kind):
+    """test_nulls_in_a_droppable_key_... for every kind, in three calls (1, 8191 and the rest: every later destination misaligned): bytes under NULL
+    Utf8 rows go through take_tail_kernel and offsets_rebase_kernel, a_s and a_s2 through one take of several Utf8 columns"""
+    n = BIG
+    tables = _tables(kind, n)
+
+    def feed(run, t, table):
+        rows = len(next(iter(table.values())))
+        for _, lo, hi in (BATCHINGS["three_calls"] if rows == n else [("d", 0, rows)]):
+            run.device(t, table, lo, hi, validity="always", poison=_far(kind))
+    got, ran = _profiled(gpu, lambda: _fed(gpu, kind, tables, feed))
+    host = _fed(gpu, kind, tables, lambda run, t, table: run.host(t, table))
+    assert len(got) == len(host) and got == host == _want(kind, n)
+    _check_route(kind, ran)
+
+
+@pytest.mark.gpu
+def test_borrowed_columns_over_far_poison_are_read_in_place(gpu):
+    """filter_plain fed with borrow=True: the leaf reads the caller's tensors -- poisoned slots, bytes under NULL texts and all -- without a copy"""
+    n = T + 16
+    table = _tables("filter_plain", n)[0]
+    plan = u.plan_of("filter_plain")[0]
+    run = u.Run(gpu, plan)
+    try:
+        held, ran = _profiled(gpu, lambda: run.device(0, table, borrow=True, poison=_far("filter_plain")))
+        assert "feed_census_kernel" in ran and not ran & {"offsets_rebase_kernel", "take_tail_kernel"}, sorted(ran)
+        assert run.rows() == _want("filter_plain", n)
+        assert any(None in r for r in _want("filter_plain", n))
+        del held
+    finally:
+        run.close()
+
+
 @pytest.mark.gpu
 def test_validity_arrives_with_a_column_that_reaches_the_output(gpu):
     """a first batch without a NULL anywhere, then one with: the earlier rows are back-filled as valid"""

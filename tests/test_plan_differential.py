@@ -5,7 +5,11 @@ its bits, Timestamp as Int64, Utf8 as bytes.
 
 The CPU tests hold the interpreter to what is already pinned (the reference's transcribed vectors, every *_ref module on its own table), every case
 of the corpus to `explain` (no refusal) and to the interpreter (no NotImplementedError), and every quirk of plan_interp.QUIRKS to at least one case of
-the stratum named next to it that tells it from the true rule."""
+the stratum named next to it that tells it from the true rule.
+
+What lies under a NULL is tests/null_poison.py's: the same cases run once more with near and far values in every NULL slot of every fed column
+(validity alone decides), after the CPU tests have shown that those values, read, would change the answer; literal plans put what FAILS a live row
+under NULLs."""
 import functools
 import json
 import os
@@ -15,6 +19,7 @@ import numpy as np
 import pyarrow as pa
 import pytest
 
+import null_poison as npz
 import plan_corpus as pc
 import plan_interp as pi
 from oracle import generic_ops as g
@@ -383,6 +388,196 @@ def _text_kind(e):
     return None
 
 
+# ------------------------------------------------------------------ CPU 2b: what lies under a NULL (tests/null_poison.py)
+NULL_STRATA = [s for s in pc.STRATA if s not in pc.ERROR_STRATA]
+POISON_TYPES = ("Int32", "Int64", "UInt64", "Timestamp", "Float64", "Utf8")
+
+
+def _keys_of(stratum):
+    return [(stratum, seed, i) for seed in SEEDS for i in range(pc.CASES_PER_SEED)]
+
+
+def _rows_of_case(key):
+    return max(len(next(iter(t.values()))) for t in _case(*key).tables)
+
+
+def _unmasked_tables(key, pool, only=None):
+    """the case's tables with every NULL (of the columns of type `only`, or of every column) replaced by its poison AS A LIVE VALUE; None where that
+    changes nothing (no such NULL)"""
+    c = _case(*key)
+    out, changed = [], False
+    for leaf, (fields, t) in enumerate(zip(pi.leaf_schemas(c.plan), c.tables)):
+        u = dict(t)
+        for f in fields:
+            if (only is None or npz.type_name(f["data_type"]) == only) and any(v is None for v in t[f["name"]]):
+                u[f["name"]] = npz.unmasked(pool, key, leaf, f["name"], t[f["name"]], f["data_type"])
+                changed = True
+        out.append(u)
+    return out if changed else None
+
+
+@functools.lru_cache(maxsize=None)
+def _detects(key, pool, only=None):
+    """would the interpreter's answer change (or the run fail) if the poison of this pool were read as values?"""
+    c = _case(*key)
+    tables = _unmasked_tables(key, pool, only)
+    if tables is None:
+        return False
+    try:
+        rows = run_plan(c.plan, tables)[2]
+    except Exception:                                             # ExprError from a divisor or a cast, OverflowError from a date beyond datetime, ...
+        return True
+    a, b = _norm(rows), _norm(_want(*key)[2])
+    return (a != b) if c.ordered else (_multiset(a) != _multiset(b))
+
+
+def test_the_far_pool_holds_what_it_promises():
+    from test_plan_like import reference_like
+    import parse_text_ref as ptref
+    far = npz.FAR
+    for pattern in pc.LIKES:
+        assert pattern == "" or any(reference_like(s, pattern) for s in far["Utf8"]), pattern
+    assert {len(s) for s in far["Utf8"]} >= {17, 70} and {b"12x", b"99999999999999999999", b"a/b/c", b"\xff\xfe", b"\x80", b"\xe2\x82"} <= set(far["Utf8"])
+    for s in (b"\xff\xfe", b"\x80", b"\xe2\x82"):
+        with pytest.raises(UnicodeDecodeError):
+            s.decode()
+    assert all(ptref.parse_one(s, t) is None for s in ("12x", "99999999999999999999") for t in ptref.TARGETS)
+    assert {-2**31, 2**31 - 1, -1, 0x55555555, 0} <= set(far["Int32"]) and {-2**63, 2**63 - 1, -1, 0x5555555555555555, 2**40, 0} <= set(far["Int64"])
+    assert {0, 2**64 - 1, 0x5555555555555555, 2**40} <= set(far["UInt64"])
+    assert {pc.TS_MAX + 1, pc.TS_MIN - 1, -2**63, 2**63 - 1, 0} <= set(far["Timestamp"])
+    bits = {struct.unpack("<Q", struct.pack("<d", v))[0] for v in far["Float64"]}
+    assert bits >= {0x7FF8000000000000, 0xFFF8000000000000, 0x7FF0000000000000, 0xFFF0000000000000, 0x8000000000000000, 1, 0x7FEFFFFFFFFFFFFF, 0}
+
+
+@pytest.mark.parametrize("stratum", pc.STRATA)
+def test_poisoned_batches_read_as_the_plain_ones_and_differ_in_their_buffers(stratum):
+    """for every case and both pools: every poisoned column equals the plain one as Arrow compares (and by to_pylist() in the cases of at most 9000
+    rows), null_count is the number of Nones, the array validates in full -- bytes that are no UTF-8 under a NULL included --, and its buffers DIFFER
+    from pyarrow's: asserted for every column with at least 8 NULLs under far (a draw of 0 is one of five at the most) and with at least 32 NULLs
+    and a live value other than 0 / '' under near (a near pool is the live values and 0).  No near poison moves the minimum or maximum over all
+    slots; slot() agrees with slots(); the slots do not depend on how the table is cut"""
+    for key in _keys_of(stratum):
+        c = _case(*key)
+        small = _rows_of_case(key) <= 9000
+        plain = _batches(c.plan, c.tables, [None] * len(c.tables))
+        for pool in npz.POOLS:
+            got = _batches(c.plan, c.tables, [None] * len(c.tables), poison=(pool, key))
+            for leaf, (fields, t) in enumerate(zip(pi.leaf_schemas(c.plan), c.tables)):
+                a, b = plain[leaf][0], got[leaf][0]
+                assert a.schema == b.schema
+                for f, x, y in zip(fields, a.columns, b.columns):
+                    where = (key, pool, f["name"])
+                    vals = t[f["name"]]
+                    ty = npz.type_name(f["data_type"])
+                    y.validate(full=True)
+                    assert y.null_count == x.null_count == sum(v is None for v in vals), where
+                    if ty == "Float64" or small:                  # (Arrow's equals takes a live NaN for unequal to itself; datetime ends before the far timestamps)
+                        x64, y64 = (x.cast(pa.int64()), y.cast(pa.int64())) if ty == "Timestamp" else (x, y)
+                        a_list, b_list = y64.to_pylist(), x64.to_pylist()
+                        assert (_norm([tuple(a_list)]) == _norm([tuple(b_list)])) if ty == "Float64" else (a_list == b_list), where
+                    if ty != "Float64":
+                        assert y.equals(x), where
+                    if not y.null_count:
+                        continue
+                    live = [v for v in vals if v is not None and v == v]
+                    if y.null_count >= (8 if pool == "far" else 32) and (pool == "far" or any(v not in (0, "") for v in live)):
+                        assert [bytes(m) for m in y.buffers()[1:]] != [bytes(m) for m in x.buffers()[1:]], where
+                    if not small:
+                        continue
+                    under = npz.slots(pool, *key, leaf, f["name"], vals, ty)
+                    if pool == "near" and ty != "Utf8" and live:
+                        s = [v for v in under if v == v]
+                        assert min(s) == min(live) and max(s) == max(live), where
+                    k = vals.index(None)
+                    assert _norm([(npz.slot(pool, *key, leaf, f["name"], k, vals, ty),)]) == _norm([(under[k],)]), where
+        if not small:
+            continue
+        cut = _batches(c.plan, c.tables, c.batch_cuts, poison=("far", key))
+        whole = _batches(c.plan, c.tables, [None] * len(c.tables), poison=("far", key))
+        for bs, w in zip(cut, whole):
+            for j, col in enumerate(w[0].columns):
+                parts = [b.column(j) for b in bs]
+                at = 2 if pa.types.is_string(col.type) else 1
+                assert pa.concat_arrays(parts).null_count == col.null_count, key
+                assert b"".join(p.buffers()[at].to_pybytes() for p in parts) == col.buffers()[at].to_pybytes(), key
+
+
+SENSITIVITY_PER_SEED, SENSITIVITY_PER_STRATUM = 2, 12
+
+
+@pytest.mark.parametrize("stratum", NULL_STRATA)
+def test_the_poison_would_change_the_answer_if_it_were_read(stratum):
+    """Sensitivity: what makes test_gpu_ignores_what_lies_under_a_null mean something.  Every None of a case's tables is replaced by its poison AS A
+    LIVE VALUE and the interpreter runs the case: it must give another result than _want, or raise.  Such a case `detects` (under either pool: the
+    GPU test feeds both).  Asserted: every (stratum, seed) has at least 2 detecting cases of 6, every stratum at least 12 of 24.
+
+    The cases are tried smallest first and the count stops where both floors are met, which keeps the two cases of 20 011 and 32 769 rows out of
+    most strata; all four seeds are checked.  The full counts, from a run without that stop (cases of 24 detecting under near, under far, under
+    either; then the cases of 6 per seed 0 .. 3 under either):
+
+    stratum          near far either  per seed (either)
+    filter_project     17  19     19  4 6 4 5
+    text               17  16     17  4 4 5 4
+    group_narrow       18  18     18  5 5 5 3
+    group_composite    20  21     21  5 6 6 4
+    group_wide         23  23     23  6 6 5 6
+    distinct_count     19  21     21  5 6 5 5
+    global_agg         11  16     16  4 4 6 2
+    join_inner         23  22     23  6 6 5 6
+    join_semi_anti     23  21     23  6 6 6 5
+    sort_limit         22  22     22  5 5 6 6
+    window             22  22     22  6 6 5 5
+    cross              16  19     19  5 5 5 4
+    mixed              21  21     22  6 5 6 5
+    union              23  23     23  6 6 6 5
+    cast_text          23  23     23  6 6 5 6
+    parse_text         17  16     18  5 4 4 5
+    float_special      24  24     24  6 6 6 6
+
+    The minimum per (stratum, seed) is 2 (global_agg seed 3), per stratum 16 (global_agg)."""
+    per_seed, total = {seed: 0 for seed in SEEDS}, 0
+    for key in sorted(_keys_of(stratum), key=_rows_of_case):
+        if total >= SENSITIVITY_PER_STRATUM and min(per_seed.values()) >= SENSITIVITY_PER_SEED:
+            break
+        if _detects(key, "far") or _detects(key, "near"):
+            per_seed[key[1]] += 1
+            total += 1
+    assert min(per_seed.values()) >= SENSITIVITY_PER_SEED and total >= SENSITIVITY_PER_STRATUM, (stratum, per_seed, total)
+
+
+def test_every_type_has_a_case_that_detects_its_poison_alone():
+    """One column type unmasked at a time, over the cases of at most 9000 rows: for every type and each pool some case of the corpus detects.
+    The count of detecting cases per (stratum, type), near / far, of the 22 cases of at most 9000 rows, from a full run:
+
+    stratum          Int32     Int64     UInt64    Timestamp Float64   Utf8
+    filter_project   10 / 12   0 / 0     0 / 0     10 / 10   5 / 5     6 / 8
+    text             4 / 4     2 / 2     0 / 0     0 / 0     2 / 1     14 / 14
+    group_narrow     11 / 11   7 / 7     4 / 4     3 / 3     4 / 4     0 / 0
+    group_composite  12 / 12   3 / 3     7 / 7     7 / 8     6 / 6     13 / 13
+    group_wide       13 / 13   17 / 17   11 / 12   13 / 13   8 / 8     3 / 3
+    distinct_count   11 / 12   8 / 8     2 / 4     1 / 1     0 / 0     6 / 11
+    global_agg       2 / 2     6 / 6     2 / 7     0 / 7     6 / 7     0 / 0
+    join_inner       17 / 16   13 / 11   3 / 2     12 / 12   12 / 12   14 / 13
+    join_semi_anti   3 / 3     20 / 18   0 / 0     0 / 0     0 / 0     16 / 16
+    sort_limit       8 / 8     13 / 13   1 / 1     0 / 0     5 / 5     8 / 8
+    window           18 / 18   15 / 15   7 / 8     3 / 4     6 / 6     0 / 0
+    cross            11 / 11   10 / 12   0 / 0     7 / 7     8 / 8     10 / 10
+    mixed            17 / 14   10 / 9    0 / 0     0 / 0     4 / 6     5 / 5
+    union            17 / 18   14 / 15   5 / 5     1 / 1     2 / 2     20 / 20
+    cast_text        16 / 16   16 / 16   9 / 9     12 / 12   2 / 2     8 / 8
+    parse_text       3 / 3     4 / 4     4 / 4     4 / 4     0 / 0     13 / 10
+    float_special    0 / 0     10 / 10   0 / 0     0 / 0     22 / 22   0 / 0
+
+    A pair with 0 / 0 is a stratum whose plans read no column of that type, or none that holds a NULL; the corpus is not bent to fill them:
+    filter_project x Int64, filter_project x UInt64, text x UInt64, text x Timestamp, group_narrow x Utf8, distinct_count x Float64,
+    global_agg x Utf8, join_semi_anti x UInt64, join_semi_anti x Timestamp, join_semi_anti x Float64, sort_limit x Timestamp, window x Utf8,
+    cross x UInt64, mixed x UInt64, mixed x Timestamp, parse_text x Float64, float_special x Int32, float_special x UInt64,
+    float_special x Timestamp, float_special x Utf8."""
+    for ty in POISON_TYPES:
+        for pool in npz.POOLS:
+            assert any(_detects(key, pool, ty) for s in NULL_STRATA for key in sorted(_keys_of(s), key=_rows_of_case) if _rows_of_case(key) <= 9000), (ty, pool)
+
+
 @pytest.mark.parametrize("stratum", pc.STRATA)
 def test_every_case_explains_and_evaluates(stratum):
     """zero refusals from flockgpu_plan_explain, no NotImplementedError from the interpreter; a case of an error stratum raises ExprError and nothing
@@ -466,17 +661,22 @@ def gpu():
     c.close()
 
 
-def _batches(plan, tables, cuts_per_table):
-    """per leaf (in the interpreter's leaf order) the list of record batches: one batch, or one per pair of neighbouring cuts"""
+def _batches(plan, tables, cuts_per_table, poison=None):
+    """per leaf (in the interpreter's leaf order) the list of record batches: one batch, or one per pair of neighbouring cuts.  poison: None -- what
+    pyarrow writes under a NULL (0, an empty range) --, or (pool, (stratum, seed, i)): what tests/null_poison.py puts there"""
     out = []
-    for fields, t, cuts in zip(pi.leaf_schemas(plan), tables, cuts_per_table):
+    for leaf, (fields, t, cuts) in enumerate(zip(pi.leaf_schemas(plan), tables, cuts_per_table)):
         n = len(t[fields[0]["name"]])
         cuts = cuts or [0, n]
         bs = []
+        under = {f["name"]: npz.slots(poison[0], *poison[1], leaf, f["name"], t[f["name"]], f["data_type"]) for f in fields} if poison is not None else None
         for a, b in zip(cuts[:-1], cuts[1:]):
             arrs = []
             for f in fields:
                 ty = _arrow(f["data_type"])
+                if poison is not None:                           # (a row's poison does not depend on the cut)
+                    arrs.append(npz.poisoned_array(under[f["name"]][a:b], [v is not None for v in t[f["name"]][a:b]], f["data_type"]))
+                    continue
                 arrs.append(pa.array(t[f["name"]][a:b], pa.int64()).cast(ty) if pa.types.is_timestamp(ty) else pa.array(t[f["name"]][a:b], ty))
             bs.append(pa.record_batch(arrs, names=[f["name"] for f in fields]))
         out.append(bs)
@@ -515,17 +715,23 @@ def _compare(gpu, key, ran_all):
         schema, got, ran = _execute(gpu, c.plan, _batches(c.plan, c.tables, cuts), pc.generic_only(*key))
         ran_all |= ran
         where = "case%r %s (%s), generic_only=%s\n%s" % (key, how, c.note, pc.generic_only(*key), explain(c.plan))
-        if schema is not None:
-            assert schema.names == names, where
-            assert [f.type for f in schema] == [_arrow(t) for t in types], where
-        else:
-            assert not rows, where
-        got = _norm(got)
-        if not c.ordered:
-            got = _multiset(got)
-        if got != want:
-            diff = [(k, a, b) for k, (a, b) in enumerate(zip(got, want)) if a != b][:3]
-            pytest.fail("%d rows, %d expected; first differing (position, got, expected): %r\n%s" % (len(got), len(want), diff or (got[len(want):][:3], want[len(got):][:3]), where))
+        _check_rows(key, schema, got, want, where)
+
+
+def _check_rows(key, schema, got, want, where):
+    """a result against the interpreter's: names and types where a batch came back, the rows (`want` normalised, and sorted where the case is not ordered)"""
+    names, types, rows = _want(*key)
+    if schema is not None:
+        assert schema.names == names, where
+        assert [f.type for f in schema] == [_arrow(t) for t in types], where
+    else:
+        assert not rows, where
+    got = _norm(got)
+    if not _case(*key).ordered:
+        got = _multiset(got)
+    if got != want:
+        diff = [(k, a, b) for k, (a, b) in enumerate(zip(got, want)) if a != b][:3]
+        pytest.fail("%d rows, %d expected; first differing (position, got, expected): %r\n%s" % (len(got), len(want), diff or (got[len(want):][:3], want[len(got):][:3]), where))
 
 
 @pytest.mark.gpu
@@ -555,6 +761,203 @@ def test_gpu_fails_the_call_on_the_one_bad_row_and_is_correct_afterwards(gpu, st
                 _execute(gpu, c.plan, _batches(c.plan, c.tables, cuts), pc.generic_only(*key))
             assert e.value.code == _ffi.ERR_INVALID, (key, c.note, str(e.value))
         _compare(gpu, ("filter_project", seed, 3), ran)          # the next case on the same GpuContext is correct
+
+
+# ------------------------------------------------------------------ GPU: what lies under a NULL
+# Kernels of MUST_RUN that a near-poisoned whole feed may leave out, each with its reason.  Poison can legitimately change a route that depends on
+# the DATA (uniqueness of a build side, strictly increasing keys); everything else that goes missing is a failure.
+POISON_ROUTE_EXCEPTIONS = {
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("stratum", NULL_STRATA)
+def test_gpu_ignores_what_lies_under_a_null(gpu, stratum, seed):
+    """test_gpu_equals_the_interpreter with every NULL slot of every fed column holding tests/null_poison.py's values: every case fed whole, once
+    with the near pool and once with the far pool, compared EXACTLY with the unchanged _want -- validity alone decides what is NULL.  That it would
+    show is test_the_poison_would_change_the_answer_if_it_were_read.  Under near poison (which leaves every column's minimum and maximum where
+    they were) the kernels of MUST_RUN must still run, POISON_ROUTE_EXCEPTIONS apart; under far poison what ran is printed."""
+    from flock_amd.runtime import explain
+    ran = {pool: set() for pool in npz.POOLS}
+    for i in range(pc.CASES_PER_SEED):
+        key = (stratum, seed, i)
+        c = _case(*key)
+        want = _norm(_want(*key)[2])
+        if not c.ordered:
+            want = _multiset(want)
+        for pool in npz.POOLS:
+            feeds = _batches(c.plan, c.tables, [None] * len(c.tables), poison=(pool, key))
+            schema, got, r = _execute(gpu, c.plan, feeds, pc.generic_only(*key))
+            ran[pool] |= r
+            _check_rows(key, schema, got, want, "case%r %s poison (%s), generic_only=%s\n%s" % (key, pool, c.note, pc.generic_only(*key), explain(c.plan)))
+    for pool in npz.POOLS:
+        print("\n%s seed %d %s poison ran: %s" % (stratum, seed, pool, " ".join(sorted(ran[pool]))))
+    excused = POISON_ROUTE_EXCEPTIONS.get(stratum, {})
+    missing = [k for k in pc.MUST_RUN[stratum] if k not in excused and not any(name.startswith(k) for name in ran["near"])]
+    assert not missing, (stratum, seed, missing, sorted(ran["near"]))
+
+
+# ------------------------------------------------------------------ GPU: a failing value under a NULL fails nothing (literal plans and tables)
+HOSTILE_ROWS = (65, 4097)
+_TS0 = 1_436_918_400_000
+
+
+def _hostile_cases():
+    """name -> (columns, expression, its type, {column: value of live row k}, the column that holds the NULLs, what lies under them, {column: value
+    beside a NULL row}, does a live row with that value fail the call).  `safe` in a name: the try_cast_expr form (a live row gives NULL there)."""
+    out = {}
+    ab32, ab64 = [("id", "Int64"), ("a", "Int32"), ("b", "Int32")], [("id", "Int64"), ("a", "Int64"), ("b", "Int64")]
+    c = lambda cols, name: pc.col(name, cols)
+    live_ab = {"a": lambda k: k * 3 - 100, "b": lambda k: k % 5 + 1}
+    out["a / b over a zero divisor"] = (ab32, pc.binop(c(ab32, "a"), "Divide", c(ab32, "b")), "Int32", live_ab, "b", 0, {}, True)
+    out["a % b over a zero divisor"] = (ab64, pc.binop(c(ab64, "a"), "Modulo", c(ab64, "b")), "Int64", live_ab, "b", 0, {}, True)
+    out["INT_MIN under a NULL over -1"] = (ab32, pc.binop(c(ab32, "a"), "Divide", c(ab32, "b")), "Int32", live_ab, "a", -2**31, {"b": -1}, True)
+    out["-1 under a NULL below INT_MIN"] = (ab32, pc.binop(c(ab32, "a"), "Divide", c(ab32, "b")), "Int32", live_ab, "b", -1, {"a": -2**31}, True)
+    out["INT64_MIN % -1 under a NULL"] = (ab64, pc.binop(c(ab64, "a"), "Modulo", c(ab64, "b")), "Int64", live_ab, "b", -1, {"a": -2**63}, True)
+    for safe in (False, True):
+        tag = " (safe)" if safe else ""
+        cols = [("id", "Int64"), ("l", "Int64")]
+        out["Int64 to Int32 over 2^40" + tag] = (cols, pc.cast(c(cols, "l"), "Int32", safe), "Int32", {"l": lambda k: k * 1000 - 5}, "l", 2**40, {}, not safe)
+        cols = [("id", "Int64"), ("f", "Float64")]
+        for what, v in (("NaN", float("nan")), ("1e300", 1e300)):
+            out["Float64 to Int64 over %s%s" % (what, tag)] = (cols, pc.cast(c(cols, "f"), "Int64", safe), "Int64", {"f": lambda k: k / 4 - 9}, "f", v, {}, not safe)
+        cols = [("id", "Int64"), ("s", "Utf8")]
+        for ty in ("Int32", "Int64", "UInt64"):
+            out["Utf8 to %s over '12x'%s" % (ty, tag)] = (cols, pc.cast(c(cols, "s"), ty, safe), ty, {"s": lambda k: str(k * 7)}, "s", b"12x", {}, not safe)
+        out["Utf8 to Timestamp over '12x'" + tag] = (cols, pc.cast(c(cols, "s"), "ts", safe), "ts", {"s": lambda k: "2015-03-%02d" % (k % 28 + 1)}, "s", b"12x", {}, not safe)
+        cols = [("id", "Int64"), ("t", "ts")]
+        out["Timestamp to Utf8 over the year 10000" + tag] = (cols, pc.cast(c(cols, "t"), "Utf8", safe), "Utf8", {"t": lambda k: _TS0 + 86_399_123 * k}, "t", pc.TS_MAX + 1, {}, not safe)
+    # no status of the dialect: sqrt of a negative is NaN, date_trunc has no range check (and Python's datetime ends before INT64_MIN: nothing to expect
+    # of a live row) -- the NULL rows must still come out NULL, whatever the slot would have given
+    cols = [("id", "Int64"), ("f", "Float64")]
+    out["sqrt over -1"] = (cols, pc.fn("sqrt", "Float64", c(cols, "f")), "Float64", {"f": lambda k: k / 4}, "f", -1.0, {}, False)
+    cols = [("id", "Int64"), ("t", "ts")]
+    out["date_trunc over INT64_MIN"] = (cols, pc.fn("date_trunc", "ts", pc.lit("Utf8", "month"), c(cols, "t")), "ts", {"t": lambda k: _TS0 + 86_399_123 * k}, "t", -2**63, {}, None)
+    return out
+
+
+HOSTILE = _hostile_cases()
+
+
+def _hostile_rows(n):
+    return sorted({k for k in range(n) if k % 7 == 3} | {k for k in (0, 63, 64, 4095, 4096, n - 1) if k < n})
+
+
+def _hostile_tables(name, n):
+    """-> (the table with None in the NULL rows, the same with what lies under them as live values, per column its slots)"""
+    cols, _, _, live, null_col, slot, beside, _ = HOSTILE[name]
+    at = set(_hostile_rows(n))
+    masked, unmasked = {"id": list(range(n))}, {"id": list(range(n))}
+    for col, make in live.items():
+        vals = [beside[col] if (k in at and col in beside) else make(k) for k in range(n)]
+        masked[col] = [None if (k in at and col == null_col) else v for k, v in enumerate(vals)]
+        unmasked[col] = [slot if (k in at and col == null_col) else v for k, v in enumerate(vals)]
+    return masked, unmasked
+
+
+def _hostile_plans(name):
+    """the expression as a projected column, and as a filter's predicate (IS NOT NULL of it: a computed leaf, the general evaluator)"""
+    cols, e, ty, _, _, _, _, _ = HOSTILE[name]
+    a = pc.scan(cols)
+    return {"projection": pc.proj(a, [(a.c("id"), "id", "Int64"), (e, "e", ty)]).plan,
+            "filter": pc.keep(pc.filt(a, {"physical_expr": "is_not_null_expr", "arg": e}), ["id"]).plan}
+
+
+def _hostile_batch(name, n, all_valid):
+    """the record batch: the slots hold the unmasked table's values, the validity is the masked table's (or all 1)"""
+    cols = HOSTILE[name][0]
+    masked, unmasked = _hostile_tables(name, n)
+    arrs = []
+    for col, ty in cols:
+        slots = [v.encode() if isinstance(v, str) else v for v in unmasked[col]]
+        arrs.append(npz.poisoned_array(slots, [all_valid or v is not None for v in masked[col]], ty))
+    return [[pa.record_batch(arrs, names=[col for col, _ in cols])]]
+
+
+def _as_text(table):
+    return {k: [v.decode() if isinstance(v, bytes) else v for v in vals] for k, vals in table.items()}
+
+
+@pytest.mark.parametrize("name", sorted(HOSTILE))
+def test_the_hostile_slots_are_hostile_to_the_interpreter(name):
+    """CPU: over the masked table every plan evaluates (NULL in, NULL out); with the slots as live values the interpreter raises ExprError exactly
+    where the case says a live row fails -- and, for sqrt, another result (NaN is a value)"""
+    from flock_amd.runtime import explain
+    fails = HOSTILE[name][7]
+    for n in HOSTILE_ROWS[:1]:
+        masked, unmasked = _hostile_tables(name, n)
+        for how, plan in _hostile_plans(name).items():
+            explain(plan)
+            rows = run_plan(plan, [masked])[2]
+            assert len(rows) == (n if how == "projection" else n - len(_hostile_rows(n))), (name, how)
+            if how == "projection":
+                assert [r[1] is None for r in rows] == [k in set(_hostile_rows(n)) for k in range(n)], name
+            if fails:
+                with pytest.raises(g.ExprError):
+                    run_plan(plan, [_as_text(unmasked)])
+            elif name == "sqrt over -1":                         # (a safe cast of a live row gives the NULL the NULL row gives: only the GPU run can tell)
+                assert _norm(run_plan(plan, [_as_text(unmasked)])[2]) != _norm(rows), (name, how)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", HOSTILE_ROWS)
+@pytest.mark.parametrize("name", sorted(HOSTILE))
+def test_a_failing_value_under_a_null_fails_nothing(gpu, name, n):
+    """Every NULL row's slot holds what would fail a live row (a zero divisor, INT_MIN over -1, a value that does not fit the cast, a text that does
+    not parse, a timestamp in the year 10000): as a projected column and under a filter's predicate the call succeeds and equals the interpreter.
+    The same slots with validity all 1 fail the call with FLOCKGPU_ERR_INVALID, as the `errors` strata do -- the slot really is hostile; where the
+    dialect has no status for the value (a safe cast, sqrt of a negative) the all-valid run equals the interpreter over the unmasked table.
+    CAST(Timestamp AS Utf8) under a predicate is outside the dialect: the filter form of that case is refused by name, with and without NULLs."""
+    from flock_amd import FlockGpuError, _ffi
+    fails = HOSTILE[name][7]
+    masked, unmasked = _hostile_tables(name, n)
+    one_nan = lambda rows: [tuple("NaN" if isinstance(v, float) and v != v else v for v in r) for r in rows]      # (the sign of sqrt(-1)'s NaN is the machine's)
+    for how, plan in _hostile_plans(name).items():
+        want = _norm(run_plan(plan, [masked])[2])
+        if how == "filter" and HOSTILE[name][2] == "Utf8":
+            # a text-valued CAST under a predicate is outside the dialect (the general evaluator takes no text): refused by name, NULLs or not
+            for all_valid in (False, True):
+                with pytest.raises(FlockGpuError) as e:
+                    _execute(gpu, plan, _hostile_batch(name, n, all_valid), True)
+                assert e.value.code == _ffi.ERR_UNSUPPORTED and "CAST" in str(e.value), (name, str(e.value))
+            continue
+        _, got, ran = _execute(gpu, plan, _hostile_batch(name, n, False), True)
+        assert _norm(got) == want, (name, how, n, sorted(ran))
+        if fails:
+            with pytest.raises(FlockGpuError) as e:
+                _execute(gpu, plan, _hostile_batch(name, n, True), True)
+            assert e.value.code == _ffi.ERR_INVALID, (name, how, str(e.value))
+        elif fails is False:
+            _, got, _ = _execute(gpu, plan, _hostile_batch(name, n, True), True)
+            assert _norm(one_nan(got)) == _norm(one_nan(run_plan(plan, [_as_text(unmasked)])[2])), (name, how, n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", HOSTILE_ROWS)
+def test_a_matching_value_under_a_null_selects_nothing_in_the_one_pass_predicate(gpu, n):
+    """the leaves of the one-pass predicate program (a column or its remainder against a literal, IN, LIKE, a Utf8 comparison) cannot fail, but they
+    can MATCH: every NULL row's slot satisfies its leaf, and no NULL row is selected.  With validity all 1 every such row is."""
+    cols = [("id", "Int64"), ("i", "Int32"), ("l", "Int64"), ("s", "Utf8"), ("f", "Float64")]
+    a = pc.scan(cols)
+    at = set(_hostile_rows(n))
+    slots = {"id": list(range(n)), "i": [6 if k in at else 1 for k in range(n)], "l": [2**40 if k in at else 5 for k in range(n)],
+             "s": [b"12x" if k in at else b"no" for k in range(n)], "f": [float("inf") if k in at else 0.25 for k in range(n)]}
+    leaves = {"i": pc.binop(a.c("i"), "Eq", pc.lit("Int32", 6)), "i%": pc.binop(pc.binop(a.c("i"), "Modulo", pc.lit("Int32", 3)), "Eq", pc.lit("Int32", 0)),
+              "i in": {"physical_expr": "in_list_expr", "expr": a.c("i"), "list": [pc.lit("Int32", x) for x in (6, 7, 8)], "negated": False},
+              "l": pc.binop(a.c("l"), "Gt", pc.lit("Int64", 100)), "s like": pc.binop(a.c("s"), "Like", pc.lit("Utf8", "1%x")),
+              "s not like": pc.binop(a.c("s"), "NotLike", pc.lit("Utf8", "n_")), "s cmp": pc.binop(a.c("s"), "Lt", pc.lit("Utf8", "2")),
+              "f": pc.binop(a.c("f"), "Gt", pc.lit("Float64", 3.0))}
+    for what, pred in leaves.items():
+        plan = pc.keep(pc.filt(a, pred), ["id"]).plan
+        col = what.split()[0].rstrip("%")
+        for all_valid in (False, True):
+            arrs = [npz.poisoned_array(slots[c], [all_valid or c != col or k not in at for k in range(n)], ty) for c, ty in cols]
+            _, got, ran = _execute(gpu, plan, [[pa.record_batch(arrs, names=[c for c, _ in cols])]], True)
+            assert sorted(r[0] for r in got) == (sorted(at) if all_valid else []), (what, n, all_valid)
+            assert "pred_flag_kernel" in ran or any(k.startswith("strmatch") for k in ran), (what, sorted(ran))
+            table = {c: [None if (not all_valid and c == col and k in at) else (v.decode() if isinstance(v, bytes) else v) for k, v in enumerate(slots[c])] for c, _ in cols}
+            assert sorted(r[0] for r in run_plan(plan, [table])[2]) == sorted(r[0] for r in got), what
 
 
 # ------------------------------------------------------------------ findings, reduced: literal plans and tables, no generator

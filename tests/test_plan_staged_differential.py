@@ -290,9 +290,9 @@ def test_a_partitioned_join_or_aggregate_needs_key_edges_and_a_stage_on_rank_zer
 
 
 # ------------------------------------------------------------------ GPU
-def _relations(c):
-    """one whole RecordBatch per relation of the case, built the way the differential builds its batches"""
-    return {"r%d" % k: bs[0] for k, bs in enumerate(_batches(c.plan, c.tables, [None] * len(c.tables)))}
+def _relations(c, poison=None):
+    """one whole RecordBatch per relation of the case, built the way the differential builds its batches (poison: what lies under the NULLs)"""
+    return {"r%d" % k: bs[0] for k, bs in enumerate(_batches(c.plan, c.tables, [None] * len(c.tables), poison=poison))}
 
 
 def _stripe(rb, r, world):
@@ -378,26 +378,29 @@ def gpu():
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("stratum", STRATA)
 def test_gpu_staged_on_one_device_equals_the_interpreter(gpu, stratum, seed):
-    """every DAG of every case in scope, accepted for a distributed run or not: one instance per stage over whole relations is sound for every DAG"""
+    """every DAG of every case in scope, accepted for a distributed run or not: one instance per stage over whole relations is sound for every DAG.
+    Seed 0 runs once more with tests/null_poison.py's far pool under every NULL of the relations: the hand-over between stages -- the exchange's
+    packing, the hash partitioning -- sees hostile slots too, and validity alone decides"""
     from flock_amd.stages import StagedRun
     for key, dag in _jobs(stratum, seed, False):
         c = _case(*key)
-        relations = _relations(c)
         want = _want_rows(key)[0 if c.ordered else 1]
-        for on_device in (False, True):
-            where = "case%r %s on_device=%s (%s)" % (key, "/".join(dag.rules), on_device, c.note)
-            run = StagedRun(gpu, dag.stages, instances=1, on_device=on_device)
-            try:
-                out = run.run(relations)
-            finally:
-                run.close()
-            _check_schema(out, key, where)
-            got = _norm(rows_of(out))
-            if not c.ordered:
-                got = _multiset(got)
-            if got != want:
-                diff = [(k, a, b) for k, (a, b) in enumerate(zip(got, want)) if a != b][:3]
-                pytest.fail("%d rows, %d expected; first differing (position, got, expected): %r\n%s" % (len(got), len(want), diff or (got[len(want):][:3], want[len(got):][:3]), where))
+        for poison in (None, ("far", key)) if seed == 0 else (None,):
+            relations = _relations(c, poison)
+            for on_device in (False, True):
+                where = "case%r %s on_device=%s poison=%s (%s)" % (key, "/".join(dag.rules), on_device, poison and poison[0], c.note)
+                run = StagedRun(gpu, dag.stages, instances=1, on_device=on_device)
+                try:
+                    out = run.run(relations)
+                finally:
+                    run.close()
+                _check_schema(out, key, where)
+                got = _norm(rows_of(out))
+                if not c.ordered:
+                    got = _multiset(got)
+                if got != want:
+                    diff = [(k, a, b) for k, (a, b) in enumerate(zip(got, want)) if a != b][:3]
+                    pytest.fail("%d rows, %d expected; first differing (position, got, expected): %r\n%s" % (len(got), len(want), diff or (got[len(want):][:3], want[len(got):][:3]), where))
 
 
 # ------------------------------------------------------------------ a row that fails the execute, on one rank of three
