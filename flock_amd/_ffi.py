@@ -215,6 +215,8 @@ SYMBOLS = {
     "flockgpu_take_i64": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "flockgpu_take_utf8": (_i, [_vp, C.POINTER(Utf8), _vp, _i64, C.c_int32, C.POINTER(Utf8), C.POINTER(_i64)]),
     "flockgpu_inclusive_scan_i32": (_i, [_vp, _vp, _i64]),
+    "flockgpu_pane_split": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, C.c_int32, C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(_i64), C.POINTER(_vp)]),
+    "flockgpu_take_u8": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "flockgpu_ipc_pack_body": (_i, [_vp, C.POINTER(IpcBuffer), _i, _vp, _i64, C.POINTER(_i64)]),
     "flockgpu_json_lines_decode": (_i, [_vp, _vp, _i64, C.POINTER(JsonField), _i, C.POINTER(JsonColumn), C.POINTER(_i64)]),
     "flockgpu_json_lines_decode_nullable": (_i, [_vp, _vp, _i64, C.POINTER(JsonNField), _i, C.POINTER(JsonNColumn), C.POINTER(_i64)]),
@@ -290,6 +292,7 @@ SYMBOLS = {
     "flockgpu_plan_ring_state": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i)]),
     "flockgpu_plan_feed_pane": (_i, [_vp, _i, _i64, _vp, C.POINTER(_vp), _i]),
     "flockgpu_plan_prefetch_pane": (_i, [_vp, _i, _i64, _vp, C.POINTER(_vp), _i]),
+    "flockgpu_plan_feed_pane_columns": (_i, [_vp, _i, _i64, C.POINTER(TextColumn), C.c_int32, _i64, C.c_uint32]),
     "flockgpu_plan_partition_scheme": (C.c_char_p, []),
     "flockgpu_plan_check_partition_scheme": (_i, [C.c_char_p]),
     # asynchronous twins of the batched-window calls (one call in flight per ctx)

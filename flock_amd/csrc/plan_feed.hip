@@ -3,8 +3,8 @@
 //   clean_data_sources context.rs:227-254                     -> flockgpu_plan_reset
 // and what this library adds to it: the device-side pane ring (flockgpu_plan_ring_*, flockgpu_plan_feed_pane), the prefetch of the next
 // pane (flockgpu_plan_prefetch_pane), leaves that read another plan's relation or result in place (flockgpu_plan_feed_shared / _from).
-// At the end: device columns into a leaf and a retained result out as device columns (flockgpu_plan_feed_columns / _result_columns; the kernels
-// are plan_source.hip's).
+// At the end: device columns into a leaf, as a whole feed or as a pane of the ring, and a retained result out as device columns
+// (flockgpu_plan_feed_columns / _feed_pane_columns / _result_columns; the kernels are plan_source.hip's).
 // Host-side code only.  Each decision has one owner: check_feed / apply_feed (what a feed is, and doing it), match_schema / check_column
 // (a fed batch against the leaf), reserve_rows (room for an append), add_run / issue_runs (what travels as one copy, and how).
 #include <memory>
@@ -790,6 +790,75 @@ int flockgpu_plan_prefetch_pane(flockgpu_plan *plan, int input, int64_t pane_id,
     return FLOCKGPU_OK;
 }
 
+// The ring's bookkeeping around the feed of one pane, for host batches (flockgpu_plan_feed_pane) and device columns
+// (flockgpu_plan_feed_pane_columns) alike: pane_turn decides whether `pane_id` may be fed now and whether it begins a new pane (nothing changes),
+// pane_begin opens that pane, pane_undo takes the opening back after a feed that failed behind its validation, pane_fed books what a feed appended.
+struct PaneTurn {
+    int64_t pane_id = 0;
+    bool begin = false;
+    // what pane_begin changes, kept so that a feed that fails AFTER its validation (allocation, HIP error, staging) leaves the rows ring as it
+    // was (ADVICE r4).  q5's state ring cannot go back -- the closing pane's rows are folded into its groups by then -- so there a failed
+    // first feed leaves the new pane begun and empty: the same pane id is simply fed again.
+    int ring_n_before = 0;
+    int64_t ring_first_before = 0;
+    bool newest_done_before = false;
+};
+static int pane_turn(flockgpu_plan *plan, const char *who, int64_t pane_id, PaneTurn *turn) {
+    flockgpu_ctx *ctx = plan->ctx;
+    const int64_t newest = plan->ring_first + plan->ring_n - 1;
+    const bool begin = plan->ring_n == 0 || pane_id == newest + 1;
+    if (!begin && pane_id != newest)
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: pane %lld out of order -- the ring holds panes [%lld, %lld], only pane %lld or %lld can be fed", who,
+                    (long long)pane_id, (long long)plan->ring_first, (long long)newest, (long long)newest, (long long)(newest + 1));
+    if (begin && plan->ring_n == plan->ring_ppw)
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: the ring is full (%d panes): flockgpu_plan_reset retires the oldest before pane %lld begins", who,
+                    plan->ring_ppw, (long long)pane_id);
+    turn->pane_id = pane_id;
+    turn->begin = begin;
+    return FLOCKGPU_OK;
+}
+static int pane_begin(flockgpu_plan *plan, PaneTurn *turn) {
+    turn->ring_n_before = plan->ring_n;
+    turn->ring_first_before = plan->ring_first;
+    turn->newest_done_before = plan->ring_newest_done;
+    if (!turn->begin) return FLOCKGPU_OK;
+    if (plan->ring_q5 && plan->ring_n > 0) {   // the pane that closes leaves its groups behind, its rows go
+        FG_TRY(ring_q5_partial(plan));
+        for (auto &ld : plan->leaves) {
+            ld.rows = 0;
+            for (auto &c : ld.cols) c.bytes = 0;
+            ld.pane_rows.clear();
+            ld.pane_bytes.clear();
+        }
+    }
+    if (plan->ring_n == 0) plan->ring_first = turn->pane_id;
+    plan->ring_n += 1;
+    for (size_t l = 0; l < plan->leaves.size(); ++l) {
+        plan->leaves[l].pane_rows.push_back(0);
+        plan->leaves[l].pane_bytes.emplace_back(plan->leaves[l].cols.size(), 0);
+    }
+    if (plan->ring_q5) plan->ring_groups.push_back(0);
+    plan->ring_newest_done = false;
+    return FLOCKGPU_OK;
+}
+static void pane_undo(flockgpu_plan *plan, const PaneTurn &turn) {
+    if (!turn.begin || plan->ring_q5) return;
+    plan->ring_n = turn.ring_n_before;
+    plan->ring_first = turn.ring_first_before;
+    plan->ring_newest_done = turn.newest_done_before;
+    for (auto &l : plan->leaves) {
+        if (!l.pane_rows.empty()) l.pane_rows.pop_back();
+        if (!l.pane_bytes.empty()) l.pane_bytes.pop_back();
+    }
+}
+// The newest pane gained what `ld` holds beyond `before`.
+static void pane_fed(flockgpu_plan *plan, LeafData &ld, const LeafSnapshot &before) {
+    ld.pane_rows.back() += ld.rows - before.rows;
+    for (size_t c = 0; c < ld.cols.size(); ++c) ld.pane_bytes.back()[c] += ld.cols[c].bytes - before.bytes[c];
+    plan->ring_newest_done = false;   // (more rows of the newest pane: its groups are counted again from its rows)
+    if (plan->ring_q5) plan->ring_groups.back() = 0;
+}
+
 int flockgpu_plan_feed_pane(flockgpu_plan *plan, int input, int64_t pane_id, const struct ArrowSchema *schema,
                             const struct ArrowArray *const *batches, int n_batches) {
     if (!plan) return FLOCKGPU_ERR_INVALID;
@@ -798,14 +867,8 @@ int flockgpu_plan_feed_pane(flockgpu_plan *plan, int input, int64_t pane_id, con
     API_CLOCK("feed_pane");
     plan->col_stats.clear();
     if (input < 0 || input >= (int)plan->leaves.size()) return fail(ctx, FLOCKGPU_ERR_INVALID, "feed_pane: bad argument");
-    const int64_t newest = plan->ring_first + plan->ring_n - 1;
-    const bool begin = plan->ring_n == 0 || pane_id == newest + 1;
-    if (!begin && pane_id != newest)
-        return fail(ctx, FLOCKGPU_ERR_INVALID, "feed_pane: pane %lld out of order -- the ring holds panes [%lld, %lld], only pane %lld or %lld can be fed",
-                    (long long)pane_id, (long long)plan->ring_first, (long long)newest, (long long)newest, (long long)(newest + 1));
-    if (begin && plan->ring_n == plan->ring_ppw)
-        return fail(ctx, FLOCKGPU_ERR_INVALID, "feed_pane: the ring is full (%d panes): flockgpu_plan_reset retires the oldest before pane %lld begins",
-                    plan->ring_ppw, (long long)pane_id);
+    PaneTurn turn;
+    FG_TRY(pane_turn(plan, "feed_pane", pane_id, &turn));
     // a pane that flockgpu_plan_prefetch_pane already brought over: its side buffers are appended below, device to device
     const bool from_prefetch = n_batches == 0 && !schema && plan->pre.active && plan->pre.input == input && plan->pre.pane == pane_id;
     if (plan->pre.active && !from_prefetch && plan->pre.input == input)
@@ -823,41 +886,8 @@ int flockgpu_plan_feed_pane(flockgpu_plan *plan, int input, int64_t pane_id, con
         API_CLOCK2(c1, "feed_pane.validate");
         if (n_batches > 0 || schema) FG_TRY(check_feed(plan, input, schema, batches, n_batches, chk));
     }
-    // what `begin` changes, kept so that a feed that fails AFTER its validation (allocation, HIP error, staging) leaves the rows ring as it
-    // was (ADVICE r4).  q5's state ring cannot go back -- the closing pane's rows are folded into its groups by then -- so there a failed
-    // first feed leaves the new pane begun and empty: the same pane id is simply fed again.
-    const int ring_n_before = plan->ring_n;
-    const int64_t ring_first_before = plan->ring_first;
-    const bool newest_done_before = plan->ring_newest_done;
-    auto undo_begin = [&]() {
-        if (!begin || plan->ring_q5) return;
-        plan->ring_n = ring_n_before;
-        plan->ring_first = ring_first_before;
-        plan->ring_newest_done = newest_done_before;
-        for (auto &l : plan->leaves) {
-            if (!l.pane_rows.empty()) l.pane_rows.pop_back();
-            if (!l.pane_bytes.empty()) l.pane_bytes.pop_back();
-        }
-    };
-    if (begin) {
-        if (plan->ring_q5 && plan->ring_n > 0) {   // the pane that closes leaves its groups behind, its rows go
-            FG_TRY(ring_q5_partial(plan));
-            for (auto &ld : plan->leaves) {
-                ld.rows = 0;
-                for (auto &c : ld.cols) c.bytes = 0;
-                ld.pane_rows.clear();
-                ld.pane_bytes.clear();
-            }
-        }
-        if (plan->ring_n == 0) plan->ring_first = pane_id;
-        plan->ring_n += 1;
-        for (size_t l = 0; l < plan->leaves.size(); ++l) {
-            plan->leaves[l].pane_rows.push_back(0);
-            plan->leaves[l].pane_bytes.emplace_back(plan->leaves[l].cols.size(), 0);
-        }
-        if (plan->ring_q5) plan->ring_groups.push_back(0);
-        plan->ring_newest_done = false;
-    }
+    auto undo_begin = [&]() { pane_undo(plan, turn); };
+    FG_TRY(pane_begin(plan, &turn));
     // the leaf's cursors as the pane's feed finds them: what a feed that fails half-way goes back to
     LeafData &ld = plan->leaves[(size_t)input];
     const LeafSnapshot before(ld);
@@ -920,10 +950,7 @@ int flockgpu_plan_feed_pane(flockgpu_plan *plan, int input, int64_t pane_id, con
             return rc_feed;
         }
     }
-    ld.pane_rows.back() += ld.rows - before.rows;
-    for (size_t c = 0; c < ld.cols.size(); ++c) ld.pane_bytes.back()[c] += ld.cols[c].bytes - before.bytes[c];
-    plan->ring_newest_done = false;   // (more rows of the newest pane: its groups are counted again from its rows)
-    if (plan->ring_q5) plan->ring_groups.back() = 0;
+    pane_fed(plan, ld, before);
     return FLOCKGPU_OK;
 }
 
@@ -1075,60 +1102,80 @@ bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t
 
 }  // namespace
 
-int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows, uint32_t flags) {
-    if (!plan) return FLOCKGPU_ERR_INVALID;
+// What columns_check found out about a feed of device columns and columns_apply acts on (FeedCheck's twin; the two halves of
+// flockgpu_plan_feed_columns, which flockgpu_plan_feed_pane_columns runs either side of the ring's begin).
+struct ColumnsCheck {
+    bool nothing = false;                     // no rows: the feed is a no-op
+    std::vector<int> at, utf8_of;             // leaf column -> fed column (-1: not read) / its Utf8 slot in the census (-1: fixed width)
+    std::vector<char> with_valid;             // NULLs that stay -> validity bytes go along
+    std::vector<int64_t> first, add_bytes;    // per Utf8 column: its first byte in the source, the bytes it adds
+    std::vector<flockgpu_utf8> taken;         // per Utf8 column: the surviving rows, when rows are left out
+    const int32_t *keep_rows = nullptr;       // the rows that stay, when rows are left out
+    bool drop = false;
+    int64_t n_keep = 0;
+    int scheme_state = -1;
+};
+
+// Device columns for one leaf, first half: every check of the feed -- the match by name, the census of NULLs and Utf8 byte ranges, the take of the
+// Utf8 survivors -- with nothing of the plan or the leaf changed.  `who` begins the messages.
+static int columns_check(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows, const char *who, ColumnsCheck &ck) {
     flockgpu_ctx *ctx = plan->ctx;
-    if (plan->ring_ppw) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: the plan has an open pane ring (flockgpu_plan_feed_pane, or flockgpu_plan_ring_close first)");
-    if (input < 0 || input >= (int)plan->ir.leaves.size() || n_cols < 0 || (n_cols && !cols) || rows < 0 || (flags & ~(uint32_t)FLOCKGPU_FEED_BORROW))
-        return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: bad argument");
-    if (plan->async_pending) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: an asynchronous execute is in flight (flockgpu_plan_wait first)");
+    ck.nothing = false;
+    if (plan->async_pending) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: an asynchronous execute is in flight (flockgpu_plan_wait first)", who);
     FG_HIP(ctx, hipSetDevice(ctx->device));
     const Leaf &lf = plan->ir.leaves[(size_t)input];
     LeafData &ld = plan->leaves[(size_t)input];
-    if (ld.borrowed && !ld.user_cols) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: input %d shares another plan's relation; reset the plan first", input);
+    if (ld.borrowed && !ld.user_cols) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: input %d shares another plan's relation; reset the plan first", who, input);
     // hash placement: device columns carry no scheme tag -- an untagged batch
-    int scheme_state = plan->scheme_state;
+    int &scheme_state = ck.scheme_state;
+    scheme_state = plan->scheme_state;
     if (lf.co_partitioned && rows > 0) {
         if (scheme_state == 1)
             return fail(ctx, FLOCKGPU_ERR_INVALID,
-                        "plan_feed_columns: mixed hash placement -- this stage was fed partitions tagged '%s' and untagged ones (another engine's hash): "
-                        "every producer of a stage must place rows the same way", kPartitionScheme);
+                        "%s: mixed hash placement -- this stage was fed partitions tagged '%s' and untagged ones (another engine's hash): "
+                        "every producer of a stage must place rows the same way", who, kPartitionScheme);
         scheme_state = 0;
     }
     // the columns the leaf reads, by name (match_schema's rules and messages)
     const size_t n_leaf = lf.schema.size();
-    std::vector<int> at(n_leaf, -1);
+    std::vector<int> &at = ck.at;
+    at.assign(n_leaf, -1);
     for (size_t c = 0; c < n_leaf; ++c) {
         if (!lf.needed[c]) continue;
         for (int32_t i = 0; i < n_cols && at[c] < 0; ++i)
             if (cols[i].name && lf.schema[c].name == cols[i].name) at[c] = i;
-        if (at[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: column '%s' missing from the fed schema", lf.schema[c].name.c_str());
+        if (at[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: column '%s' missing from the fed schema", who, lf.schema[c].name.c_str());
         const flockgpu_text_column &col = cols[at[c]];
         if (!format_ok(lf.schema[c], text_format(col.type)))
-            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: column '%s' has Arrow format '%s', the plan scans %s", lf.schema[c].name.c_str(), text_format(col.type),
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: column '%s' has Arrow format '%s', the plan scans %s", who, lf.schema[c].name.c_str(), text_format(col.type),
                         type_name(lf.schema[c]));
     }
     // (before anything is allocated or launched)
-    if (rows >= (int64_t(1) << 31) || ld.rows + rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than 2^31 rows per relation");
-    if (rows == 0) return FLOCKGPU_OK;
+    if (rows >= (int64_t(1) << 31) || ld.rows + rows >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than 2^31 rows per relation", who);
+    if (rows == 0) {
+        ck.nothing = true;
+        return FLOCKGPU_OK;
+    }
     CensusArgs ca;
-    std::vector<int> census_of(n_leaf, -1), utf8_of(n_leaf, -1);
+    std::vector<int> census_of(n_leaf, -1);
+    std::vector<int> &utf8_of = ck.utf8_of;
+    utf8_of.assign(n_leaf, -1);
     for (size_t c = 0; c < n_leaf; ++c) {
         if (at[c] < 0) continue;
         const flockgpu_text_column &col = cols[at[c]];
         const bool utf8 = lf.schema[c].type == ColType::UTF8;
         if (utf8 ? !col.utf8.offsets : !col.values)
-            return fail(ctx, FLOCKGPU_ERR_INVALID, utf8 ? "plan_feed_columns: Utf8 column '%s' without offsets" : "plan_feed_columns: column '%s' without a data buffer", lf.schema[c].name.c_str());
+            return fail(ctx, FLOCKGPU_ERR_INVALID, utf8 ? "%s: Utf8 column '%s' without offsets" : "%s: column '%s' without a data buffer", who, lf.schema[c].name.c_str());
         if (!aligned_to(utf8 ? (const void *)col.utf8.offsets : col.values, utf8 ? 4 : col_width(lf.schema[c].type)))
-            return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: column '%s' is not aligned to its element size", lf.schema[c].name.c_str());
+            return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: column '%s' is not aligned to its element size", who, lf.schema[c].name.c_str());
         if (col.valid) {
-            if (ca.n_valid == kCensusCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than %d columns with validity bytes", kCensusCols);
+            if (ca.n_valid == kCensusCols) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than %d columns with validity bytes", who, kCensusCols);
             if (lf.null_droppable[c]) ca.droppable |= uint64_t(1) << ca.n_valid;
             ca.valid[ca.n_valid] = col.valid;
             census_of[c] = ca.n_valid++;
         }
         if (utf8) {
-            if (ca.n_utf8 == kCensusUtf8) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: more than %d Utf8 columns", kCensusUtf8);
+            if (ca.n_utf8 == kCensusUtf8) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: more than %d Utf8 columns", who, kCensusUtf8);
             ca.offsets[ca.n_utf8] = col.utf8.offsets;
             utf8_of[c] = ca.n_utf8++;
         }
@@ -1138,25 +1185,34 @@ int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_te
     CensusResult cr;
     FG_TRY(feed_census_begin(ctx, base.c_str(), ca, rows, &cr));
     FG_TRY(feed_census_wait(ctx, cr));
-    bool drop = false;
-    std::vector<char> with_valid(n_leaf, 0);
+    bool &drop = ck.drop;
+    drop = false;
+    std::vector<char> &with_valid = ck.with_valid;
+    with_valid.assign(n_leaf, 0);
     for (size_t c = 0; c < n_leaf; ++c) {
         if (census_of[c] < 0 || cr.nulls(census_of[c]) == 0) continue;   // (validity bytes that are all 1 do not reach the leaf)
         if (lf.null_droppable[c]) drop = true;
+        else if (plan->ring_ppw && plan->ring_q5)   // (check_feed's refusal: q5's ring keeps Partial COUNT groups of plain columns)
+            return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: column '%s' holds NULLs that reach the output; q5's pane ring keeps no validity", who, lf.schema[c].name.c_str());
         else with_valid[c] = 1;
     }
-    const int64_t n_keep = drop ? cr.kept() : rows;
-    std::vector<int64_t> first(n_leaf, 0), add_bytes(n_leaf, 0);
+    int64_t &n_keep = ck.n_keep;
+    n_keep = drop ? cr.kept() : rows;
+    std::vector<int64_t> &first = ck.first, &add_bytes = ck.add_bytes;
+    first.assign(n_leaf, 0);
+    add_bytes.assign(n_leaf, 0);
     for (size_t c = 0; c < n_leaf; ++c) {
         if (utf8_of[c] < 0) continue;
         first[c] = cr.utf8_first(utf8_of[c]);
         add_bytes[c] = cr.utf8_last(utf8_of[c]) - first[c];
-        if (first[c] < 0 || add_bytes[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: the offsets of Utf8 column '%s' decrease", lf.schema[c].name.c_str());
-        if (add_bytes[c] && !cols[at[c]].utf8.data) return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: Utf8 column '%s' without a data buffer", lf.schema[c].name.c_str());
+        if (first[c] < 0 || add_bytes[c] < 0) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: the offsets of Utf8 column '%s' decrease", who, lf.schema[c].name.c_str());
+        if (add_bytes[c] && !cols[at[c]].utf8.data) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: Utf8 column '%s' without a data buffer", who, lf.schema[c].name.c_str());
     }
     // ---- rows with NULLs that may be left out: the row list, and the Utf8 columns taken at it (their byte totals: the take's own wait)
-    const int32_t *keep_rows = nullptr;
-    std::vector<flockgpu_utf8> taken(n_leaf, flockgpu_utf8{nullptr, nullptr});
+    const int32_t *&keep_rows = ck.keep_rows;
+    keep_rows = nullptr;
+    std::vector<flockgpu_utf8> &taken = ck.taken;
+    taken.assign(n_leaf, flockgpu_utf8{nullptr, nullptr});
     if (drop && n_keep > 0) {
         FG_TRY(feed_census_rows(ctx, base.c_str(), cr, rows, n_keep, &keep_rows));
         std::vector<size_t> u8;
@@ -1180,10 +1236,28 @@ int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_te
         for (size_t c = 0; c < n_leaf; ++c) add_bytes[c] = 0;
     }
     for (size_t c = 0; c < n_leaf; ++c)
-        if (utf8_of[c] >= 0 && ld.cols[c].bytes + add_bytes[c] >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "plan_feed_columns: Utf8 column exceeds 2^31 bytes");
+        if (utf8_of[c] >= 0 && ld.cols[c].bytes + add_bytes[c] >= (int64_t(1) << 31)) return fail(ctx, FLOCKGPU_ERR_UNSUPPORTED, "%s: Utf8 column exceeds 2^31 bytes", who);
     // (rows behind columns that are read in place: the leaf gets its own copy of those first -- before anything of the plan's state changes, so that
     // a failure here leaves plan and leaf as they were)
     if (n_keep > 0 && ld.user_cols) FG_TRY(own_user_columns(plan, input));
+    return FLOCKGPU_OK;
+}
+
+// Device columns for one leaf, second half: the checked columns are appended behind the rows the leaf holds NOW (or, FLOCKGPU_FEED_BORROW, read in
+// place).  A failure leaves the leaf's cursors where they were.
+static int columns_apply(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int64_t rows, uint32_t flags, const ColumnsCheck &ck) {
+    flockgpu_ctx *ctx = plan->ctx;
+    const Leaf &lf = plan->ir.leaves[(size_t)input];
+    LeafData &ld = plan->leaves[(size_t)input];
+    const size_t n_leaf = lf.schema.size();
+    const std::vector<int> &at = ck.at, &utf8_of = ck.utf8_of;
+    const std::vector<char> &with_valid = ck.with_valid;
+    const std::vector<int64_t> &first = ck.first, &add_bytes = ck.add_bytes;
+    const std::vector<flockgpu_utf8> &taken = ck.taken;
+    const int32_t *keep_rows = ck.keep_rows;
+    const bool drop = ck.drop;
+    const int64_t n_keep = ck.n_keep;
+    const int scheme_state = ck.scheme_state;
     // ---- every check is behind us: from here on the leaf changes (apply_feed's resets)
     plan->has_retained = false;
     plan->col_stats.clear();
@@ -1269,6 +1343,56 @@ int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_te
     ld.rows += n_keep;
     ld.dropped += rows - n_keep;
     return FLOCKGPU_OK;   // the copies are ordered before the plan's kernels on the ctx stream
+}
+
+int flockgpu_plan_feed_columns(flockgpu_plan *plan, int input, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows, uint32_t flags) {
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    if (plan->ring_ppw)
+        return fail(ctx, FLOCKGPU_ERR_INVALID,
+                    "plan_feed_columns: the plan has an open pane ring (flockgpu_plan_feed_pane / flockgpu_plan_feed_pane_columns, or flockgpu_plan_ring_close first)");
+    if (input < 0 || input >= (int)plan->ir.leaves.size() || n_cols < 0 || (n_cols && !cols) || rows < 0 || (flags & ~(uint32_t)FLOCKGPU_FEED_BORROW))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "plan_feed_columns: bad argument");
+    ColumnsCheck ck;
+    FG_TRY(columns_check(plan, input, cols, n_cols, rows, "plan_feed_columns", ck));
+    if (ck.nothing) return FLOCKGPU_OK;
+    return columns_apply(plan, input, cols, rows, flags, ck);
+}
+
+int flockgpu_plan_feed_pane_columns(flockgpu_plan *plan, int input, int64_t pane_id, const flockgpu_text_column *cols, int32_t n_cols, int64_t rows,
+                                    uint32_t flags) {
+    static const char *const who = "plan_feed_pane_columns";
+    if (!plan) return FLOCKGPU_ERR_INVALID;
+    flockgpu_ctx *ctx = plan->ctx;
+    if (flags & (uint32_t)FLOCKGPU_FEED_BORROW)
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: FLOCKGPU_FEED_BORROW does not go with a pane: the ring outlives the reset that ends a borrow", who);
+    if (flags) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: flags must be 0", who);
+    if (!plan->ring_ppw) return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: the plan has no open pane ring (flockgpu_plan_ring_open)", who);
+    API_CLOCK("feed_pane_columns");
+    if (input < 0 || input >= (int)plan->ir.leaves.size() || n_cols < 0 || (n_cols && !cols) || rows < 0 || (rows > 0 && !cols))
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: bad argument", who);
+    PaneTurn turn;
+    FG_TRY(pane_turn(plan, who, pane_id, &turn));
+    if (plan->pre.active && plan->pre.input == input)
+        return fail(ctx, FLOCKGPU_ERR_INVALID, "%s: pane %lld of input %d was prefetched: feed it with flockgpu_plan_feed_pane(.., NULL, NULL, 0) first", who,
+                    (long long)plan->pre.pane, plan->pre.input);
+    // every check of the feed first: a refused feed must leave the ring as it was
+    ColumnsCheck ck;
+    ck.nothing = true;
+    if (rows > 0 || n_cols > 0) FG_TRY(columns_check(plan, input, cols, n_cols, rows, who, ck));
+    plan->col_stats.clear();
+    FG_TRY(pane_begin(plan, &turn));
+    if (ck.nothing) return FLOCKGPU_OK;   // an empty pane still advances the ring
+    LeafData &ld = plan->leaves[(size_t)input];
+    const LeafSnapshot before(ld);
+    const int rc = columns_apply(plan, input, cols, rows, 0, ck);
+    if (rc != FLOCKGPU_OK) {
+        if (!plan->ring_q5) before.restore(ld);   // (columns_apply went back to these cursors itself; q5's state ring: the begun pane stays begun and empty)
+        pane_undo(plan, turn);
+        return rc;
+    }
+    pane_fed(plan, ld, before);
+    return FLOCKGPU_OK;
 }
 
 int flockgpu_plan_result_columns(const flockgpu_plan *plan, flockgpu_text_column *out, int32_t capacity, int32_t *n_cols, int64_t *rows) {

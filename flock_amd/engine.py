@@ -934,11 +934,36 @@ class GpuContext:
         self._check(self._lib.flockgpu_partition_by_key(self._h, keys.data_ptr(), keys.numel(), C.byref(w), n_parts, C.byref(r)))
         return int(r.rows)
 
+    def pane_split(self, time, hop_ms: int, origin_ms: int = 0, valid=None, max_panes: int = 4096):
+        """Rows -> panes of a hopping window by event time (flockgpu_pane_split; the rules are A-PN1..11 in csrc/panes.hpp): `time` is an int64
+        device tensor of milliseconds, pane(t) = floor((t - origin_ms) / hop_ms).  Returns (first_pane, bounds, rows): `bounds` a numpy int64
+        array of n_panes + 1 entries, `rows` None when the rows are in pane order -- pane first_pane + k is rows [bounds[k], bounds[k + 1]) of
+        the input -- and otherwise an int32 device tensor, a stable permutation: pane first_pane + k is the input rows
+        rows[bounds[k] : bounds[k + 1]].  `valid` (uint8, 0 = NULL): a NULL timestamp refuses the call.  More than `max_panes` panes:
+        FLOCKGPU_ERR_UNSUPPORTED."""
+        torch = _torch()
+        n = int(time.numel())
+        if n and time.dtype != torch.int64:
+            raise ValueError("pane_split: the time column is int64 milliseconds")
+        if valid is not None and valid.numel() != n:
+            raise ValueError(f"pane_split: validity has {valid.numel()} entries for {n} rows")
+        cap = int(max_panes)
+        bounds = np.zeros(max(min(cap, 65536), 1) + 1, dtype=np.int64)
+        first, n_panes, row_list = C.c_int64(0), C.c_int32(0), C.c_void_p()
+        self._check(self._lib.flockgpu_pane_split(self._h, time.data_ptr() if n else None, None if valid is None or not n else valid.data_ptr(), n,
+                                                  int(origin_ms), int(hop_ms), cap, C.byref(first), C.byref(n_panes),
+                                                  bounds.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(row_list)))
+        rows = None
+        if row_list.value:   # the list is the context's until its next call: the caller gets a copy
+            rows = torch.empty(n, dtype=torch.int32, device=time.device)
+            self._check(self._lib.flockgpu_memcpy(self._h, rows.data_ptr(), row_list.value, n * 4, _ffi.D2D))
+        return first.value, bounds[:n_panes.value + 1].copy(), rows
+
     def take(self, src, rows):
-        """out[i] = src[rows[i]] for an int32 / int64 device tensor."""
+        """out[i] = src[rows[i]] for an int32 / int64 / uint8 (validity bytes) device tensor."""
         torch = _torch()
         out = torch.empty(rows.numel(), dtype=src.dtype, device=src.device)
-        fn = {torch.int32: self._lib.flockgpu_take_i32, torch.int64: self._lib.flockgpu_take_i64}[src.dtype]
+        fn = {torch.int32: self._lib.flockgpu_take_i32, torch.int64: self._lib.flockgpu_take_i64, torch.uint8: self._lib.flockgpu_take_u8}[src.dtype]
         self._check(fn(self._h, src.data_ptr(), rows.data_ptr(), rows.numel(), out.data_ptr()))
         return out
 

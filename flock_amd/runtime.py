@@ -187,15 +187,22 @@ class _Plan:
         self.gpu._check(rc)
         return True
 
-    def feed_columns(self, i: int, columns, valid=None, borrow: bool = False):
+    def feed_columns(self, i: int, columns, valid=None, borrow: bool = False, pane: Optional[int] = None):
         """`feed` for rows that already lie in device memory (flockgpu_plan_feed_columns): `columns` = [(name, "int32" | "int64" | "uint64" |
         "float64" | "timestamp_ms" | "utf8", tensor | DeviceUtf8)] and `valid` = {name: uint8 tensor, 1 = not NULL}, csv_encode's argument
         shape -- what csv_decode, json_lines_decode and the device generator leave in HBM.  Columns are matched to the leaf by name, extra
         ones are ignored; the rows append behind what the leaf holds.  `borrow`: the tensors stay as they are until `reset`, and the library
         may read them in place instead of copying (it decides; the result is the same).  Either way this object holds the tensors until
-        `reset`: the library reads them on its own stream."""
+        `reset`: the library reads them on its own stream.  With `pane` the rows are pane `pane` of the plan's device-side window ring
+        (flockgpu_plan_feed_pane_columns; no columns: an empty pane, which still advances the ring); a ring outlives the reset that ends a
+        borrow, so `borrow` does not go with it."""
+        if pane is not None and borrow:
+            raise ValueError("feed_columns: `borrow` does not go with `pane` (the ring outlives the reset that ends a borrow)")
         spec, rows, keep = self.gpu._text_columns(columns, valid, who="feed_columns")
-        rc = self._lib.flockgpu_plan_feed_columns(self.h, i, spec, len(columns), rows, _ffi.FEED_BORROW if borrow else 0)
+        if pane is None:
+            rc = self._lib.flockgpu_plan_feed_columns(self.h, i, spec, len(columns), rows, _ffi.FEED_BORROW if borrow else 0)
+        else:
+            rc = self._lib.flockgpu_plan_feed_pane_columns(self.h, i, pane, spec if columns else None, len(columns), rows, 0)
         self.gpu._check(rc)
         self._fed.append(keep)
         self._base_fed.add(i)
@@ -381,17 +388,36 @@ class ExecutionContext:
                 if hit is not None:
                     yield plan, i, hit
 
-    def feed_device_sources(self, sources, borrow: bool = False):
+    def feed_device_sources(self, sources, borrow: bool = False, pane: Optional[int] = None):
         """feed_data_sources for relations that already lie in device memory: `sources` = [(columns, valid)], each as `_Plan.feed_columns`
         takes them (what csv_decode / event_source return).  Every source goes to every plan leaf whose columns it covers.  `borrow`: the
-        tensors stay unchanged until clean_data_sources, and the library may read them in place.  Returns how many leaves were fed."""
-        if self._ring:
+        tensors stay unchanged until clean_data_sources, and the library may read them in place.  `pane`: with an open window ring the
+        sources are ONE pane (what `device_panes` cuts a batch into).  A pane's rows are copied into the ring, so here a source goes to ONE
+        leaf of a plan -- the first whose columns it covers, feed_data_sources' rule, which is what lets host panes and device panes
+        alternate in one ring (q5's second `bid` scan reads the first's rows either way) -- and a plan that no source matched gets the empty
+        pane, as feed_data_sources(sources, pane) gives it.  Returns how many leaves were fed."""
+        if self._ring and pane is None:
             raise ValueError("feed_device_sources: a window ring takes panes from the host (feed_data_sources(sources, pane))")
+        if pane is not None and not self._ring:
+            raise ValueError("feed_device_sources: `pane` goes with an open window ring")
         fed = 0
-        for plan, i, si in list(self._device_leaf_sources(sources)):
-            columns, valid = sources[si]
-            plan.feed_columns(i, columns, valid, borrow)
-            fed += 1
+        if pane is None:
+            for plan, i, si in list(self._device_leaf_sources(sources)):
+                columns, valid = sources[si]
+                plan.feed_columns(i, columns, valid, borrow)
+                fed += 1
+            return fed
+        schemas = [_columns_schema(columns) for columns, _ in sources]
+        for plan in self.plans:
+            used = set()
+            for i in range(len(plan.inputs)):
+                hit = next((si for si, schema in enumerate(schemas) if si not in used and plan.matches(i, schema)), None)
+                if hit is not None:
+                    used.add(hit)
+                    plan.feed_columns(i, sources[hit][0], sources[hit][1], borrow, pane)
+                    fed += 1
+            if not used and plan.inputs:   # nothing arrived in this pane: the ring still advances
+                plan.feed_columns(0, [], None, False, pane)
         return fed
 
     def result_columns(self, plan: int = 0):
@@ -552,4 +578,49 @@ def collect(ctx: ExecutionContext, streams, pane: Optional[int] = None):
     else:
         out = ctx.execute()
     ctx.clean_data_sources()
+    return out
+
+
+def collect_device(ctx: ExecutionContext, sources, pane: Optional[int] = None):
+    """`collect` for relations that already lie in device memory (`feed_device_sources`): feed -> execute -> clean.  With an open window
+    ring `sources` is ONE pane (an entry of `device_panes`) and the result is the window that pane completes."""
+    ctx.feed_device_sources(sources, pane=pane)
+    if ctx.is_shuffling():
+        out = ctx.execute_partitioned()
+        assert len(out) == 1
+        out = out[0]
+    else:
+        out = ctx.execute()
+    ctx.clean_data_sources()
+    return out
+
+
+def device_panes(gpu: GpuContext, columns, valid, time_column: str, hop_ms: int, origin_ms: int = 0, max_panes: int = 4096):
+    """A batch of device columns cut into the panes of a hopping window by event time (`GpuContext.pane_split` on column `time_column`):
+    [(pane_id, columns_k, valid_k)] for every pane from the first present to the last, panes in between that hold no row included with zero
+    rows -- each entry what `feed_device_sources([(columns_k, valid_k)], pane=pane_id)` takes.  The entries are views of the batch: tensors
+    are sliced, a DeviceUtf8 is sliced with its offsets as they are (the feed rebases them).  Rows that are not in pane order are brought
+    into it first, with ONE take per column and validity column (stable: arrival order is kept inside a pane)."""
+    valid = dict(valid or {})
+    hit = [col for name, _, col in columns if name == time_column]
+    if not hit or isinstance(hit[0], DeviceUtf8):
+        raise ValueError(f"device_panes: no fixed-width column {time_column!r}")
+    first, bounds, rows = gpu.pane_split(hit[0], hop_ms, origin_ms, valid.get(time_column), max_panes)
+    if rows is not None:
+        import torch
+        slot, taken = 0, []
+        for name, t, col in columns:
+            if isinstance(col, DeviceUtf8):
+                col, slot = gpu.take_utf8(col, rows, slot), slot + 1
+            elif t == "float64":
+                col = gpu.take(col.view(torch.int64), rows).view(torch.float64)
+            else:
+                col = gpu.take(col, rows)
+            taken.append((name, t, col))
+        columns, valid = taken, {name: gpu.take(v, rows) for name, v in valid.items()}
+    out = []
+    for k in range(len(bounds) - 1):
+        lo, hi = int(bounds[k]), int(bounds[k + 1])
+        cols_k = [(name, t, DeviceUtf8(col.offsets[lo:hi + 1], col.data) if isinstance(col, DeviceUtf8) else col[lo:hi]) for name, t, col in columns]
+        out.append((first + k, cols_k, {name: v[lo:hi] for name, v in valid.items()}))
     return out

@@ -348,6 +348,30 @@ int flockgpu_q11_user_sessions(flockgpu_ctx *ctx, const flockgpu_bid_cols *bid, 
  * stable.  `keys` is a 16-byte aligned device column; the outputs are ctx-owned device arrays of `rows` entries. */
 int flockgpu_group_rows_by_key(flockgpu_ctx *ctx, const int32_t *keys, int64_t rows, int32_t **out_keys, int32_t **out_rows);
 
+/* ---- event-time panes: a batch of rows cut into the panes of a hopping window by a timestamp column, on the device -- what WindowSchedule
+ * does on the host from the generator's epoch structure, for rows that carry nothing but a timestamp (decoded text).  The rules are
+ * A-PN1..11 in csrc/panes.hpp.
+ *   pane(t) = floor((t - origin_ms) / hop_ms), rounding towards minus infinity, the difference formed exactly; a pane id outside Int64 is
+ *   FLOCKGPU_ERR_INVALID.
+ * *first_pane = the smallest pane id present, *n_panes = the largest minus the smallest plus 1 (panes in between that hold no row included);
+ * bounds[0] = 0 <= bounds[1] <= ... <= bounds[*n_panes] = rows (host, room for capacity + 1 entries).  rows == 0: *n_panes = 0, *first_pane = 0.
+ * Rows in pane order (pane ids never decrease along the rows; timestamps inside a pane in any order -- a time-ordered stream):
+ *   *row_list = NULL and pane *first_pane + k is rows [bounds[k], bounds[k + 1]) of the input itself.  One streaming pass over the 8 bytes a row
+ *   (and the validity bytes), one small launch for the bounds, two host waits; no division per row.
+ * Otherwise *row_list (device, ctx-owned, valid until the next call on the context) is a stable permutation: pane *first_pane + k is the input
+ *   rows row_list[bounds[k] .. bounds[k + 1]), ascending inside the pane.
+ * `time_ms` needs 8-byte alignment, `valid` (one byte per row, 0 = NULL; NULL pointer: no NULLs) none.
+ *   FLOCKGPU_ERR_INVALID      hop_ms <= 0, capacity outside [1, 65536], rows outside [0, 2^31), null pointers, a validity byte of 0 (the message
+ *                             names the first such row, 0-based), a pane id outside Int64;
+ *   FLOCKGPU_ERR_UNSUPPORTED  more than `capacity` panes (the message names the first pane id, the last pane id and the capacity).
+ * A refused call writes nothing to `bounds`. */
+int flockgpu_pane_split(flockgpu_ctx *ctx, const int64_t *time_ms /* device */, const uint8_t *valid /* device, or NULL */,
+                        int64_t rows, int64_t origin_ms, int64_t hop_ms, int32_t capacity,
+                        int64_t *first_pane, int32_t *n_panes, int64_t *bounds /* host, capacity + 1 */,
+                        const int32_t **row_list /* device, ctx-owned; NULL when the rows are in pane order */);
+/* out[i] = src[rows[i]] for one-byte values (validity bytes at a row list); `rows` is 16-byte aligned, `out` caller-allocated. */
+int flockgpu_take_u8(flockgpu_ctx *ctx, const uint8_t *src, const int32_t *rows, int64_t n, uint8_t *out);
+
 /* ---- JSON lines -> columns (the decode step of `select_event_to_batches`,
  * flock/src/datasource/nexmark/nexmark.rs:180-205): the reference keeps an epoch's events as newline-delimited
  * serde_json objects (generator.rs:79-93) and decodes them with arrow's json::Reader against the relation's schema

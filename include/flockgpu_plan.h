@@ -192,7 +192,8 @@ int flockgpu_plan_feed_from(flockgpu_plan *plan, int input, const flockgpu_plan 
  * bytes are 16-byte aligned, offsets[0] is 0 and validity bytes are 4-byte aligned -- and copies otherwise.  Without the flag the columns may
  * be released once the stream has passed the call (flockgpu_plan_reset and every execute wait for it).
  *   FLOCKGPU_ERR_INVALID      bad arguments, an asynchronous execute in flight, a leaf that reads another plan's relation, an open pane ring
- *                             (feed panes with flockgpu_plan_feed_pane), a needed column missing, a column without its buffer;
+ *                             (feed panes with flockgpu_plan_feed_pane / flockgpu_plan_feed_pane_columns), a needed column missing, a column
+ *                             without its buffer;
  *   FLOCKGPU_ERR_UNSUPPORTED  a needed column of another type, 2^31 rows (decided from `rows` before anything is allocated or launched),
  *                             2^31 bytes in a Utf8 column, more than 64 columns with validity bytes or 32 Utf8 columns.
  * A refused call leaves the leaf as it was.
@@ -254,6 +255,24 @@ int flockgpu_plan_feed_pane(flockgpu_plan *plan, int input, int64_t pane_id, con
  * follows the pane's feed; flockgpu_plan_ring_close / flockgpu_plan_destroy drop a prefetch that was never fed. */
 int flockgpu_plan_prefetch_pane(flockgpu_plan *plan, int input, int64_t pane_id, const struct ArrowSchema *schema,
                                 const struct ArrowArray *const *batches, int n_batches);
+/* flockgpu_plan_feed_pane for `rows` rows that already lie in device memory (what the decoders leave in HBM, cut into panes by
+ * flockgpu_pane_split): the ring's rules are flockgpu_plan_feed_pane's, the columns' rules flockgpu_plan_feed_columns'.  The first call names the
+ * first pane; after that only the newest pane (more rows) or its successor (after a flockgpu_plan_reset if the ring is full) may be fed; an older
+ * pane, a skipped pane or a full ring is FLOCKGPU_ERR_INVALID and leaves the ring as it was.  rows == 0 (`cols` may be NULL) is an empty pane: it
+ * still advances the ring.  Host panes and device panes of one ring may alternate, inside one pane too; a pane that
+ * flockgpu_plan_prefetch_pane has pending for `input` must be fed first (FLOCKGPU_ERR_INVALID).  Columns are matched by name, extra ones are
+ * ignored, Int64 and Timestamp(ms) are interchangeable; pointers need only their element's alignment and Utf8 offsets need not start at 0, so a
+ * pane can be a slice of a decoded batch.  An all-1 validity column reaches the ring without validity, rows whose NULL cannot change the result
+ * are left out, every other NULL-carrying column takes its validity bytes along (earlier panes count as valid); q5's state ring refuses NULLs in
+ * a column it needs (FLOCKGPU_ERR_UNSUPPORTED), as the host pane feed does.  What the ring retains is what it retains for host panes: the same
+ * panes fed either way give the same windows.  `flags` must be 0; FLOCKGPU_FEED_BORROW is FLOCKGPU_ERR_INVALID (a ring outlives the reset that
+ * ends a borrow).  The limits and refusals of flockgpu_plan_feed_columns apply (2^31 rows and Utf8 bytes, 64 validity and 32 Utf8 columns, an
+ * asynchronous execute in flight, a leaf that reads another plan's relation); messages begin with "plan_feed_pane_columns:".  The columns may be
+ * released once the stream has passed the call (flockgpu_plan_reset and every execute wait for it).  A call that fails after its validation
+ * leaves the leaf's cursors and the ring where they were -- except on q5's state ring, whose begun pane stays begun and empty (feed the same
+ * pane id again). */
+int flockgpu_plan_feed_pane_columns(flockgpu_plan *plan, int input, int64_t pane_id, const flockgpu_text_column *cols,
+                                    int32_t n_cols, int64_t rows, uint32_t flags);
 
 /* ---- hash placement of a shuffling stage.  flockgpu_plan_execute_partitioned places a row in partition
  *     (murmur3_fmix32(fold32(key)) * n) >> 32
